@@ -14,9 +14,13 @@ rank-0 HOST memory.  Inside it: every new frame goes up through the pinned ring 
 per rank, each field is copied to pinned host memory while the next one computes, and with N > 1 the ranks' fields
 stream to rank 0 in chunked RCCL gathers beside the computation (weak scaling: K fields per rank, no data-path
 collective).  W warm-up fields of the same sliding job run before it, so the timed fields are the steady state of a
-long job (one new frame per field).  `engine_ms_per_step` is the same loop with inputs and outputs left in HBM.
+long job (one new frame per field).
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes the last step's fields if --dump-outputs DIR is given, and
+prints the line.  --full adds, after the timed region, every other figure (--no-cpu-baseline / --no-roofline / --no-jobs
+leave one out):
+  engine_ms_per_step  the same loop with inputs and outputs left in HBM
+  plans         the other arithmetic plan on the next fields of the same job (N=1 only)
   roofline      dominant kernel, from a SEPARATE pass after the timed region (per-launch HIP events on the launch
                 stream perturb the timing, so they never run inside `value`; the encoder prefetch that otherwise runs
                 on a side stream beside the iterations is queued behind the field in this pass): achieved algorithmic TFLOP/s vs the dense
@@ -24,6 +28,12 @@ Extra objects on the line:
                 under profiles/ (a stored constant of that profile run, labelled so); `hbm_kernels`: the lookup
   cpu_baseline  the CPU oracle (oracle/mof_oracle.py, "port") timed on this box's host cores BEFORE the timed region on a
                 bounded sample of the same workload (N=1 only), plus the engine-vs-oracle EPE on it
+  job_300, cli_e2e  the whole job and the drop-in CLI, in fresh child processes (tools/job_bench.py)
+
+--dump-outputs DIR writes DIR/flow.npy: float32 [N, H, W, 2], the field every rank computed in its last timed step (rank
+order), as the job hands it to its caller.  Inputs are the seeded synthetic clip and seeded weights, so equal arguments
+give equal inputs.  Above DUMP_LIMIT_BYTES it is DIR/flow_sample.npy instead: float32 [N, P, 2] at P pixel positions
+drawn without replacement by np.random.default_rng(0) and sorted (row-major index over H x W).
 """
 import argparse
 import json
@@ -45,6 +55,7 @@ import torch  # noqa: E402
 F16_MATRIX_PEAK_TFLOPS = 2500.0
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E, ~8 TB/s
 F32_MATRIX_PEAK_TFLOPS = 157.3
+DUMP_LIMIT_BYTES = 60 * 2 ** 20   # --dump-outputs stays under 64 MB (one 1080p field is 16.6 MB, one 4K field 66 MB)
 
 DTYPE_NOTE = {
     "f16x3": "f16x3 (split-f16 MFMA: 3 f16 MFMAs per product, f32 accumulate, fp32-grade)",
@@ -72,8 +83,14 @@ def main():
     ap.add_argument("--corr-volume", default=None, choices=["f32", "f16", "f16@1", "f16@2", "f16@3"],
                     help="storage of the correlation pyramids (vfml/cfg.py corr_volume; default f32; f16 is the opt-in "
                          "half-size volume, ~1e-4 px against the oracle at 1080p)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true", help="skip the separate per-launch timing pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every figure beside the headline: CPU baseline, engine-only pass, the other "
+                         "arithmetic plan, roofline pass, whole-job figures (off: set up, warm up, time, print)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write every rank's field of the last timed step to DIR/flow.npy "
+                         "(float32 [N,H,W,2]; above 60 MiB a seeded sample of pixels, DIR/flow_sample.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the separate per-launch timing pass")
     ap.add_argument("--full-output", action="store_true",
                     help="compute all 2(T-2) flows of the model output per field instead of the one the reference "
                          "path keeps ([0, shape[1]//2]); the default drops, in the last two iterations, the centre "
@@ -86,8 +103,11 @@ def main():
                          "at 1080p on 16 threads; the line then carries an engine-vs-oracle check at the headline size); "
                          "N = one field on a 16:9 centre crop of that height, scaled to full size by the analytic FLOP ratio")
     ap.add_argument("--no-jobs", action="store_true",
-                    help="skip the whole-job figures (job_300, cli_e2e: fresh child processes, about a minute more)")
+                    help="with --full: skip the whole-job figures (job_300, cli_e2e: fresh child processes, about a "
+                         "minute more)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.workload == "mof4k-tile":
         args.height, args.width = 2160, 3840
@@ -95,11 +115,15 @@ def main():
         args.height, args.width, args.seq = 720, 1280, 9
         # (the tri-frame network computes eight fields per pass of the engine: whole passes only, or the last, partial one
         # - a third of the chip - sets the average: 20 steps 134 fields/s, 24 or 32 steps 174)
-        args.steps = -(-args.steps // 8) * 8
+        if args.steps % 8:
+            ap.error(f"--workload bof720p computes 8 fields per engine pass: --steps must be a multiple of 8, "
+                     f"got {args.steps}")
     elif args.workload == "memflow1080p":
         args.seq = 3
-    if args.workload != "mof1080p":
+    if args.workload != "mof1080p" or not args.full:
         args.no_cpu_baseline = True
+    if not args.full:
+        args.no_roofline = args.no_jobs = True
     if args.full_output:
         os.environ["VFML_FULL_OUTPUT"] = "1"      # read by processing/videoflow_processor.py at import
     # mof1080p runs the EPE-budgeted mixed plan by default (vfml/cfg.py DEFAULT_MIXED_PLAN: mean EPE <= 1e-4 px at
@@ -159,9 +183,9 @@ def main():
     # -- synthetic clip in host memory; one sliding job per rank: W warm-up fields, K timed, P profiled, E engine-only --
     K, Wm, T = args.steps, args.warmup, args.seq
     Pn = 0 if args.no_roofline else min(K, 4)
-    En = min(K, 6)
+    En = min(K, 6) if args.full else 0
     alt_precision = ({"mof1080p": "f16x3", "bof720p": "f16"}.get(args.workload)
-                     if (precision == "mixed" and world == 1) else None)
+                     if (precision == "mixed" and world == 1 and args.full) else None)
     An = (Wm + K + Wm) if alt_precision else 0           # second plan: warm-up + timed, then the first plan's warm-up again
     per_rank = Wm + K + En + An + Pn
     # the job is one clip of world * per_rank fields; every rank holds it in host memory (same synthetic generator on
@@ -213,6 +237,8 @@ def main():
     elapsed = vdist.max_over_ranks(elapsed, dev)
     if rank == 0:
         assert out is not None and out.shape[0] == K * world and np.isfinite(out[-1]).all() and np.isfinite(out[0]).all()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, out[K - 1::K])     # each rank's last timed field (its K fields are contiguous)
     del out, result_buf
 
     # -- engine only: the next fields with inputs and outputs left in HBM ----------------------------------------
@@ -320,7 +346,7 @@ def main():
                                     "skip the centre frames outside its dependency cone (bit-identical for it; "
                                     "--full-output computes all 2(T-2))")},
         "rank0_local_ms_per_step": 1000.0 * t_local / K,
-        "engine_ms_per_step": eng_ms,       # same job, frames already in HBM, fields left in HBM (a separate pass)
+        "engine_ms_per_step": eng_ms,       # --full: same job, frames already in HBM, fields left in HBM (a separate pass)
     }
     if alt is not None:
         result["plans"] = {
@@ -389,6 +415,19 @@ def main():
     print(json.dumps(result))
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(dirpath, fields):
+    """fields: float32 [N, H, W, 2] -> dirpath/flow.npy, or a fixed sample of pixel positions above DUMP_LIMIT_BYTES."""
+    os.makedirs(dirpath, exist_ok=True)
+    fields = np.ascontiguousarray(fields, dtype=np.float32)
+    if fields.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(dirpath, "flow.npy"), fields)
+        return
+    n, h, w, c = fields.shape
+    npix = DUMP_LIMIT_BYTES // (n * c * fields.itemsize)
+    pix = np.sort(np.random.default_rng(0).choice(h * w, size=npix, replace=False))
+    np.save(os.path.join(dirpath, "flow_sample.npy"), fields.reshape(n, h * w, c)[:, pix])
 
 
 def whole_jobs(precision):

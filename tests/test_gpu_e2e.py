@@ -257,7 +257,7 @@ def test_full_size_properties_1080p_and_4k_tiles(gpu):
     caches give bit-identical fields to encoding the window from scratch, a second run is bit-identical
     (no atomics, no order dependence), and the host-array API equals the resident path; at 4K --tile
     (config 3) the runner's pasted frame equals the six tiles computed one by one, ragged edge tiles included.
-    (The oracle comparison at 1080p itself is part of every bench.py run: `cpu_baseline.epe_mean_px`.)"""
+    (The oracle comparison at 1080p itself is part of every `bench.py --full` run: `cpu_baseline.epe_mean_px`.)"""
     import contextlib
     import io
     import numpy as np

@@ -1,4 +1,4 @@
-"""Print the per-layer-shape table of a bench.py JSON line (roofline.all_variants[*].shapes)."""
+"""Print the per-layer-shape table of a `bench.py --full` JSON line (roofline.all_variants[*].shapes)."""
 import json
 import sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -1,5 +1,5 @@
 """Whole-job figures of BASELINE config 2 (MOF_sintel seq 5, 1920x1080, 300-frame synthetic clip) in a FRESH process, for
-bench.py's `job_300` and `cli_e2e` objects (GPU only).  One JSON line on stdout.
+`bench.py --full`'s `job_300` and `cli_e2e` objects (GPU only).  One JSON line on stdout.
 
     python tools/job_bench.py job300            the reference's frame loop (flow_processor.py:959-976: one field per frame of
                                                 the clip, clip-edge windows included) through vfml.runner.run_sharded, host
