@@ -20,6 +20,7 @@
  */
 #ifndef VFML_H
 #define VFML_H
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -404,6 +405,27 @@ int vfml_taa_blend(const void* current, int cur_type, const float* flow, const v
  * ((1 - s), 0, 0) * 255; (255, 0, 0) where the target is outside the image.  SURVEY.md 8(f)-4. */
 int vfml_flow_quality_map(const unsigned char* frame1, const unsigned char* frame2, const float* flow, int fh, int fw,
                           int h, int w, float threshold, unsigned char* out, void* stream);
+
+/* Batch flow-cache correction (reference correction_worker.py: worker_process :221-341), one frame per call, all on
+ * `stream`, no host synchronisation.  frame1, frame2: [h][w][3] u8 RGB; flow: [h][w][2] f32 at the frame's resolution;
+ * lod: [lh][lw][2] f32, the coarsest cached LOD of the frame (the flow itself when there is none); twiddles: device
+ * [2][50] f64, cos and sin of 2 pi m / 50.  Bad pixels are those whose quality map (vfml_flow_quality_map at
+ * good_threshold) has a red byte > 0.  Each is re-estimated by a phase correlation of two 50x50 grey regions around
+ * the pixel and its LOD target; where that similarity is < fine_threshold, by an 11x11 TM_CCOEFF_NORMED match over the
+ * 50-row search area (as wide as the frame where the reference's slice is) and a spiral search; the better result is
+ * written to out_flow (a copy of flow, which it may not alias) when its similarity is > good_threshold or > the
+ * pixel's current one.  counts: device int32[2] <- bad pixels before and after.  Only radii 25 / 5.5 / 25 (region,
+ * template, search) are built.  records: null, or device f64 [record_capacity][VFML_CORRECT_RECORD] <- per bad pixel
+ * in raster order: pixel index, original similarity, LOD vector x/y, phase shift x/y, coarse vector x/y, coarse
+ * similarity, fine attempted, fine valid, fine vector x/y, fine similarity, accepted, 0.  workspace: device, at least
+ * vfml_flow_correct_workspace_bytes(h, w) bytes.  DESIGN.md section 8 defines every rounding step. */
+#define VFML_CORRECT_RECORD 16
+size_t vfml_flow_correct_workspace_bytes(int h, int w);
+int vfml_flow_correct(const unsigned char* frame1, const unsigned char* frame2, const float* flow, const float* lod,
+                      int lh, int lw, int h, int w, const double* twiddles, double good_threshold,
+                      double fine_threshold, double region_radius, double template_radius, double search_radius,
+                      float* out_flow, int* counts, double* records, int64_t record_capacity, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 const char* vfml_last_error(void);
 int vfml_abi_version(void);

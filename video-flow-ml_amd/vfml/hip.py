@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -164,6 +164,11 @@ def lib():
     L.vfml_taa_blend.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_double,
                                  c_double, c_void_p]
     L.vfml_flow_quality_map.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p]
+    L.vfml_flow_correct_workspace_bytes.argtypes = [c_int, c_int]
+    L.vfml_flow_correct_workspace_bytes.restype = ctypes.c_size_t
+    L.vfml_flow_correct.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                    c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
+                                    ctypes.c_int64, c_void_p, ctypes.c_size_t, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -178,7 +183,8 @@ EXPORTS = [
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
-    "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_last_error", "vfml_abi_version",
+    "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
+    "vfml_last_error", "vfml_abi_version",
 ]
 
 
@@ -753,3 +759,40 @@ def flow_quality_map(frame1, frame2, flow, threshold):
 def convex_upsample(coords1, coords_off, ch, mask, mask_off, ld_mask, h, w, out, out_off=0):
     _check(lib().vfml_convex_upsample(_ptr(_dev(coords1), coords_off), ch, _ptr(_dev(mask), mask_off), ld_mask, h, w,
                                       _ptr(_dev(out), out_off), _stream()), "vfml_convex_upsample")
+
+
+CORRECT_RECORD = 16
+
+
+def flow_correct(frame1, frame2, flow, lod, twiddles, good_threshold, fine_threshold, region_radius=25,
+                 template_radius=5.5, search_radius=25, records=None):
+    """One frame's batch correction (vfml_flow_correct): uint8 frames [H,W,3], float32 flow [H,W,2] and LOD [lh,lw,2],
+    float64 twiddles [2,50] (device tensors) -> (corrected flow [H,W,2], device int32 counts [2]: bad pixels before /
+    after).  `records`: None, or a device float64 tensor [cap, 16] that receives the first cap bad pixels' records."""
+    f1, f2 = _dev(frame1.contiguous(), torch.uint8), _dev(frame2.contiguous(), torch.uint8)
+    fl, ld = _dev(flow.contiguous()), _dev(lod.contiguous())
+    tw = _dev(twiddles.contiguous(), torch.float64)
+    h, w = f1.shape[:2]
+    if tuple(f1.shape) != (h, w, 3) or f2.shape != f1.shape:
+        raise ValueError(f"flow_correct: frames {tuple(f1.shape)} {tuple(f2.shape)}")
+    if tuple(fl.shape) != (h, w, 2):
+        raise ValueError(f"flow_correct: flow {tuple(fl.shape)} is not at the frame's resolution {h}x{w}")
+    if ld.dim() != 3 or ld.shape[2] != 2 or tuple(tw.shape) != (2, 50):
+        raise ValueError(f"flow_correct: LOD {tuple(ld.shape)}, twiddles {tuple(tw.shape)}")
+    cap = 0
+    if records is not None:
+        records = _dev(records, torch.float64)
+        if records.dim() != 2 or records.shape[1] != CORRECT_RECORD or not records.is_contiguous():
+            raise ValueError(f"flow_correct: records {tuple(records.shape)}, want contiguous [cap, {CORRECT_RECORD}]")
+        cap = records.shape[0]
+    L = lib()
+    nbytes = L.vfml_flow_correct_workspace_bytes(h, w)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=f1.device)
+    out = torch.empty_like(fl)
+    counts = torch.zeros(2, dtype=torch.int32, device=f1.device)
+    _check(L.vfml_flow_correct(c_void_p(f1.data_ptr()), c_void_p(f2.data_ptr()), _ptr(fl), _ptr(ld), ld.shape[0],
+                               ld.shape[1], h, w, c_void_p(tw.data_ptr()), float(good_threshold), float(fine_threshold),
+                               float(region_radius), float(template_radius), float(search_radius), _ptr(out),
+                               c_void_p(counts.data_ptr()), None if records is None else c_void_p(records.data_ptr()),
+                               cap, c_void_p(ws.data_ptr()), nbytes, _stream()), "vfml_flow_correct")
+    return out, counts
