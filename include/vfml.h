@@ -427,6 +427,30 @@ int vfml_flow_correct(const unsigned char* frame1, const unsigned char* frame2, 
                       float* out_flow, int* counts, double* records, int64_t record_capacity, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Flow field [h][w][2] f32 -> RGB [h][w][3] u8 on a colour wheel (reference encoding/flow_encoders.py: HSVFlowEncoder
+ * :30-67, TorchvisionFlowEncoder :367-427).  Both normalise by the frame's maximum magnitude, reduced on the device
+ * into a u32 cell of `workspace` (4 bytes, 4-byte aligned; cleared by the call) - no host synchronisation.
+ *   HSV    nan_to_num(0, 1, -1); H = u8(clip((atan2(y, x) + pi) / 2pi * 180, 0, 180)), S = u8(|f| / max * 255) (0
+ *          when max == 0), V = 255; then this project's 8-bit HSV2RGB (OpenCV's sector table, round half to even)
+ *   WHEEL  torchvision.utils.flow_to_image's Middlebury wheel on f / (max + FLT_EPSILON), floor(255 col) as u8, then
+ *          the reference wrapper's uint8 `* 255`, which wraps: the byte written is (256 - x) mod 256
+ * Every f32 step is rounded separately; atan2 is the f64 one rounded to f32.  DESIGN.md section 9.  SURVEY.md row 12. */
+enum { VFML_COLORIZE_HSV = 0, VFML_COLORIZE_WHEEL = 1 };
+int vfml_flow_colorize(const float* flow, int h, int w, int mode, void* workspace, unsigned char* out, void* stream);
+
+/* One output video frame from its tiles (reference visualization/video_composer.py: create_side_by_side :67-122), in
+ * one pass.  tiles / tile_types: host arrays of 2 (SIDE_BY_SIDE, STACKED) or 4 (GRID_2X2) device images [h][w][3],
+ * each VFML_PIX_U8 (RGB bytes) or an f32 / f64 TAA history, which becomes u8 by clip(0, 255) and truncation (NaN -> 0).
+ *   SIDE_BY_SIDE  (2w x h)   tile 0 | tile 1                 (original | flow)
+ *   STACKED       (w x 2h)   tile 0 over tile 1              (--flow-only)
+ *   GRID_2X2      (2w x 2h)  tile 0 | tile 1 over 2 | 3      (original | flow over TAA | TAA simple)
+ * out: rows of row_stride bytes (>= 3 x output width; padding bytes are 0), channels RGB or BGR (VFML_COMPOSE_BGR),
+ * top-down or bottom-up (VFML_COMPOSE_BOTTOM_UP, an AVI DIB).  DESIGN.md section 9.  SURVEY.md row 14. */
+enum { VFML_COMPOSE_SIDE_BY_SIDE = 0, VFML_COMPOSE_STACKED = 1, VFML_COMPOSE_GRID_2X2 = 2 };
+enum { VFML_COMPOSE_BGR = 1, VFML_COMPOSE_BOTTOM_UP = 2 };
+int vfml_compose_frame(const void* const* tiles, const int* tile_types, int h, int w, int layout, int flags,
+                       int64_t row_stride, unsigned char* out, void* stream);
+
 const char* vfml_last_error(void);
 int vfml_abi_version(void);
 

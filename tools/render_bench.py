@@ -1,0 +1,70 @@
+#!/usr/bin/env python3
+"""Render-stage throughput: the visualiser's "Run TAA processor" command (flow_processor.py --taa --skip-lods --tile
+--flow-format hsv --use-flow-cache <cache>) on a synthetic:WxHxN clip with a complete cache of seeded fields, MJPG and
+--uncompressed.  Prints one JSON line per codec: frames, seconds, frames/s, file size.
+
+    python tools/render_bench.py --size 1920x1080 --frames 60 [--device cuda] [--codec mjpg|raw|both]
+"""
+import argparse
+import contextlib
+import io
+import json
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "video-flow-ml_amd"))
+
+import numpy as np  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", default="1920x1080")
+    ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--codec", choices=["mjpg", "raw", "both"], default="both")
+    ap.add_argument("--work", default=None)
+    a = ap.parse_args()
+    import flow_processor as fp
+    from storage import FlowCacheManager
+    w, h = (int(v) for v in a.size.split("x"))
+    work = a.work or tempfile.mkdtemp(prefix="vfml_render_bench_")
+    cache = os.path.join(work, "cache_corrected")
+    os.makedirs(cache, exist_ok=True)
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
+    mgr = FlowCacheManager()
+    for i in range(a.frames):
+        f = np.stack([4 * np.sin(xx / 97 + i / 7), 3 * np.cos(yy / 61 - i / 5)], axis=2).astype(np.float32)
+        f += rng.normal(0, 0.3, f.shape).astype(np.float32)
+        mgr.save_flow_to_cache(f, cache, i, 'npz')
+    spec = f"synthetic:{w}x{h}x{a.frames}"
+    for codec in (["mjpg", "raw"] if a.codec == "both" else [a.codec]):
+        out = os.path.join(work, f"out_{codec}")
+        os.makedirs(out, exist_ok=True)
+        argv = ["--input", spec, "--output", out, "--device", a.device, "--frames", str(a.frames), "--taa",
+                "--skip-lods", "--tile", "--flow-format", "hsv", "--use-flow-cache", cache]
+        if codec == "raw":
+            argv.append("--uncompressed")
+        buf = io.StringIO()
+        t0 = time.time()
+        with contextlib.redirect_stdout(buf):
+            rc = fp.main(argv)
+        dt = time.time() - t0
+        line = [ln for ln in buf.getvalue().splitlines() if ln.startswith("Video written")]
+        avi = [os.path.join(out, n) for n in os.listdir(out) if n.endswith(".avi")]
+        print(json.dumps({"codec": codec, "size": a.size, "frames": a.frames, "rc": rc, "wall_s": round(dt, 3),
+                          "render_line": line[0] if line else None,
+                          "bytes": os.path.getsize(avi[0]) if avi else None}), flush=True)
+        for p in avi:
+            os.remove(p)
+        if rc != 0:
+            return rc
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -8,9 +8,12 @@ the MI355X engine and, under `python -m torch.distributed.run --nproc-per-node N
 sharded over N GPUs (vfml.runner): whole-frame jobs with no collective at all - every rank writes the
 cache files of its own fields - tiled jobs with the tiles streaming to rank 0 in chunked RCCL gathers.
 
-Out of scope here: decoding/encoding video with OpenCV, flow visualisation encoders,
-TAA, the side-by-side composer and the Tk/Qt tools; flags that only concern those are accepted and
-reported as skipped.  Inputs: a `.npy` file holding uint8 frames [F,H,W,3]; `synthetic:WxHxF`
+Without --interactive (the reference's normal mode) the complete cache is then rendered into the output video
+(`render_video`, reference process_video :635-1173): original | flow side by side, stacked (--flow-only) or a 2x2 grid
+with the two TAA results (--taa), MJPG or --uncompressed AVI, on the device by vfml_flow_encode / vfml_flow_colorize /
+vfml_taa_blend / vfml_compose_frame, or with the host paths under --device cpu.  Out of scope: decoding
+video with OpenCV, text labels on the tiles, --flow-input and the Tk/Qt tools; flags that only concern those are
+accepted and reported as skipped.  Inputs: a `.npy` file holding uint8 frames [F,H,W,3]; `synthetic:WxHxF`
 (vfml.synth); or any video file when OpenCV is importable.
 """
 import argparse
@@ -155,12 +158,180 @@ def load_frames(spec, start_frame, max_frames, fps_default=SYNTHETIC_FPS):
     return frames, fps_default, w, h, start_frame
 
 
+ENCODER_LINES = {
+    'hsv': "[Encoder] Using HSV color space encoder",
+    'torchvision': "[Encoder] Using TorchVision color wheel encoder",
+    'motion-vectors-rg8': "[Encoder] Using Motion Vectors RG8 encoder (clamp_range={c})",
+    'motion-vectors-rgb8': "[Encoder] Using Motion Vectors RGB8 encoder (direction+magnitude format, clamp_range={c})",
+    'gamedev': "[Encoder] Using GameDev RG channel encoder",
+}
+
+
+def render_encoder(flow_format, clamp_range):
+    """The render stage's own table of the five --flow-format names (FlowEncoderFactory keeps its three)."""
+    from encoding.flow_encoders import (GamedevFlowEncoder, HSVFlowEncoder, MotionVectorsRG8FlowEncoder,
+                                        MotionVectorsRGB8FlowEncoder, TorchvisionFlowEncoder)
+    if flow_format == 'hsv':
+        return HSVFlowEncoder()
+    if flow_format == 'torchvision':
+        return TorchvisionFlowEncoder()
+    if flow_format == 'motion-vectors-rg8':
+        return MotionVectorsRG8FlowEncoder(clamp_range=clamp_range)
+    if flow_format == 'motion-vectors-rgb8':
+        return MotionVectorsRGB8FlowEncoder(clamp_range=clamp_range)
+    return GamedevFlowEncoder()
+
+
+def render_output_path(args, fps, log=print):
+    """The reference's rule (:686-693): a directory gets a generated file name, anything else is the path itself."""
+    output_path = args.output
+    if os.path.isdir(output_path):
+        from storage.filename_generator import generate_output_filepath
+        output_path = generate_output_filepath(
+            input_path=args.input, output_dir=args.output, start_time=args.start_time, duration=args.duration,
+            start_frame=args.start_frame, max_frames=args.frames, flow_only=args.flow_only, taa=args.taa,
+            fast_mode=args.fast, tile_mode=args.tile, uncompressed=args.uncompressed, flow_format=args.flow_format,
+            motion_vectors_clamp_range=args.motion_vectors_clamp_range, fps=fps)
+        log(f"Auto-generated output filename: {os.path.basename(output_path)}")
+    return output_path
+
+
+class _FieldReader:
+    """Reads cache fields ahead of use on a small thread pool, in frame order."""
+
+    def __init__(self, mgr, cache_dir, fmt, n, ahead=4):
+        from concurrent.futures import ThreadPoolExecutor
+        self.mgr, self.cache_dir, self.fmt, self.n, self.ahead = mgr, cache_dir, fmt, n, ahead
+        self.pool = ThreadPoolExecutor(max_workers=2, thread_name_prefix="render-read")
+        self.futs = {}
+        self.next = 0
+
+    def get(self, i):
+        while self.next < min(self.n, i + self.ahead + 1):
+            self.futs[self.next] = self.pool.submit(self.mgr.load_cached_flow, self.cache_dir, self.next, self.fmt)
+            self.next += 1
+        return np.asarray(self.futs.pop(i).result(), dtype=np.float32)
+
+    def close(self):
+        self.pool.shutdown(cancel_futures=True)
+
+
+def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=None, log=print):
+    """Render the complete flow cache into the output AVI (reference process_video :958-1130, one frame at a time in
+    its order): flow picture, the two TAA histories (--taa), the composed frame, the writer.  Device path: the frames
+    are the clip on the device, each field goes up through a pinned ring, every step is a HIP kernel, and the composed
+    frame - already in the AVI chunk's layout - comes back through a pinned ring one frame behind the GPU.  --device
+    cpu runs the same loop with the host implementations."""
+    from effects.taa_processor import TAAProcessor
+    from storage.avi_writer import AviWriter, dib_stride
+    from visualization.video_composer import compose_device, create_side_by_side
+
+    n = len(frames)
+    output_path = render_output_path(args, fps, log)
+    log(f"Processing: {args.input} -> {output_path}")
+    log(f"Video FPS: {fps:.2f}")
+    flow_only, taa = args.flow_only, args.taa and not args.flow_only     # --flow-only's stacked frame shows no TAA
+    size = (width, height * 2) if args.flow_only else ((width * 2, height * 2) if args.taa else (width * 2, height))
+    if args.uncompressed:
+        log("Using uncompressed video codec. Output will be .avi and file size will be very large.")
+    else:
+        log("Using MJPG codec. Output will be .avi for compatibility.")
+    gpu = str(device).startswith('cuda')
+    from vfml.dist import host_cpu_share
+    jpeg_workers = max(1, min(8, host_cpu_share()))
+    writer = AviWriter(output_path, 0 if args.uncompressed else 'MJPG', fps, size, workers=jpeg_workers,
+                       depth=jpeg_workers + 1, log=log)
+    encoder = render_encoder(args.flow_format, args.motion_vectors_clamp_range)
+    taa_flow, taa_simple = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
+    reader = _FieldReader(FlowCacheManager(), cache_dir, fmt, n)
+    log(ENCODER_LINES.get(args.flow_format, ENCODER_LINES['gamedev']).format(c=args.motion_vectors_clamp_range))
+    t0 = time.time()
+    try:
+        if not gpu:
+            prev = None
+            for i in range(n):
+                field = reader.get(i)
+                viz = encoder.encode(field, width, height)
+                taa_frame = taa_simple_frame = None
+                if taa:
+                    taa_frame = taa_flow.apply_taa(frames[i], flow_pixels=prev, alpha=0.1, use_flow=True,
+                                                   sequence_id='flow_taa')
+                    taa_simple_frame = taa_simple.apply_taa(frames[i], flow_pixels=None, alpha=0.1, use_flow=False,
+                                                            sequence_id='simple_taa')
+                prev = field
+                writer.write(create_side_by_side(frames[i], viz, flow_only=flow_only, taa_frame=taa_frame,
+                                                 taa_simple_frame=taa_simple_frame, flow_format=args.flow_format))
+        else:
+            _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size,
+                           args.uncompressed, taa_flow, taa_simple, dib_stride, compose_device)
+    finally:
+        reader.close()
+        writer.release()
+    dt = time.time() - t0
+    log(f"Video written: {output_path} ({n} frames {size[0]}x{size[1]}, {n / max(dt, 1e-9):.2f} frames/s)")
+    return 0
+
+
+def _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size, uncompressed,
+                   taa_flow, taa_simple, dib_stride, compose_device):
+    n = len(frames)
+    if feeder is None:
+        feeder = ClipFeeder(frames, device)
+    stream = torch.cuda.current_stream()
+    # fields: host -> pinned slot -> device; a slot is refilled once its copy has left it
+    fslots = [torch.empty((height, width, 2), dtype=torch.float32).pin_memory() for _ in range(3)]
+    fevents = [None] * len(fslots)
+    # composed frames: device -> pinned slot -> writer; a slot is reused once the writer no longer holds it
+    stride = dib_stride(size[0]) if uncompressed else 3 * size[0]
+    nslots = writer.in_flight_limit() + 3
+    oslots = [torch.empty((size[1], stride), dtype=torch.uint8).pin_memory() for _ in range(nslots)]
+    oevents = [None] * nslots
+    pending = None              # (slot) composed on the device, not yet handed to the writer
+    prev = None
+    for i in range(n):
+        feeder.ensure(min(i + 2, n - 1), need=i)
+        frame = feeder.clip[i]
+        k = i % len(fslots)
+        host = reader.get(i)
+        if fevents[k] is not None:
+            fevents[k].synchronize()
+        np.copyto(fslots[k].numpy(), host)
+        field = fslots[k].to(device, non_blocking=True)
+        fevents[k] = torch.cuda.Event()
+        fevents[k].record(stream)
+        viz = encoder.encode(field, width, height)
+        taa_frame = taa_simple_frame = None
+        if taa:
+            taa_frame = taa_flow.apply_taa(frame, flow_pixels=prev, alpha=0.1, use_flow=True, sequence_id='flow_taa')
+            taa_simple_frame = taa_simple.apply_taa(frame, flow_pixels=None, alpha=0.1, use_flow=False,
+                                                    sequence_id='simple_taa')
+        prev = field
+        out = compose_device(frame, viz, taa_frame, taa_simple_frame, flow_only=flow_only, bgr=uncompressed,
+                             bottom_up=uncompressed, row_stride=stride)
+        s = i % nslots
+        writer.drain(keep=nslots - 2)        # the slot's previous frame is no longer in the writer's hands
+        oslots[s].copy_(out, non_blocking=True)
+        oevents[s] = torch.cuda.Event()
+        oevents[s].record(stream)
+        if pending is not None:
+            _hand_over(writer, oslots[pending], oevents[pending], size, uncompressed)
+        pending = s
+    if pending is not None:
+        _hand_over(writer, oslots[pending], oevents[pending], size, uncompressed)
+
+
+def _hand_over(writer, slot, event, size, uncompressed):
+    event.synchronize()
+    buf = slot.numpy()
+    writer.write_payload(buf if uncompressed else buf.reshape(size[1], size[0], 3))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     rank, local_rank, world = vdist.init_distributed()
     log = print if rank == 0 else (lambda *a, **k: None)
 
-    for flag, on in (("--taa", args.taa), ("--show-tiles", args.show_tiles), ("--flow-input", args.flow_input)):
+    for flag, on in (("--show-tiles", args.show_tiles), ("--flow-input", args.flow_input)):
         if on:
             log(f"note: {flag} concerns video composition / visualisation, which this build does not do; ignored")
     if not (args.input.startswith('synthetic:') or os.path.exists(args.input)):
@@ -190,8 +361,13 @@ def main(argv=None):
         args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant)
     complete, fmt, missing = mgr.check_cache_exists(cache_dir, n)
     if complete and not args.force_recompute:
-        log(f"Flow cache complete ({fmt}), nothing to compute: {cache_dir}")
-        return 0
+        if args.interactive:
+            log(f"Flow cache complete ({fmt}), nothing to compute: {cache_dir}")
+            return 0
+        if rank != 0:
+            return 0
+        log(f"Using optical flow cache from: {cache_dir} (format: {fmt})")
+        return render_video(args, frames, fps, width, height, cache_dir, fmt, device, log=log)
 
     if memflow:     # reference flow_processor.py:64-75: model path defaults to MemFlow_ckpt/MemFlowNet_{stage}.pth
         eng = MemFlowInference(device, args.model_path or f"MemFlow_ckpt/MemFlowNet_{args.stage}.pth", args.stage,
@@ -243,10 +419,11 @@ def main(argv=None):
         if not complete:
             log(f"Error: flow cache incomplete after the job, missing frames {missing[:8]}{'...' if len(missing) > 8 else ''}")
             return 1
-        if not args.interactive:
-            log("note: video encoding / composition is out of scope for this build; the flow cache is the output")
     if torch.distributed.is_initialized():
         torch.distributed.destroy_process_group()
+    if rank == 0 and not args.interactive:
+        _, fmt, _ = mgr.check_cache_exists(cache_dir, n)
+        return render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=feeder, log=log)
     return 0
 
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -169,6 +169,9 @@ def lib():
     L.vfml_flow_correct.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                     c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                     ctypes.c_int64, c_void_p, ctypes.c_size_t, c_void_p]
+    L.vfml_flow_colorize.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.vfml_compose_frame.argtypes = [POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int, c_int, c_int64, c_void_p,
+                                     c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -184,6 +187,7 @@ EXPORTS = [
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
+    "vfml_flow_colorize", "vfml_compose_frame",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -741,6 +745,55 @@ def taa_blend(current, flow, history, mode, alpha, sigma_color=25.0):
     _check(lib().vfml_taa_blend(c_void_p(cur.data_ptr()), _PIX[cur.dtype], None if mode == TAA_SIMPLE else _ptr(flow),
                                 c_void_p(hist.data_ptr()), _PIX[hist.dtype], c_void_p(out.data_ptr()), _PIX[out_dtype],
                                 h, w, mode, float(alpha), float(sigma_color), _stream()), "vfml_taa_blend")
+    return out
+
+
+COLORIZE_HSV, COLORIZE_WHEEL = 0, 1
+
+
+def flow_colorize(flow, mode):
+    """[H,W,2] float32 device tensor -> [H,W,3] uint8 device tensor on the HSV or torchvision colour wheel
+    (vfml_flow_colorize; the frame maximum is reduced on the device, no host sync)."""
+    f = _dev(flow.contiguous())
+    if f.dim() != 3 or f.shape[2] != 2:
+        raise ValueError(f"flow_colorize: [H,W,2] flow expected, got {tuple(f.shape)}")
+    h, w = f.shape[:2]
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=f.device)
+    cell = torch.empty(1, dtype=torch.int32, device=f.device)
+    _check(lib().vfml_flow_colorize(_ptr(f), h, w, mode, c_void_p(cell.data_ptr()), c_void_p(out.data_ptr()), _stream()),
+           "vfml_flow_colorize")
+    return out
+
+
+COMPOSE_SIDE_BY_SIDE, COMPOSE_STACKED, COMPOSE_GRID_2X2 = 0, 1, 2
+COMPOSE_BGR, COMPOSE_BOTTOM_UP = 1, 2
+
+
+def compose_frame(tiles, layout, bgr=True, bottom_up=False, row_stride=None, out=None):
+    """One output frame (vfml_compose_frame): tiles = 2 (SIDE_BY_SIDE, STACKED) or 4 (GRID_2X2) device images [H,W,3],
+    uint8 or float32 / float64 TAA histories -> uint8 device buffer [rows, row_stride] (row_stride defaults to 3 x the
+    output width).  `out`, when given, is a contiguous uint8 device tensor of at least rows x row_stride bytes."""
+    nt = 4 if layout == COMPOSE_GRID_2X2 else 2
+    if len(tiles) != nt:
+        raise ValueError(f"compose_frame: layout {layout} takes {nt} tiles, got {len(tiles)}")
+    ts = [t.contiguous() for t in tiles]
+    h, w = ts[0].shape[:2]
+    for t in ts:
+        if not (t.is_cuda and t.dtype in _PIX and tuple(t.shape) == (h, w, 3)):
+            raise ValueError(f"compose_frame: device [H,W,3] u8/f32/f64 tiles of one size expected, got "
+                             f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    ow = w if layout == COMPOSE_STACKED else 2 * w
+    oh = h if layout == COMPOSE_SIDE_BY_SIDE else 2 * h
+    stride = 3 * ow if row_stride is None else int(row_stride)
+    if out is None:
+        out = torch.empty((oh, stride), dtype=torch.uint8, device=ts[0].device)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= oh * stride):
+        raise ValueError(f"compose_frame: out must be a contiguous uint8 device tensor of >= {oh * stride} bytes")
+    ptrs = (c_void_p * nt)(*[t.data_ptr() for t in ts])
+    types = (c_int32 * nt)(*[_PIX[t.dtype] for t in ts])
+    flags = (COMPOSE_BGR if bgr else 0) | (COMPOSE_BOTTOM_UP if bottom_up else 0)
+    _check(lib().vfml_compose_frame(ptrs, types, h, w, layout, flags, stride, c_void_p(out.data_ptr()), _stream()),
+           "vfml_compose_frame")
     return out
 
 
