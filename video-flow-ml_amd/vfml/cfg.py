@@ -5,7 +5,6 @@ Stands in for `configs.multiframes_sintel_submission.get_cfg` of the VideoFlow s
 :92-94 `decoder_depth / corr_levels / corr_radius` for --fast).  A plain mutable attribute bag,
 like yacs' CfgNode as the reference uses it.
 """
-import os
 
 
 class Cfg:
@@ -65,10 +64,6 @@ BOF_F16_PLAN = {
 # 2-3 (1.00e-4) and beyond do not fit the budget.
 DEFAULT_MIXED_CORR_VOLUME = "f16@3"
 NAMED_PLANS = {"default": DEFAULT_MIXED_PLAN, "bof-f16": BOF_F16_PLAN}     # VFML_MFMA_PLAN may name one
-
-# (A/B switch: VFML_PLAN_EXCLUDE="layer,layer" takes entries out of the default plan - those layers run all three terms)
-for _k in filter(None, os.environ.get("VFML_PLAN_EXCLUDE", "").split(",")):
-    DEFAULT_MIXED_PLAN.pop(_k, None)
 
 
 def get_cfg():

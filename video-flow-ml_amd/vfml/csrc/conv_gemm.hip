@@ -221,16 +221,7 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvArgs a) {
 template <int BN, int WM, int WN>
 int launch(const ConvArgs& a, hipStream_t s) {
   constexpr size_t lds = 2 * (KG * (BM + 1) + KG * (BN + 1)) * sizeof(f32x4);
-  static bool attr_done = false;  // per instantiation; raising the dynamic-LDS cap is idempotent
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_kernel<BN, WM, WN>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_conv2d: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&conv_gemm_kernel<BN, WM, WN>), (int)lds, "vfml_conv2d")) return rc;
   hipLaunchKernelGGL((conv_gemm_kernel<BN, WM, WN>), dim3(a.mtiles * a.ntiles), dim3(256), lds, s, a);
   return vfml_check_launch("vfml_conv2d");
 }

@@ -986,16 +986,9 @@ int launch_dma_k(SplitArgs& a, hipStream_t s) {
   static_assert(lds <= 160 * 1024, "LDS");
   a.mtiles = (a.M + TBM - 1) / TBM;
   a.ntiles = (a.cout + TBN - 1) / TBN;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_dma_kernel<TM, TN, WM, WN, PERSIST, FASTK, CSWAP, NM, MF16, H16>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_conv2d_split: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&conv_gemm_dma_kernel<TM, TN, WM, WN, PERSIST, FASTK, CSWAP, NM, MF16, H16>),
+                                  (int)lds, "vfml_conv2d_split"))
+    return rc;
   // PERSIST: one workgroup per resident slot (256 CUs x 2 or 1), fewer when there are fewer tiles
   const int64_t total = (int64_t)a.mtiles * a.ntiles * (PERSIST ? a.ksplit : 1);     // work items
   const int64_t slots = 256 * (WM * WN == 4 ? 2 : 1);
@@ -1029,12 +1022,10 @@ int launch_dma(SplitArgs& a, hipStream_t s) {
     return a.fastk ? launch_dma_k<2, 2, 2, 2, true, true>(a, s) : launch_dma_k<2, 2, 2, 2, true, false>(a, s);
   }
   if constexpr (WM * WN == 4) {   // the shapes the dispatcher picks by itself: 16x16x32 MFMAs (MF16)
-    // VFML_MF32=1: the 32x32x16 shape for the full-precision uniform-step variants (A/B; MF16 is 9-12 % faster on the
-    // 1080p update-block shapes: the chip holds a higher clock on it)
-    static const int mf32 = getenv("VFML_MF32") ? atoi(getenv("VFML_MF32")) : 0;
+    // (measured against the 32x32x16 shape for the full-precision uniform-step variants: MF16 is 9-12 % faster on the
+    // 1080p update-block shapes - the chip holds a higher clock on it)
     if constexpr (TM * TN >= 2) {
       if (a.fastk) {
-        if (mf32 && a.nm == 3) return launch_dma_k<TM, TN, WM, WN, false, true>(a, s);
         if (a.nm == 2) return launch_dma_k<TM, TN, WM, WN, false, true, false, 2, true>(a, s);
         if (a.nm == 4) return launch_dma_k<TM, TN, WM, WN, false, true, false, 4, true>(a, s);
         if (a.nm == 1) return launch_dma_k<TM, TN, WM, WN, false, true, false, 1, true>(a, s);
@@ -1061,16 +1052,9 @@ int launch_nm(const SplitArgs& a, hipStream_t s) {
   constexpr size_t stage = 2 * 2 * (KG * (BM + 2) + KG * (BN + 2)) * 16;
   constexpr size_t ctile = (size_t)BM * (BN + 4) * 4;
   constexpr size_t lds = stage > ctile ? stage : ctile;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_split_kernel<BN, WM, WN, BIGC, IN16, NM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_conv2d_split: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&conv_gemm_split_kernel<BN, WM, WN, BIGC, IN16, NM>), (int)lds,
+                                  "vfml_conv2d_split"))
+    return rc;
   hipLaunchKernelGGL((conv_gemm_split_kernel<BN, WM, WN, BIGC, IN16, NM>), dim3(a.mtiles * a.ntiles), dim3(WM * WN * 64), lds, s, a);
   return vfml_check_launch("vfml_conv2d_split");
 }
@@ -1327,8 +1311,7 @@ extern "C" int vfml_softmax_rows_s16(const float* x, int64_t rows, int cols, int
   VFML_REQUIRE(x && out && rows > 0 && rows < (1ll << 31) && cols > 0 && ld_in >= cols && ld_out >= cols && ld_out % 8 == 0,
                "vfml_softmax_rows_s16: bad shape (ld_out %% 8 == 0, ld_out >= cols)");
   VFML_REQUIRE((reinterpret_cast<uintptr_t>(out) & 31u) == 0, "vfml_softmax_rows_s16: out must be 32-byte aligned");
-  static const int sweep = getenv("VFML_SOFTMAX_SWEEPS") ? atoi(getenv("VFML_SOFTMAX_SWEEPS")) : 0;
-  if (ld_out <= 256 * 4 * SOFTMAX_REG_QUADS && !sweep)
+  if (ld_out <= 256 * 4 * SOFTMAX_REG_QUADS)
     hipLaunchKernelGGL(softmax_rows_s16_reg_kernel<false>, dim3((unsigned)rows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
                        x, cols, ld_in, out, ld_out, scale);
   else
@@ -1411,6 +1394,9 @@ __global__ void add_rows_kernel(float* __restrict__ out, const float* __restrict
     *reinterpret_cast<f32x4*>(out + o) = x + y;
   }
 }
+
+// narrowest plain-f32 output the GEMM form (a.direct) writes straight from its accumulators
+constexpr int DIRECT_MIN_COUT = 1024;
 
 extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
                                  int in_fmt, int out_fmt, int aux_fmt, int k_order, void* stream) {
@@ -1505,8 +1491,6 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
   a.wbase = nullptr; a.whi_off = a.wlo_off = a.bytesb = 0; a.korder = k_order; a.direct = 0; a.fastk = 0; a.abias = 0; a.src1_delta = 0; a.out_t = nullptr; a.ld_out_t = 0; a.cswap = 0; a.bhi = 0;
   a.stats_part = d->stats_part;
   a.ksplit = 1; a.out_k1 = nullptr; a.out_t_k1 = nullptr;
-  static const int fast_epi = getenv("VFML_FAST_EPI") ? atoi(getenv("VFML_FAST_EPI")) : 1;
-  a.fast_epi = fast_epi;
   a.nm = (d->flags & VFML_CONV_MFMA1) ? 1 : (d->flags & VFML_CONV_MFMA2A) ? (bhi ? 1 : 4) : ((d->flags & VFML_CONV_MFMA2) || bhi) ? 2 : 3;
   a.pointwise = d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad_h == 0 && d->pad_w == 0;
   // one buffer descriptor serves both sources: they must lie in one allocation (within 1 GiB)
@@ -1557,8 +1541,7 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
       const int64_t rounds = (wg + slots - 1) / slots;
       return ((double)d->cout / (nt * w)) * ((double)wg / (rounds * slots)) * (w == 64 ? 0.7 : 1.0);
     };
-    static const int force = getenv("VFML_BN") ? atoi(getenv("VFML_BN")) : 0;
-    if (force == 64 || (force == 0 && eff(64) > eff(128))) bn = 64;
+    if (eff(64) > eff(128)) bn = 64;
   }
   if (in16) {   // split-row sources: every slice is a multiple of 8 channels and >= one K step wide
     // LDS-DMA kernel when both weight planes fit one descriptor window (< 1 GiB)
@@ -1573,12 +1556,11 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
       a.bhi = bhi ? 1 : 0;
       a.tilebase = tilebase;
       {
-        static const int no_fastk = getenv("VFML_NO_FASTK") ? atoi(getenv("VFML_NO_FASTK")) : 0;
         const int64_t abias = ((int64_t)d->pad_h * d->w + d->pad_w) * d->ld0 * 4;
         // (for a 1x1 convolution over whole 32-channel blocks the two K orders are the same bytes)
         const bool cblock = k_order == VFML_KORDER_CBLOCK || k_order == VFML_KORDER_CBLOCK64 ||
                             (a.pointwise && (d->c0 + d->c1) % BK == 0);
-        a.fastk = !no_fastk && cblock && d->c0 % BK == 0 && (d->c0 + d->c1) % BK == 0 &&
+        a.fastk = cblock && d->c0 % BK == 0 && (d->c0 + d->c1) % BK == 0 &&
                   (!two || (d->ld1 == d->ld0 && a.d1off >= a.d0off)) && d->kh * d->kw <= 32 &&
                   (int64_t)a.bytes0 + abias < (1ll << 31);
         VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.fastk,
@@ -1586,20 +1568,18 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
         if (a.fastk) a.korder = VFML_KORDER_CBLOCK;
         // one MFMA per product over whole 64-channel blocks: 64-channel steps of hi halves (NM 5) - for 1x1 kernels in
         // any weight order (the K axis is the channel axis), else with the weights in 64-channel-block order
-        static const int no_h64 = getenv("VFML_NO_H64") ? atoi(getenv("VFML_NO_H64")) : 0;
         // (cout > 32: the 128 x 32 tile of narrower outputs has no uniform-step instantiation)
-        if (a.nm == 1 && a.fastk && !no_h64 && d->c0 % 64 == 0 && (d->c0 + d->c1) % 64 == 0 && d->cout > 32 &&
+        if (a.nm == 1 && a.fastk && d->c0 % 64 == 0 && (d->c0 + d->c1) % 64 == 0 && d->cout > 32 &&
             (k_order == VFML_KORDER_CBLOCK64 || a.pointwise))
           a.nm = 5;
-        VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.nm == 5, "vfml_conv2d_split: VFML_KORDER_CBLOCK64 weights need the 64-channel-step kernel (VFML_NO_H64 is set?)");
+        VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.nm == 5, "vfml_conv2d_split: VFML_KORDER_CBLOCK64 weights need the 64-channel-step kernel");
         a.abias = a.fastk ? (int)abias : 0;
         a.src1_delta = two ? (a.d1off - a.d0off) * 4 : 0;
       }
-      static const int direct_min = getenv("VFML_DIRECT_MIN") ? atoi(getenv("VFML_DIRECT_MIN")) : 1024;
       // (VFML_FMT_F16 outputs exist in this form only: any width)
       a.direct = (d->epilogue == VFML_EPI_NONE || d->epilogue == VFML_EPI_RELU) && !d->addend &&
                  (out_fmt == VFML_FMT_F32 || out_fmt == VFML_FMT_F16) && !d->stats_part &&
-                 (d->cout >= direct_min || out_fmt == VFML_FMT_F16) && d->cout % 4 == 0 && d->ldo % 4 == 0 && vfml_aligned16(d->out) &&
+                 (d->cout >= DIRECT_MIN_COUT || out_fmt == VFML_FMT_F16) && d->cout % 4 == 0 && d->ldo % 4 == 0 && vfml_aligned16(d->out) &&
                  (!d->bias || vfml_aligned16(d->bias));
       VFML_REQUIRE(out_fmt != VFML_FMT_F16 || (a.direct && a.fastk),
                    "vfml_conv2d_split: VFML_FMT_F16 outputs are written by the GEMM form only (1x1 over whole 32-channel blocks, no "
@@ -1625,9 +1605,8 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
       bool ksplit = false;
       if (d->ksplit_ws) {
         VFML_REQUIRE(vfml_aligned16(d->ksplit_ws), "vfml_conv2d_split: ksplit_ws must be 16-byte aligned");
-        static const int no_ksplit = getenv("VFML_NO_KSPLIT") ? atoi(getenv("VFML_NO_KSPLIT")) : 0;
         const int64_t tiles = (int64_t)((a.M + 127) / 128) * ((d->cout + 127) / 128);
-        ksplit = !no_ksplit && a.direct && a.fastk && a.pointwise && out_fmt == VFML_FMT_F32 && !a.cswap && tiles <= 256 &&
+        ksplit = a.direct && a.fastk && a.pointwise && out_fmt == VFML_FMT_F32 && !a.cswap && tiles <= 256 &&
                  kp >= 4096;
         if (ksplit) {     // (the workspace holds the primary output's shape, then - with out_t - the transposed one's)
           a.ksplit = 2;
@@ -1687,12 +1666,11 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
         VFML_REQUIRE(!a.proj_out || cfg == 3222 || cfg == 2222, "vfml_conv2d_split: proj_out runs on the 192 x 128 / 128 x 128 tiles (VFML_DMA_TILE)");
       }
       // stride-1 "same" convolutions with a filter row of 2..5 taps: one activation stage per (channel block, tap row),
-      // shared by the row's taps (conv_gemm_tapx.hip; VFML_TAPX=0: the per-tap stages of conv_gemm_dma_kernel, for A/B)
-      static const int tapx = getenv("VFML_TAPX") ? atoi(getenv("VFML_TAPX")) : 1;
-      if (tapx && !(d->flags & VFML_CONV_PER_TAP) && !a.proj_out) {
-        // (VFML_TAPX=2: also the three-MFMA calls on the 192 x 128 / 128 x 192 tiles, where the two kernels run level)
+      // shared by the row's taps (conv_gemm_tapx.hip).  The three-MFMA calls on the 192 x 128 / 128 x 192 tiles keep the
+      // per-tap stages of conv_gemm_dma_kernel: there the two kernels run level.
+      if (!(d->flags & VFML_CONV_PER_TAP) && !a.proj_out) {
         const int tcfg = vfml_detail::tapx_cfg(a, cfg, forced);
-        if (tcfg && (tapx >= 2 || forced || a.nm == 5 || tcfg == 2241 || tcfg == 2341)) return vfml_detail::launch_tapx(a, tcfg, s);
+        if (tcfg && (forced || a.nm == 5 || tcfg == 2241 || tcfg == 2341)) return vfml_detail::launch_tapx(a, tcfg, s);
       }
       if (a.ksplit == 2) {
         // (the GEMM form is one tile shape; the partial sums of the second half of K are added once the launch is queued)

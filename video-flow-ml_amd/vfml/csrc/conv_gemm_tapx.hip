@@ -303,16 +303,9 @@ int launch_tapx_k(SplitArgs& a, hipStream_t s) {
   static_assert(lds <= 80 * 1024, "two workgroups per CU");
   a.mtiles = (a.M + TBM - 1) / TBM;
   a.ntiles = (a.cout + TBN - 1) / TBN;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_tapx_kernel<TM, TN, WM, WN, NM>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_conv2d_split: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&conv_gemm_tapx_kernel<TM, TN, WM, WN, NM>), (int)lds,
+                                  "vfml_conv2d_split"))
+    return rc;
   hipLaunchKernelGGL((conv_gemm_tapx_kernel<TM, TN, WM, WN, NM>), dim3(a.mtiles * a.ntiles), dim3(256), lds, s, a);
   return vfml_check_launch("vfml_conv2d_split");
 }

@@ -41,7 +41,6 @@ struct SplitArgs {
   int bhi;                      // LDS-DMA GEMM form: the weight operand is one plain f16 plane (no lo plane)
   double* stats_part;           // register-staged kernel: per row tile and channel {sum, sum of squares} of the result
   int nm;                       // terms of the split product: 3 all, 2 weights as plain f16, 4 activations as plain f16, 1 both
-  int fast_epi;                 // 0: the general epilogue routine everywhere (VFML_FAST_EPI=0, A/B)
   int ksplit; float* out_k1; float* out_t_k1;   // persistent GEMM form: 2 = two work items per tile, one per half of K; the second half's sums go to out_k1 (out_t_k1)
   // projection epilogue (vfml_conv_desc.proj_*): relu(out) is not stored but multiplied, per 128-column tile, by that
   // tile's slice of a second [proj_n][cout] weight (two f16 planes, lo plane proj_lo_off bytes behind the hi plane)
@@ -461,7 +460,7 @@ __device__ __forceinline__ bool epilogue_rows_fast(const SplitArgs& a, const flo
                                                    int rstride, int roff) {
   // (uniform over the workgroup: every thread takes the same route)
   const bool gru = a.epilogue == VFML_EPI_GRU_ZR || a.epilogue == VFML_EPI_GRU_Q;
-  if (!(a.fast_epi && a.vec_ok && a.cout % 4 == 0 && (!gru || (a.aux16 && a.split % 8 == 0 && a.cout % 8 == 0)) &&
+  if (!(a.vec_ok && a.cout % 4 == 0 && (!gru || (a.aux16 && a.split % 8 == 0 && a.cout % 8 == 0)) &&
         (!a.bias || (reinterpret_cast<uintptr_t>(a.bias) & 15u) == 0) && a.epilogue != VFML_EPI_TANH_RELU &&
         a.epilogue != VFML_EPI_ADD_AUX))
     return false;

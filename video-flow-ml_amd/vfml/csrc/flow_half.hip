@@ -198,15 +198,7 @@ extern "C" int vfml_flow_half(const float* flow, int n, int h, int w, const void
   a.w1_inv = 1.0f / w1_scale; a.w2_inv = 1.0f / w2_scale;
   const int64_t grid = (int64_t)n * a.tiles_x * a.tiles_y;
   VFML_REQUIRE(grid < (1ll << 31), "vfml_flow_half: too many tiles");
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&flow_half_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_flow_half: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&flow_half_kernel), FH_LDS, "vfml_flow_half")) return rc;
   hipLaunchKernelGGL(flow_half_kernel, dim3((unsigned)grid), dim3(256), FH_LDS, reinterpret_cast<hipStream_t>(stream), a);
   return vfml_check_launch("vfml_flow_half");
 }

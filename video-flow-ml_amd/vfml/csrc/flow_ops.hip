@@ -583,7 +583,6 @@ static int corr_lookup_impl(const float* const* pyr, const float* const* table, 
   a.dir_maps = dir_maps; a.dir_coords = dir_coords; a.dir_out = dir_out; a.dir_tab = dir_tab;
   const dim3 grid((nq + LOOKUP_WAVES - 1) / LOOKUP_WAVES), block(64 * LOOKUP_WAVES);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  static const int generic = getenv("VFML_LOOKUP_GENERIC") ? atoi(getenv("VFML_LOOKUP_GENERIC")) : 0;
   if (a.vol16) {
     const int m = a.vol16;
 #define VFML_LOOKUP16(RR, OO)                                                                                  \
@@ -601,10 +600,10 @@ static int corr_lookup_impl(const float* const* pyr, const float* const* table, 
       else VFML_LOOKUP16(3, false);
     }
 #undef VFML_LOOKUP16
-  } else if (radius == 4 && !generic && levels <= FIXED_LEVELS) {
+  } else if (radius == 4 && levels <= FIXED_LEVELS) {
     if (a.out16) hipLaunchKernelGGL((corr_lookup_fixed_kernel<4, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((corr_lookup_fixed_kernel<4, false>), grid, block, 0, st, a);
-  } else if (radius == 3 && !generic && levels <= FIXED_LEVELS) {
+  } else if (radius == 3 && levels <= FIXED_LEVELS) {
     if (a.out16) hipLaunchKernelGGL((corr_lookup_fixed_kernel<3, true>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((corr_lookup_fixed_kernel<3, false>), grid, block, 0, st, a);
   } else {

@@ -296,10 +296,7 @@ extern "C" int vfml_instnorm_stats(const float* x, int n, int hw, int c, float e
   return vfml_check_launch("vfml_instnorm_stats(final)");
 }
 
-static bool finalize_folds(int chunks, int c) {
-  static const int no_fold = getenv("VFML_NO_NORM_FOLD") ? atoi(getenv("VFML_NO_NORM_FOLD")) : 0;     // (A/B)
-  return !no_fold && chunks >= 1024 && c % 8 == 0;
-}
+static bool finalize_folds(int chunks, int c) { return chunks >= 1024 && c % 8 == 0; }
 
 extern "C" int64_t vfml_instnorm_finalize_workspace_bytes(int chunks, int c) {
   return finalize_folds(chunks, c) ? (int64_t)FOLD_SLICES * c * 16 : 0;

@@ -227,15 +227,7 @@ extern "C" int vfml_stem7x7s2(const float* frames, int n, int h, int w, const vo
   a.n = n; a.H = h; a.W = w; a.ho = (h - 1) / 2 + 1; a.wo = (w - 1) / 2 + 1;
   a.tiles_y = (a.ho + ST_TH - 1) / ST_TH; a.tiles_x = (a.wo + ST_TW - 1) / ST_TW;
   a.w_inv = 1.0f / w_scale;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&stem7x7s2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e != hipSuccess) {
-      vfml_set_error("vfml_stem7x7s2: hipFuncSetAttribute: %s", hipGetErrorString(e));
-      return 2;
-    }
-    attr_done = true;
-  }
+  if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&stem7x7s2_kernel), ST_LDS, "vfml_stem7x7s2")) return rc;
   const int64_t grid = (int64_t)n * a.tiles_x * a.tiles_y;
   VFML_REQUIRE(grid < (1ll << 31), "vfml_stem7x7s2: too many tiles");
   hipLaunchKernelGGL(stem7x7s2_kernel, dim3((unsigned)grid), dim3(512), ST_LDS, reinterpret_cast<hipStream_t>(stream), a);

@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <mutex>
+#include <set>
+#include <utility>
 #include "../../../include/vfml.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -67,3 +70,24 @@ static inline int vfml_check_launch(const char* what) {
 }
 
 static inline bool vfml_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// Raise `kernel`'s dynamic-LDS cap to `bytes` on the current device before its first launch there.  The attribute is held
+// per device, so a process that drives several GPUs sets it on each; callers may be on several host threads.  0, or 2
+// with the error set ("<who>: hipFuncSetAttribute: ...").
+inline int vfml_lds_cap(const void* kernel, int bytes, const char* who) {
+  static std::mutex mu;
+  static std::set<std::pair<const void*, int>> done;     // (kernel, device)
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({kernel, dev})) return 0;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) {
+      done.insert({kernel, dev});
+      return 0;
+    }
+  }
+  vfml_set_error("%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+  return 2;
+}

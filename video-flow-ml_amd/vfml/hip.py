@@ -284,8 +284,7 @@ def conv_variant(cout, split=False, ctot=32, in16=False, m=0, order=KORDER_TAP, 
             return f"conv_gemm_dma_kernel<1, 1, 4, 1, false, false, false, {nm}, true, false>"
         # the shared-stage kernel (csrc/conv_gemm_tapx.hip: vfml_detail::tapx_cfg and the dispatcher's condition):
         # `same` = (kh, kw) of a stride-1 "same" convolution, else None
-        tapx_mode = int(os.environ.get("VFML_TAPX", "1"))
-        tapx = (tapx_mode and not per_tap and fastk and same is not None and 2 <= same[1] <= 5 and same[0] <= 4
+        tapx = (not per_tap and fastk and same is not None and 2 <= same[1] <= 5 and same[0] <= 4
                 and nm in (3, 5))
         tiles256 = -(-m // 256)
         fills = tiles256 * 100 >= -(-tiles256 // 512) * 512 * 85      # 256-row tiles fill their last round to 85 %
@@ -305,7 +304,7 @@ def conv_variant(cout, split=False, ctot=32, in16=False, m=0, order=KORDER_TAP, 
         for c, name in cands[1:]:
             if c < best:
                 best, t = c, name
-        if tapx and t in ("3, 2, 2, 2", "2, 3, 2, 2") and (nm == 5 or tapx_mode >= 2):
+        if tapx and t in ("3, 2, 2, 2", "2, 3, 2, 2") and nm == 5:
             return f"conv_gemm_tapx_kernel<{t}, {nm}>"
         return f"conv_gemm_dma_kernel<{t}, false, {fk}, false, {nm}, true, false>"
     bigc = "true" if (ctot >= 32 or in16) else "false"
@@ -417,11 +416,11 @@ def conv2d(in0, c0, ld0, n, h, w, weight, bias, cout, kh, kw, out, ldo, *, strid
     ctot = c0 + c1
     pointwise = kh == 1 and kw == 1 and stride == 1 and pad_h == 0 and pad_w == 0
     fastk = (is_split and in_fmt == FMT_S16 and (weight.order in (KORDER_CBLOCK, KORDER_CBLOCK64) or (pointwise and ctot % 32 == 0))
-             and c0 % 32 == 0 and ctot % 32 == 0 and kh * kw <= 32 and not os.environ.get("VFML_NO_FASTK")
+             and c0 % 32 == 0 and ctot % 32 == 0 and kh * kw <= 32
              and (in1 is None or (ld1 == ld0 and in1.data_ptr() + 4 * in1_off >= in0.data_ptr() + 4 * in0_off)))
     nm_eff = {"2a": 4}.get(mfma, mfma)
     if (mfma == 1 and fastk and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32 and
-            (weight.order == KORDER_CBLOCK64 or pointwise) and not os.environ.get("VFML_NO_H64")):
+            (weight.order == KORDER_CBLOCK64 or pointwise)):
         nm_eff = 5                                           # 64-channel steps of hi halves
     elif is_split and weight.lo is None:
         nm_eff = {3: 2, 2: 2, 4: 1, 1: 1}[nm_eff]            # a single weight plane has no lo half to use

@@ -12,8 +12,6 @@ iterations, so the P x P attention matrix is computed ONCE per field, kept resid
 split-row halves (4.2 GB at 1080p; no flash-style re-computation needed with 288 GB), and every
 iteration is one long-K GEMM  attn[P,P] . v[P,128]  on the MFMA kernel with the residual add fused.
 """
-import os
-
 import torch
 import torch.nn as nn
 
@@ -23,8 +21,8 @@ from .weights import pack_conv_weight
 
 # attention probabilities are stored times 2^14 (split rows hold f16 halves: an unscaled 1080p row, 32400 probabilities
 # of 3e-5 on average, would sit in the f16 subnormals); the read-out GEMM divides it out through out_scale
-ATT_SCALE = float(os.environ.get("VFML_ATT_SCALE", "16384"))      # (override: precision experiments)
-ATT_PLAIN = os.environ.get("VFML_ATT_SPLIT_ROWS", "0") != "1"       # 1: keep the probabilities as split rows (hi + lo)
+ATT_SCALE = 16384.0
+ATT_PLAIN = True            # False: keep the probabilities as split rows (hi + lo)
 
 
 def memflow_conv_spec(cfg):
@@ -109,9 +107,8 @@ class MemFlowNetHIP(MOFNetHIP):
                 w = torch.nn.functional.pad(w, (0, 0, 0, 0, 0, cor_p - cin))
             # update-block convolutions read split-row activations (all but convf1): channel-block K order
             cb = split and ((name.startswith(ub + ".") and not name.endswith(".convf1")) or
-                            (self._enc_split_rows() and (
-                                (name.split(".")[0] in ("fnet", "cnet") and name.count(".") > 1) or
-                                name in ("fnet.conv2", "cnet.conv2"))))
+                            (name.split(".")[0] in ("fnet", "cnet") and name.count(".") > 1) or
+                            name in ("fnet.conv2", "cnet.conv2"))
             if cb:
                 cblock_names.add(name)
             P[name] = (pack_conv_weight(w, cin_pad=4 if cin in (2, 3) else None, cblock=cb), b)
@@ -232,10 +229,9 @@ class MemFlowNetHIP(MOFNetHIP):
 
             # memory read-out operator: attn = softmax(q k^T / sqrt(d)), P x P per pair, once per field
             P8 = (Pn + 7) // 8 * 8
-            # V as plain f16 in the read-out (one MFMA per product, 64-channel steps of hi halves: the kernel's NM 5) unless
-            # VFML_ATT_V_SPLIT=1 keeps its split rows (two MFMAs per product): row stride a multiple of 64 then
-            v_f16 = not os.environ.get("VFML_ATT_V_SPLIT")
-            ldA = (P8 + 63) // 64 * 64 if v_f16 else (P8 + 31) // 32 * 32
+            # V as plain f16 in the read-out (one MFMA per product, 64-channel steps of hi halves: the kernel's NM 5): row
+            # stride a multiple of 64
+            ldA = (P8 + 63) // 64 * 64
             qmap = self._buf("att_q", MP * AD, dev)
             kmap = self._buf("att_k", MP * AD, dev)
             wgt, b = P["query"]
@@ -306,7 +302,7 @@ class MemFlowNetHIP(MOFNetHIP):
                 for k in range(B if plain else 0):
                     hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
                     hip.conv2d(vrows, ldA, ldA, AD, 1, 1, attn[k], None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
-                               in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1 if v_f16 else 3, ksplit_ws=ro_ws)
+                               in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
                     hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=gamma, aux_off=k * Pn * GLD + MF,
                                    out_off=k * Pn * GLD + MT)
                 for k in range(0 if plain else B):

@@ -81,7 +81,6 @@ class MOFNetHIP(_Holder):
         self._graphs = {}
         self._side2 = {}      # per device: the stream of the flow half of the motion encoder (_run body)
         self._pyr_free = []
-        self._pyr_busy = set()    # cache keys of the pyramids the field in flight reads (a prefetch must not recycle them)
         self._side = {}                # per device: the stream the next window's encoders run on (prefetch_frames)
         self._prefetch_done = None     # event: the last prefetch's launches
         self._prefetch_dev = None
@@ -112,8 +111,7 @@ class MOFNetHIP(_Holder):
             """K-axis block of a split-row layer's weight planes: 64 channels where the layer runs one MFMA per product
             over whole 64-channel blocks, more than 32 outputs wide (the kernel then steps 64 channels of hi halves at a
             time: include/vfml.h VFML_KORDER_CBLOCK64), else 32."""
-            if (split and self._nm(layer) == 1 and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32
-                    and not os.environ.get("VFML_NO_H64")):
+            if split and self._nm(layer) == 1 and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32:
                 cb64_names.add(layer)
                 return 64
             return True
@@ -132,14 +130,12 @@ class MOFNetHIP(_Holder):
                 wp[:, :cor] = w[:, sel]
                 wp[:, cor_p:cor_p + cor] = w[:, base + sel]
                 w = wp
-            if (name.endswith(".flow_head.conv2") and split and cout == 4 and (kh, kw) == (3, 3)
-                    and not os.environ.get("VFML_NO_TAPSUM")):       # (A/B switch)
+            if name.endswith(".flow_head.conv2") and split and cout == 4 and (kh, kw) == (3, 3):
                 # 3x3 to four channels as a 1x1 to 36 (tap-major) + vfml_tapsum3x3: nine times fewer MFMA steps than a
                 # 3x3 convolution padded to a 32-column tile
                 w = w.permute(2, 3, 0, 1).reshape(36, cin, 1, 1).contiguous()
                 cout_packed[name] = 36
-            if (name.endswith(".encoder.convf1") and split and (cin, kh, kw) == (4, 7, 7)
-                    and not os.environ.get("VFML_NO_ROWS7")):        # (A/B switch)
+            if name.endswith(".encoder.convf1") and split and (cin, kh, kw) == (4, 7, 7):
                 # 7x7 over the 4-channel flow as 7x1 over 32 channels = the seven horizontal taps' quads per pixel
                 # (vfml_flow_rows7): [cout][kx*4 + c][ky][1], channels 28..31 zero
                 w7 = torch.zeros(cout, 32, 7, 1, device=device)
@@ -153,9 +149,8 @@ class MOFNetHIP(_Holder):
             # 4-channel f32 flow), and so do the encoders behind their 4-channel stem: those weights go in
             # channel-block K order (include/vfml.h)
             cb = split and ((name.startswith("update_block.") and (not name.endswith(".convf1") or name in rows7)) or
-                            (self._enc_split_rows() and (
-                                (name.split(".")[0] in ("fnet", "cnet") and name.count(".") > 1) or
-                                name in ("fnet.conv2", "cnet.conv2"))))
+                            (name.split(".")[0] in ("fnet", "cnet") and name.count(".") > 1) or
+                            name in ("fnet.conv2", "cnet.conv2"))
             if cb:
                 cblock_names.add(name)
                 cb = block_of(name, w.shape[1], w.shape[1], cout)
@@ -194,7 +189,7 @@ class MOFNetHIP(_Holder):
                     sw.order = (hip.KORDER_CBLOCK64 if name in cb64_names else
                                 hip.KORDER_CBLOCK if name in cblock_names else hip.KORDER_TAP)
                     P[name] = (sw, b)
-        if split and os.environ.get("VFML_STEM", "1") != "0":        # (A/B switch: the general kernel for the stems)
+        if split:
             for enc in ("fnet", "cnet"):
                 leaf = self._param(f"{enc}.conv1")
                 if tuple(leaf.weight.shape) == (64, 3, 7, 7):
@@ -216,15 +211,6 @@ class MOFNetHIP(_Holder):
         if p not in self.PRECISIONS:
             raise ValueError(f"cfg.precision must be one of {self.PRECISIONS}, got {p!r}")
         return p
-
-    def _enc_split_rows(self):
-        """Encoder activations as split rows through the LDS-DMA convolution kernels (the default; `instnorm_apply` writes
-        split rows, the norm statistics come from the convolution epilogues), or f32 rows split while register-staged
-        (VFML_ENC_S16=0).  Measured A/B on one box at 1080p: with the per-tap kernel the split-row path was 0.25 ms per
-        field SLOWER (profiles/r02_encoder_paths.md: the 64-channel layers at half resolution re-read every input pixel
-        once per filter tap); with one activation stage per filter row on 256 x 64 / 256 x 96 tiles (conv_gemm_tapx.hip)
-        and the fast epilogue it is 0.2 ms FASTER (26.27 / 26.26 vs 26.42 / 26.50 ms, profiles/r02_kernel_anatomy.md)."""
-        return os.environ.get("VFML_ENC_S16", "1") != "0"
 
     def _split(self):
         """Every arithmetic but 'f32' runs the split-f16 kernels on split-row activations; they differ in the
@@ -284,8 +270,8 @@ class MOFNetHIP(_Holder):
     def _tile(self):
         """Layout of the correlation volumes: 4 x 8 tiles (hip.VolTile) on the split-row path - a lookup window then lies in
         ~8 lines of 128 bytes instead of ~13, 149 -> 107 us per lookup at 1080p (tools/exp/lookup_tiled.py) - for the price
-        of whole edge tiles (+3.4 % GEMM columns at 1080p).  VFML_VOL_TILE=0: row-major (A/B switch; same fields)."""
-        if not self._split() or os.environ.get("VFML_VOL_TILE", "1") == "0":
+        of whole edge tiles (+3.4 % GEMM columns at 1080p).  'f32': row-major."""
+        if not self._split():
             return None
         return self._VOL_TILE
 
@@ -415,16 +401,15 @@ class MOFNetHIP(_Holder):
         # split-f16 path: activations are split rows (written by instnorm_apply, read by the LDS-DMA convolution
         # kernel); every convolution leaves per-block sums of its raw result behind (its tile is in LDS anyway) and
         # only the fold remains.  Blocks (128 output pixels after the f32-source stem, 32 after split-row sources)
-        # must not straddle frames.
+        # must not straddle frames.  Measured at 1080p against f32 rows split while register-staged: 0.2 ms per field
+        # faster (26.27 / 26.26 vs 26.42 / 26.50 ms, profiles/r02_kernel_anatomy.md).
         split_prec = self._split()
-        AF = hip.FMT_S16 if (split_prec and self._enc_split_rows()) else hip.FMT_F32
+        AF = hip.FMT_S16 if split_prec else hip.FMT_F32
         part_len = n * ((h2 * w2 + 31) // 32) * 64 * 2            # largest layer: half resolution, 64 channels
         parts = self._buf("enc_part", 3 * part_len, dev, torch.float64) if split_prec else None
         # (the norm fold's first pass; like every encoder workspace it belongs to this engine, and whatever runs the
         # encoders on another stream - prefetch_frames - is ordered against the main stream's use by _join_prefetch)
         fold_ws = self._buf("enc_foldws", min(n, 8) * 64 * 128 * 2, dev, torch.float64) if split_prec else None
-
-        enc_c64 = os.environ.get("VFML_ENC_C64", "1") != "0"         # (A/B switch: the general kernel for layer1's convolutions)
 
         def conv_stats(src, c, hh_, ww_, name, planes, dst, slot, k, stride=1, pad=0, src_fmt=hip.FMT_F32):
             wgt, b = P[name]
@@ -438,7 +423,7 @@ class MOFNetHIP(_Holder):
                 return stats_of(dst, hw, planes, slot)
             chunks = (hw + rows - 1) // rows
             part = parts[slot * part_len:]
-            if (enc_c64 and c == 64 and planes == 64 and k == 3 and stride == 1 and pad == 1 and nm == 3 and src_fmt == hip.FMT_S16
+            if (c == 64 and planes == 64 and k == 3 and stride == 1 and pad == 1 and nm == 3 and src_fmt == hip.FMT_S16
                     and ww_ % 32 == 0 and getattr(wgt, "order", None) == hip.KORDER_CBLOCK and wgt.kp == 576 and wgt.lo is not None):
                 # the residual blocks of layer1: persistent workgroups, weights in registers, one patch per tile (same bits)
                 hip.conv3x3_c64(src, c, n, hh_, ww_, wgt, b, dst, planes, stats_part=part)
@@ -567,38 +552,24 @@ class MOFNetHIP(_Holder):
         keys = [(k, H, W, L, self._plan_key(), self._packed_serial) for k in frame_keys]
         need_f = [j for j in range(N) if ("f", keys[j]) not in self._feat_cache]
         need_c = [j for j in range(1, N - 1) if ("c", keys[j]) not in self._feat_cache]
-        # ... and the window's new correlation pyramids: HBM-write-bound GEMMs beside MFMA-bound iterations
-        need_p = self._prefetch_pyramids() and any(("p", keys[c], keys[t]) not in self._feat_cache
-                                                   for c in range(1, N - 1) for t in (c + 1, c - 1))
-        if not need_f and not need_c and not need_p:
+        if not need_f and not need_c:
             return
         main = torch.cuda.current_stream(dev)
         side = self._side.get(dev)
         if side is None:
-            # (VFML_PREFETCH_PRIO: HIP stream priority of the prefetch stream - larger = lower; A/B switch)
-            side = self._side[dev] = torch.cuda.Stream(device=dev, priority=int(os.environ.get("VFML_PREFETCH_PRIO", "0")))
+            side = self._side[dev] = torch.cuda.Stream(device=dev)
         P = self._pack(dev)
-        dbg = os.environ.get("VFML_PREFETCH_DBG", "")
-        if "serial" in dbg:
+        if "serial" in os.environ.get("VFML_PREFETCH_DBG", ""):
             side.wait_stream(main)
         else:
             side.wait_event(self._pre_body)
-        if "nof" in dbg:
-            need_f = []
-        if "noc" in dbg:
-            need_c = []
         frames.record_stream(side)       # (a view of the caller's clip: its block must outlive the side stream's reads)
         with torch.cuda.stream(side):
             new = []
-            feats = None
-            if need_f or need_p:
-                feats = self._frame_features(frames, list(range(N)) if need_p else need_f, keys, H, W, P, dev, L, hl, wl, Sl,
-                                             vt=geo.VT)
-                new += list(feats.values())
+            if need_f:
+                new += list(self._frame_features(frames, need_f, keys, H, W, P, dev, L, hl, wl, Sl, vt=geo.VT).values())
             if need_c:
                 new += list(self._frame_context(frames, need_c, keys, H, W, P, dev, h * w, N - 2).values())
-            if need_p:
-                new.append(self._window_pyramids(feats, keys, N, geo, dev, protect=self._pyr_busy))
             done = torch.cuda.Event()
             done.record(side)
         # the cached tensors were allocated on the side stream and will be read (and one day freed) under the main one
@@ -617,15 +588,13 @@ class MOFNetHIP(_Holder):
         walk(new)
         self._prefetch_done, self._prefetch_dev = done, dev
 
-    def _pyramid_buffers(self, sizes, dev, limit, protect=()):
+    def _pyramid_buffers(self, sizes, dev, limit):
         """Level buffers for a new correlation pyramid (5.6 GB at 1080p).  When the pyramid cache is at its
         limit the least recently used pyramid is retired FIRST and its buffers are handed to the new one:
         in the steady state of a sliding job no field allocates (a 5.6 GB hipMalloc costs up to 150 ms, and
         retiring only after the new allocation made the third field of every job pay for one)."""
         while sum(1 for k in self._feat_cache if k[0] == "p") >= limit:
-            oldest = next((k for k in self._feat_cache if k[0] == "p" and k not in protect), None)
-            if oldest is None:        # everything cached is being read on another stream: a fresh allocation it is
-                break
+            oldest = next(k for k in self._feat_cache if k[0] == "p")
             self._pyr_free.append(self._feat_cache.pop(oldest))
         for i, bufs in enumerate(self._pyr_free):
             if [b.numel() for b in bufs] == sizes and bufs[0].device == dev:
@@ -683,25 +652,17 @@ class MOFNetHIP(_Holder):
         return types.SimpleNamespace(L=L, AF=AF, hl=hl, wl=wl, Sl=Sl, VT=VT, Nl=Nl, Pv=Pv, TILE=TILE, vol16=mask, VF=VF,
                                      VFl=VFl, ldl=ldl, psz=psz)
 
-    def _prefetch_pyramids(self):
-        """VFML_PREFETCH_PYR=1: the next window's new correlation pyramids are built on the prefetch stream too.  Off: the
-        resident workgroups of the persistent volume GEMM take a workgroup slot of every CU from the iterations'
-        convolutions for as long as they run - 24.75 ms per field with it against 24.70 without (fields bit-identical)."""
-        return os.environ.get("VFML_PREFETCH", "1") != "0" and os.environ.get("VFML_PREFETCH_PYR", "0") == "1" and not self.tri_frame
-
-    def _window_pyramids(self, feats, keys, N, geo, dev, protect=()):
+    def _window_pyramids(self, feats, keys, N, geo, dev):
         """K3/K4: the correlation pyramids of a window, one per problem (query frame -> target frame): level l is one GEMM of
         the query frame's features against the 2^l-pooled features of the target frame.  A pyramid depends on its two frames
         only, so with frame keys it is kept across windows: consecutive sliding windows share 2(N-3) of their 2(N-2)
-        problems.  Returns {"f": [...], "b": [...]} (per centre frame, a list of level buffers).
-        protect: cache keys of pyramids another stream is reading - their buffers are not recycled for new ones."""
+        problems.  Returns {"f": [...], "b": [...]} (per centre frame, a list of level buffers)."""
         D, L = self.cfg.feat_dim, geo.L
         AF, VFl, Nl, Pv, ldl, psz = geo.AF, geo.VFl, geo.Nl, geo.Pv, geo.ldl, geo.psz
         scale = 1.0 / float(D) ** 0.5
         if AF == hip.FMT_S16:
             scale /= self.FMAP_ROW_SCALE       # the split-row query features carry a factor 16
-        # (two more than a window and its reverse twin need when the next window's are built beside this one's iterations)
-        lim = 2 * (N - 2) + 2 + (2 if self._prefetch_pyramids() else 0)
+        lim = 2 * (N - 2) + 2
         pyrs = {"f": [], "b": []}
         for c in range(1, N - 1):
             for d, tgt in (("f", c + 1), ("b", c - 1)):
@@ -713,7 +674,7 @@ class MOFNetHIP(_Holder):
                     else:
                         # (registered before it is filled: same stream, and the next allocation then sees
                         # the right count and retires a stale pyramid instead of asking the allocator)
-                        pyr = self._pyramid_buffers(psz, dev, limit=lim, protect=protect)
+                        pyr = self._pyramid_buffers(psz, dev, limit=lim)
                         self._cache_put("p", pk, pyr, limit=lim)
                     # Level 0 of the reverse problem (tgt -> c) is the transpose of this one's: when it is
                     # going to be needed (tgt is, or next field becomes, a centre frame: the "f" problems of
@@ -724,11 +685,10 @@ class MOFNetHIP(_Holder):
                     # order of a transposed forward volume: both routes give the same bits)
                     rk = ("p", keys[tgt], keys[c]) if pk is not None else None
                     gemm_form = AF == hip.FMT_S16 and Pv % 4 == 0 and Nl[0] >= 1024
-                    dual = (rk is not None and d == "f" and gemm_form and ("p", rk) not in self._feat_cache
-                            and not os.environ.get("VFML_NO_DUAL"))      # (A/B switch; results are identical)
+                    dual = rk is not None and d == "f" and gemm_form and ("p", rk) not in self._feat_cache
                     rev = None
                     if dual:
-                        rev = self._pyramid_buffers(psz, dev, limit=lim, protect=protect)
+                        rev = self._pyramid_buffers(psz, dev, limit=lim)
                         self._cache_put("p", rk, rev, limit=lim)
                     cnm = self._nm("corr") if self._split() else 3
                     for l in range(L):
@@ -879,8 +839,6 @@ class MOFNetHIP(_Holder):
 
             # K3/K4 correlation pyramids, one per problem (query frame -> target frame)
             pyrs = self._window_pyramids(feats, keys, N, geo, dev)
-            self._pyr_busy = ({("p", keys[c], keys[t]) for c in range(1, N - 1) for t in (c + 1, c - 1)}
-                              if keys is not None else set())
 
             # Recurrent state, one row of GLD floats per cell:  [ z | r*h | h | inp | mf | mt ]
             # (one allocation, so that cat([r*h, x]) and cat([h, x]) are channel slices of it)
@@ -931,9 +889,8 @@ class MOFNetHIP(_Holder):
             # and those are named by two device tables.  With cfg.use_graph the sequence is captured into a HIP
             # graph the second time a configuration is seen and replayed from then on (~250 launches per field
             # become one; same kernels, same order: bit-identical results).
-            # both directions behind one another in one table: the two lookups of an iteration as ONE launch (at most 8 maps;
-            # A/B switch VFML_LOOKUP_BIDIR=0)
-            bidir = 2 * M <= 8 and 2 * M * L <= 48 and os.environ.get("VFML_LOOKUP_BIDIR", "1") != "0"
+            # both directions behind one another in one table: the two lookups of an iteration as ONE launch (at most 8 maps)
+            bidir = 2 * M <= 8 and 2 * M * L <= 48
             if bidir:
                 tab_fb = self._buf("pyr_table_fb", 64, dev, torch.int64)
                 hip.ptr_table_set(tab_fb, [p for d in ("f", "b") for m in pyrs[d] for p in m])
@@ -958,9 +915,7 @@ class MOFNetHIP(_Holder):
                     branch = self._side2.get(dev)
                     if branch is None:
                         branch = self._side2[dev] = torch.cuda.Stream(device=dev)
-                # (A/B switch: VFML_FUSE_HEAD=0 runs the flow head's two layers as two launches)
-                fuse_head = os.environ.get("VFML_FUSE_HEAD", "1") != "0" and AF == hip.FMT_S16
-                fuse_flow = os.environ.get("VFML_FUSE_FLOW", "1") != "0" and AF == hip.FMT_S16      # (A/B switch, as above)
+                fuse = AF == hip.FMT_S16          # the fused flow-head / flow-half launches read split rows
                 for it in range(cfg.decoder_depth):
                     # pick_only: the caller takes flow M (the backward flow of the first centre frame - the reference's
                     # `[0, shape[1]//2]`).  Going back from the last iteration, centre 0's result depends on one centre
@@ -976,7 +931,7 @@ class MOFNetHIP(_Holder):
                     def flow_half(nm=nm):
                         wgt, b = P[f"{ub}.encoder.convf1"]
                         wgt2, b2 = P[f"{ub}.encoder.convf2"]
-                        if (fuse_flow and self._rows7 and mf(f"{ub}.encoder.convf1") == 1 and mf(f"{ub}.encoder.convf2") == 1
+                        if (fuse and self._rows7 and mf(f"{ub}.encoder.convf1") == 1 and mf(f"{ub}.encoder.convf2") == 1
                                 and getattr(wgt2, "order", None) == hip.KORDER_CBLOCK64 and wgt.kp == 224 and wgt2.kp == 1152):
                             # both layers in one launch, the 128-channel map between them in LDS (vfml_flow_half; same bits)
                             hip.flow_half(flow4, nm, h, w, wgt, b, wgt2, b2, cf, 256, out_off=192)
@@ -1058,7 +1013,7 @@ class MOFNetHIP(_Holder):
                     wgt, b = P[f"{ub}.flow_head.conv1"]
                     wgt2, b2 = P[f"{ub}.flow_head.conv2"]
                     nm_head = mf(f"{ub}.flow_head.conv1")
-                    if self._tapsum and fuse_head and nm_head in (3, "2a") and mf(f"{ub}.flow_head.conv2") == nm_head:
+                    if self._tapsum and fuse and nm_head in (3, "2a") and mf(f"{ub}.flow_head.conv2") == nm_head:
                         # both layers in ONE launch (vfml_conv_desc.proj_out): the 256-channel map stays in LDS, the launch
                         # leaves two partial 36-column maps (one per 128-channel half) that the tap sum adds
                         hip.conv2d(G, 128, GLD, ng, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
@@ -1100,7 +1055,7 @@ class MOFNetHIP(_Holder):
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), vol16,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), os.environ.get("VFML_FUSE_HEAD", "1"), bidir, os.environ.get("VFML_FUSE_FLOW", "1"))
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"))
             self._pre_body = torch.cuda.Event()
             self._pre_body.record(torch.cuda.current_stream(dev))      # (what a prefetch of the next window waits for)
             self._run_body(body, gkey, dev)
