@@ -578,6 +578,11 @@ def test_graph_replay_of_the_iteration_body_is_bit_identical(gpu):
 
 
 MIXED_TOL = 1e-4    # px: the mixed plan's budget at 1080p, a tenth of north_star's tolerance
+# max EPE <= MIXED_R x mean EPE against the CPU oracle: the deviation of the plan's own oracle from the plain oracle has
+# max / mean <= 4.0 at the small sizes (tests_support.MIXED_MAX_OVER_MEAN_CPU, measured in test_noise_floor.py), float32 noise
+# 3 to 6; times 4 for the maximum over a field with 130 times as many pixels: 16.  A field of rounding errors has no
+# outliers; one block or edge that is wrong has.
+MIXED_R = 4.0 * 4.0
 
 
 def test_mixed_plan_stays_within_its_budget_at_1080p(gpu):
@@ -629,6 +634,8 @@ def test_mixed_plan_stays_within_its_budget_at_1080p(gpu):
             worst = max(worst, float(e.mean()))
             print(f"mixed plan 1080p seed {seed} T={T}: mean EPE {float(e.mean()):.3e} px, max {float(e.max()):.3e} px vs {tag}")
             assert float(e.mean()) <= MIXED_TOL, (seed, T, float(e.mean()))
+            if seed == 0:
+                assert float(e.max()) <= MIXED_R * float(e.mean()), (T, float(e.max()), float(e.mean()))
         for n in nets.values():
             n.release_workspace()
         del nets

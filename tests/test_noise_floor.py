@@ -1,0 +1,190 @@
+"""CPU tests of the elementwise-parity helpers (tests/tests_support.py) and of the plan oracle (oracle/plan_oracle.py)."""
+import pytest
+import torch
+
+import tests_support as ts
+
+
+def _seeded(seed=0):
+    from vfml import get_cfg
+    from vfml.weights import seeded_state_dict
+    return seeded_state_dict(get_cfg(), seed)
+
+
+# ----------------------------------------------------------------------------- error_stats on constructed fields
+def test_error_stats_sees_one_block_where_the_mean_does_not():
+    """A 1080p field that is 0.4 px off in ONE 64 x 64 block: the mean stays below the old tolerance (EPE_TOL), the block
+    statistic reports 0.4 - for an interior block and for a ragged one at the bottom edge (1080 = 16 x 64 + 56 rows)."""
+    H, W = 1080, 1920
+    ref = torch.zeros(1, 2, 2, H, W)
+    for rows, cols in ((slice(320, 384), slice(640, 704)), (slice(1024, 1080), slice(1856, 1920))):
+        got = ref.clone()
+        got[0, 1, 0, rows, cols] = 0.4                      # flow 1 only, x component
+        s = ts.error_stats(got, ref)
+        npx = (rows.stop - rows.start) * 64
+        assert s["block"] == pytest.approx(0.4, rel=1e-6)
+        assert s["max"] == pytest.approx(0.4, rel=1e-6)
+        assert s["mean"] == pytest.approx(0.4 * npx / (H * W), rel=1e-6)
+        assert s["mean"] < ts.EPE_TOL                       # what the mean-only assertion lets through
+        assert s["p999"] == pytest.approx(0.4, rel=1e-6)    # 4096 of 2.07 M pixels are more than 0.1 % of them
+        assert s["per_flow"][0] == {k: 0.0 for k in ts.STAT_KEYS}
+        assert s["per_flow"][1]["block"] == s["block"]
+    # a block that straddles the tile grid is shared by four tiles
+    got = ref.clone()
+    got[0, 0, 1, 32:96, 32:96] = 0.4
+    assert ts.error_stats(got, ref)["block"] == pytest.approx(0.1, rel=1e-6)
+
+
+def test_error_stats_sees_the_outer_ring_where_the_mean_does_not():
+    """0.04 px off everywhere in the outer 8-pixel ring of a 1080p field (2.3 % of it): mean 9.2e-4 < EPE_TOL, ring 0.04."""
+    H, W = 1080, 1920
+    ref = torch.zeros(1, 2, 2, H, W)
+    got = ref.clone()
+    got[0, 0, 1] = 0.04
+    got[0, 0, 1, 8:H - 8, 8:W - 8] = 0.0
+    s = ts.error_stats(got, ref)
+    share = 1.0 - (H - 16) * (W - 16) / (H * W)
+    assert s["ring"] == pytest.approx(0.04, rel=1e-6)
+    assert s["mean"] == pytest.approx(0.04 * share, rel=1e-6) and s["mean"] < ts.EPE_TOL
+    assert s["block"] == pytest.approx(0.04 * (1 - 48 * 56 / (56 * 64)), rel=1e-6)       # a ragged corner tile: 56 x 64
+    assert s["per_flow"][1]["ring"] == 0.0
+    # an error inside the ring's inner edge is not in the ring statistic
+    got = ref.clone()
+    got[0, 0, 0, 8:H - 8, 8:W - 8] = 1.0
+    assert ts.error_stats(got, ref)["ring"] == 0.0
+
+
+def test_low_resolution_layout_and_stats():
+    """engine_low turns the engine's [M, h, w, 4] cells into the oracle's [1, 2M, 2, h, w]; low_stats uses 8-cell tiles
+    and a one-cell ring."""
+    M, h, w = 2, 17, 20
+    low = torch.arange(M * h * w * 4, dtype=torch.float32).view(M, h, w, 4)
+    o = ts.engine_low(low)
+    assert o.shape == (1, 2 * M, 2, h, w)
+    assert o[0, 1, 1, 3, 5] == low[1, 3, 5, 1] and o[0, 2, 0, 3, 5] == low[0, 3, 5, 2] and o[0, 3, 1, 16, 19] == low[1, 16, 19, 3]
+    ref = torch.zeros(1, 2, 2, h, w)
+    got = ref.clone()
+    got[0, 0, 0, 16, :] = 0.5                                # the last row of cells: a ragged tile row of one cell
+    s = ts.low_stats(got, ref)
+    assert s["block"] == pytest.approx(0.5) and s["ring"] == pytest.approx(0.5 * w / (2 * w + 2 * h - 4))
+    with pytest.raises(ValueError):
+        ts.error_stats(got[0], ref[0])
+
+
+# ----------------------------------------------------------------------------- the float64 oracle and N
+def test_noise_floor_is_rounding_noise_and_cached():
+    """N on a small input: not zero (the two oracles are different arithmetics), far below the old tolerance, and
+    max / mean of the order the issue measured (3 to 7; bounded at 20 here).  The oracle pair is computed once."""
+    sd = _seeded()
+    cfg = ts.oracle_cfg(decoder_depth=4)
+    x = ts.to_float_frames(ts.make_frames("clip", 3, 128, 128))
+    ora = ts.oracle_f64(cfg, sd)
+    assert all(p.dtype == torch.float64 for p in ora.parameters())
+    assert torch.equal(ora.fnet.conv1.weight.float(), sd["fnet.conv1.weight"])
+    N = ts.noise_floor(x, cfg, sd)
+    print("N (T3 128x128, depth 4):", ts.fmt_stats(N))
+    assert 0.0 < N["mean"] < ts.EPE_TOL / 30 and N["max"] < 20 * N["mean"]
+    assert N["mean"] <= N["p999"] <= N["max"] and N["mean"] <= N["block"] <= N["max"]
+    pair = ts.oracle_pair(x, cfg, sd)
+    assert pair is ts.oracle_pair(x.clone(), ts.oracle_cfg(decoder_depth=4), dict(sd))
+    assert pair["f64"][0].dtype == torch.float64 and pair["f32"][0].dtype == torch.float32
+    Nl = ts.noise_floor_low(x, cfg, sd)
+    assert 0.0 < Nl["mean"] < N["mean"]                      # cells, not pixels: an eighth
+
+
+@pytest.mark.parametrize("kind", ts.INPUT_KINDS)
+def test_input_kinds(kind):
+    f = ts.make_frames(kind, 3, 128, 160)
+    assert f.shape == (3, 128, 160, 3) and f.dtype == torch.uint8
+    if kind == "letterbox":
+        assert int(f[:, :24].max()) == 0 and int(f[:, 104:].max()) == 0 and int(f[:, 24:104].max()) > 0
+    if kind == "patch":
+        assert int((f != 128).any(-1).sum()) <= 3 * 32 * 48 and not torch.equal(f[0], f[1])
+    if kind in ("black", "white"):
+        assert f.unique().numel() == 1
+
+
+# ----------------------------------------------------------------------------- the plan oracle
+def test_plan_oracle_with_an_empty_plan_is_the_plain_oracle():
+    from oracle import plan_oracle as po
+    sd = _seeded()
+    cfg = ts.oracle_cfg(decoder_depth=3)
+    x = ts.to_float_frames(ts.make_frames("rand", 3, 128, 128))
+    for dt in (torch.float32, torch.float64):
+        plain = ts.oracle_f32(cfg, sd).to(dt)
+        plan = po.build_network(cfg, {}, "f32").eval()
+        plan.load_state_dict(sd)
+        plan.to(dt)
+        a, al = plain(x.to(dt), {})
+        b, bl = plan(x.to(dt), {})
+        assert torch.equal(a, b) and torch.equal(al, bl)
+
+
+def test_plan_oracle_names_counts_and_scales_as_the_engine_does():
+    """count_of is MOFNetHIP._nm for every layer name of both shipped plans; auto_scale is hip.SplitWeight.auto_scale."""
+    from oracle import plan_oracle as po
+    from vfml import build_network, get_cfg, hip
+    from vfml.cfg import BOF_F16_PLAN, DEFAULT_MIXED_PLAN
+    from vfml.weights import conv_spec
+    for a in (1e-3, 0.0441, 0.25, 1.0, 3.9, 16384.0, 0.0):
+        assert po.auto_scale(a) == hip.SplitWeight.auto_scale(a)
+    names = [n for n, *_ in conv_spec(get_cfg()) if ".gru." not in n] + ["corr"]
+    names += [f"update_block.gru.conv{g}{k}.{p}" for g in ("zr", "q") for k in "12" for p in ("iter", "ctx")]
+    for plan in (DEFAULT_MIXED_PLAN, BOF_F16_PLAN, {}, {"corr": "2a", "fnet": 2, "fnet.layer1": "2w"}):
+        cfg = get_cfg()
+        cfg.precision, cfg.mfma_plan = "mixed", dict(plan)
+        net = build_network(cfg)
+        for n in names:
+            assert po.count_of(plan, n) == net._nm(n), (n, plan)
+    # every convolution of the oracle carries a conv_spec name (what a plan's prefixes are matched against)
+    ora = po.build_network(ts.oracle_cfg(), DEFAULT_MIXED_PLAN, "f16@3")
+    convs = {n for n, m in ora.named_modules() if isinstance(m, torch.nn.Conv2d)}
+    assert convs == {n for n, *_ in conv_spec(get_cfg())}
+    w = torch.tensor([[0.3, -0.0441], [1e-4, 0.01]], dtype=torch.float64)
+    s = po.auto_scale(0.3)
+    assert s * 0.3 < 16384.0 <= 2 * s * 0.3
+    assert torch.equal(po.round_weight(w), (w * s).half().double() / s)
+    assert torch.equal(po.round_weight(w[1:], packed=w), (w[1:] * s).half().double() / s)
+
+
+def test_plan_oracle_restructured_paths_are_the_same_function(monkeypatch):
+    """With the f16 rounding itself switched off, the plan oracle's own routes - gate convolutions as [z | r] matrices in
+    an iteration part and a context part, pyramid levels from pooled target features, the first motion-encoder convolution -
+    compute what the plain oracle computes (float64: to 1e-10 px)."""
+    from oracle import plan_oracle as po
+    from vfml.cfg import BOF_F16_PLAN
+    sd = _seeded()
+    cfg = ts.oracle_cfg(decoder_depth=3)
+    x = ts.to_float_frames(ts.make_frames("clip", 4, 136, 160)).double()
+    ref, ref_low = ts.oracle_f64(cfg, sd)(x, {})
+    monkeypatch.setattr(po, "f16", lambda t: t)
+    net = po.build_network(cfg, BOF_F16_PLAN, "f16").eval()        # ("": 1 reaches every route)
+    net.load_state_dict(sd)
+    got, low = net.double()(x, {})
+    assert float((got - ref).abs().max()) < 1e-10 and float((low - ref_low).abs().max()) < 1e-10
+
+
+def test_default_plan_differs_from_the_plain_oracle_by_the_plans_size():
+    """The shipped plan in float64 against the plain float64 oracle, T3 128x128, seed 0: the plan's own error.  Expected
+    about 2e-5 px mean (the engine's mixed plan measures 4.5e-5 .. 8.8e-5 px at 1080p, budget 1e-4): asserted between three
+    times the float32 noise floor's mean and the budget.  max / mean of this deviation is the R that
+    test_mixed_plan_stays_within_its_budget_at_1080p holds the engine's seed-0 fields to (times 4 for the larger field)."""
+    from vfml.cfg import DEFAULT_MIXED_CORR_VOLUME, DEFAULT_MIXED_PLAN
+    sd = _seeded()
+    cfg = ts.oracle_cfg()
+    worst = 0.0
+    for T, H, W in ((3, 128, 128), (5, 128, 192)):
+        x = ts.to_float_frames(ts.make_frames("rand", T, H, W))
+        plain = ts.oracle_pair(x, cfg, sd)
+        plan = ts.oracle_pair(x, cfg, sd, DEFAULT_MIXED_PLAN, DEFAULT_MIXED_CORR_VOLUME)
+        dev = ts.error_stats(plan["f64"][0], plain["f64"][0])
+        N = ts.noise_floor(x, cfg, sd)
+        Np = ts.noise_floor(x, cfg, sd, DEFAULT_MIXED_PLAN, DEFAULT_MIXED_CORR_VOLUME)
+        worst = max(worst, dev["max"] / dev["mean"])
+        print(f"T{T} {H}x{W}: plan vs plain (f64): {ts.fmt_stats(dev)}; max/mean {dev['max'] / dev['mean']:.2f}; "
+              f"N {ts.fmt_stats(N)}; N_plan {ts.fmt_stats(Np)}")
+        assert 3 * N["mean"] < dev["mean"] < 1e-4
+        assert Np["mean"] < dev["mean"] / 2                 # the plan's rounding noise is small against the plan's error
+    print(f"largest max/mean of the default plan's deviation: {worst:.2f}")
+    assert worst < ts.MIXED_MAX_OVER_MEAN_CPU
+
