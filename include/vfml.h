@@ -27,6 +27,8 @@
 extern "C" {
 #endif
 
+/* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay and VFML_COMPOSE_GRID_2X3: additions only, every earlier
+ * entry point keeps its signature and its results, so the number did not move. */
 #define VFML_ABI_VERSION 25
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -438,15 +440,36 @@ int vfml_flow_correct(const unsigned char* frame1, const unsigned char* frame2, 
 enum { VFML_COLORIZE_HSV = 0, VFML_COLORIZE_WHEEL = 1 };
 int vfml_flow_colorize(const float* flow, int h, int w, int mode, void* workspace, unsigned char* out, void* stream);
 
-/* One output video frame from its tiles (reference visualization/video_composer.py: create_side_by_side :67-122), in
- * one pass.  tiles / tile_types: host arrays of 2 (SIDE_BY_SIDE, STACKED) or 4 (GRID_2X2) device images [h][w][3],
+/* Encoded motion vectors -> flow field: the inverse of vfml_flow_encode's RG8 / RGB8 modes as the reference decodes them
+ * (encoding/flow_encoders.py: MotionVectorsRG8FlowEncoder.decode, MotionVectorsRGB8FlowEncoder.decode 'rgb+' :336-343).
+ * encoded: [h][w][3] u8 RGB, rows contiguous, any alignment (the bottom half of an uploaded --flow-input frame is
+ * such a block); flow: [h][w][2] f32, 8-byte aligned; clamp = float32(clamp_range).  n = u8 / 255;
+ *   RG8   flow = (n * 2) * clamp - clamp                                   (B is not read)
+ *   RGB8  dx = n_r * 2 - 1, dy = n_g * 2 - 1, mag = (1 / sqrt(dx dx + dy dy + n_b n_b)) * clamp, flow = (dx, dy) * mag
+ * Every f32 step is rounded separately, quotient and root correctly: bit for bit the host decoder.  VFML_ENCODE_GAMEDEV
+ * and unknown modes are rejected.  DESIGN.md section 9. */
+int vfml_flow_decode(const unsigned char* encoded, int h, int w, int mode, float clamp, float* flow, void* stream);
+
+/* Radar picture of the difference of two flow fields (reference flow_processor.py: create_difference_overlay :490-578).
+ * flow_a, flow_b: [h][w][2] f32, 8-byte aligned; out: [h][w][3] u8 RGB.  m = sqrt(dx dx + dy dy) of a - b in f32, classes
+ * against the f32 values of the thresholds: m <= 0.1 green (0,255,0), <= 0.5 yellow (255,255,0), <= 1 orange
+ * (255,165,0), <= 2 red (255,0,0), > 2 magenta (255,0,255), NaN black.  The legend is drawn in the same pass: for
+ * i = 0..4, x = 10 + 45 i, y0 = h - 20, a white rectangle (x-1, y0-13)..(x+13, y0+1) and over it class i's colour
+ * (x, y0-12)..(x+12, y0), corners inclusive, clipped to the picture; its numbers are not drawn.  DESIGN.md section 9. */
+int vfml_flow_diff_overlay(const float* flow_a, const float* flow_b, int h, int w, unsigned char* out, void* stream);
+
+/* One output video frame from its tiles (reference visualization/video_composer.py: create_side_by_side :67-122,
+ * flow_processor.py: create_6_video_grid :1218-1269), in one pass.  tiles / tile_types: host arrays of 2 (SIDE_BY_SIDE,
+ * STACKED), 4 (GRID_2X2) or 6 (GRID_2X3) device images [h][w][3],
  * each VFML_PIX_U8 (RGB bytes) or an f32 / f64 TAA history, which becomes u8 by clip(0, 255) and truncation (NaN -> 0).
  *   SIDE_BY_SIDE  (2w x h)   tile 0 | tile 1                 (original | flow)
  *   STACKED       (w x 2h)   tile 0 over tile 1              (--flow-only)
  *   GRID_2X2      (2w x 2h)  tile 0 | tile 1 over 2 | 3      (original | flow over TAA | TAA simple)
+ *   GRID_2X3      (2w x 3h)  0 | 1 over 2 | 3 over 4 | 5     (... over TAA external flow | flow difference; --flow-input)
  * out: rows of row_stride bytes (>= 3 x output width; padding bytes are 0), channels RGB or BGR (VFML_COMPOSE_BGR),
  * top-down or bottom-up (VFML_COMPOSE_BOTTOM_UP, an AVI DIB).  DESIGN.md section 9.  SURVEY.md row 14. */
-enum { VFML_COMPOSE_SIDE_BY_SIDE = 0, VFML_COMPOSE_STACKED = 1, VFML_COMPOSE_GRID_2X2 = 2 };
+enum { VFML_COMPOSE_SIDE_BY_SIDE = 0, VFML_COMPOSE_STACKED = 1, VFML_COMPOSE_GRID_2X2 = 2,
+       VFML_COMPOSE_GRID_2X3 = 3 };
 enum { VFML_COMPOSE_BGR = 1, VFML_COMPOSE_BOTTOM_UP = 2 };
 int vfml_compose_frame(const void* const* tiles, const int* tile_types, int h, int w, int layout, int flags,
                        int64_t row_stride, unsigned char* out, void* stream);

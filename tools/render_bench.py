@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Render-stage throughput: the visualiser's "Run TAA processor" command (flow_processor.py --taa --skip-lods --tile
 --flow-format hsv --use-flow-cache <cache>) on a synthetic:WxHxN clip with a complete cache of seeded fields, MJPG and
---uncompressed.  Prints one JSON line per codec: frames, seconds, frames/s, file size.
+--uncompressed.  Prints one JSON line per codec: frames, seconds, frames/s, file size.  With --flow-input each codec gets
+a second job: the same cache rendered with --flow-only --flow-format motion-vectors-rg8 (the flow video), then
+--taa --flow-input <that video> --flow-format motion-vectors-rg8, the 2x3 comparison grid.
 
-    python tools/render_bench.py --size 1920x1080 --frames 60 [--device cuda] [--codec mjpg|raw|both]
+    python tools/render_bench.py --size 1920x1080 --frames 60 [--device cuda] [--codec mjpg|raw|both] [--flow-input]
 """
 import argparse
 import contextlib
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--codec", choices=["mjpg", "raw", "both"], default="both")
+    ap.add_argument("--flow-input", action="store_true", help="also render the 2x3 --flow-input grid")
     ap.add_argument("--work", default=None)
     a = ap.parse_args()
     import flow_processor as fp
@@ -42,11 +45,11 @@ def main():
         f += rng.normal(0, 0.3, f.shape).astype(np.float32)
         mgr.save_flow_to_cache(f, cache, i, 'npz')
     spec = f"synthetic:{w}x{h}x{a.frames}"
-    for codec in (["mjpg", "raw"] if a.codec == "both" else [a.codec]):
-        out = os.path.join(work, f"out_{codec}")
+    def run(job, codec, extra, keep=False):
+        out = os.path.join(work, f"out_{job}_{codec}")
         os.makedirs(out, exist_ok=True)
-        argv = ["--input", spec, "--output", out, "--device", a.device, "--frames", str(a.frames), "--taa",
-                "--skip-lods", "--tile", "--flow-format", "hsv", "--use-flow-cache", cache]
+        argv = ["--input", spec, "--output", out, "--device", a.device, "--frames", str(a.frames), "--skip-lods",
+                "--tile", "--use-flow-cache", cache] + extra
         if codec == "raw":
             argv.append("--uncompressed")
         buf = io.StringIO()
@@ -56,13 +59,27 @@ def main():
         dt = time.time() - t0
         line = [ln for ln in buf.getvalue().splitlines() if ln.startswith("Video written")]
         avi = [os.path.join(out, n) for n in os.listdir(out) if n.endswith(".avi")]
-        print(json.dumps({"codec": codec, "size": a.size, "frames": a.frames, "rc": rc, "wall_s": round(dt, 3),
-                          "render_line": line[0] if line else None,
+        print(json.dumps({"job": job, "codec": codec, "size": a.size, "frames": a.frames, "rc": rc,
+                          "wall_s": round(dt, 3), "render_line": line[0] if line else None,
                           "bytes": os.path.getsize(avi[0]) if avi else None}), flush=True)
-        for p in avi:
-            os.remove(p)
+        if not keep:
+            for p in avi:
+                os.remove(p)
+        return rc, avi
+
+    for codec in (["mjpg", "raw"] if a.codec == "both" else [a.codec]):
+        rc, _ = run("taa", codec, ["--taa", "--flow-format", "hsv"])
         if rc != 0:
             return rc
+        if a.flow_input:
+            mv = ["--flow-format", "motion-vectors-rg8"]
+            rc, avi = run("flow_only", codec, ["--flow-only"] + mv, keep=True)
+            if rc == 0:
+                rc, _ = run("flow_input", codec, ["--taa", "--flow-input", avi[0]] + mv)
+            for p in avi:
+                os.remove(p)
+            if rc != 0:
+                return rc
     return 0
 
 

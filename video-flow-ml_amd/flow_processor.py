@@ -11,10 +11,14 @@ cache files of its own fields - tiled jobs with the tiles streaming to rank 0 in
 Without --interactive (the reference's normal mode) the complete cache is then rendered into the output video
 (`render_video`, reference process_video :635-1173): original | flow side by side, stacked (--flow-only) or a 2x2 grid
 with the two TAA results (--taa), MJPG or --uncompressed AVI, on the device by vfml_flow_encode / vfml_flow_colorize /
-vfml_taa_blend / vfml_compose_frame, or with the host paths under --device cpu.  Out of scope: decoding
-video with OpenCV, text labels on the tiles, --flow-input and the Tk/Qt tools; flags that only concern those are
-accepted and reported as skipped.  Inputs: a `.npy` file holding uint8 frames [F,H,W,3]; `synthetic:WxHxF`
-(vfml.synth); or any video file when OpenCV is importable.
+vfml_taa_blend / vfml_compose_frame, or with the host paths under --device cpu.  With `--taa --flow-input VIDEO` (the
+reference's comparison mode, :436-578, :724-765, :1009-1127) a second video carries external motion vectors in its
+bottom half - the layout `--flow-only --flow-format motion-vectors-rg8|rgb8` writes - and the output is a 2x3 grid:
+original | external flow picture over TAA | TAA simple over TAA with the external flow | flow difference
+(vfml_flow_decode, vfml_flow_diff_overlay, the GRID_2X3 layout of vfml_compose_frame).  Out of scope:
+text labels on the tiles and the Tk/Qt tools; flags that only concern those are accepted and reported as skipped.
+Inputs: a `.npy` file holding uint8 frames [F,H,W,3]; `synthetic:WxHxF` (vfml.synth); an `.avi` file of the kinds
+storage/avi_writer.py writes (storage/avi_reader.py); or any video file when OpenCV is importable.
 """
 import argparse
 import os
@@ -91,6 +95,17 @@ def validate_frame_range(start_frame, frame_count, total_frames):
     return start_frame, min(frame_count, total_frames - start_frame)
 
 
+def _own_avi_reader(spec):
+    """True when `spec` is an .avi file and OpenCV is not importable: storage/avi_reader.py reads it then."""
+    if not spec.lower().endswith('.avi'):
+        return False
+    try:
+        import cv2  # noqa: F401
+    except ImportError:
+        return True
+    return False
+
+
 def probe_input(spec):
     """-> (fps, total_frames) of an input without decoding it."""
     if spec.startswith('synthetic:'):
@@ -98,6 +113,10 @@ def probe_input(spec):
         return SYNTHETIC_FPS, n
     if spec.endswith('.npy'):
         return SYNTHETIC_FPS, int(np.load(spec, mmap_mode='r').shape[0])
+    if _own_avi_reader(spec):
+        from storage import avi_reader
+        info = avi_reader.probe(spec)
+        return info["fps"], info["frames"]
     try:
         import cv2
     except ImportError:
@@ -137,6 +156,10 @@ def load_frames(spec, start_frame, max_frames, fps_default=SYNTHETIC_FPS):
         if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
             raise ValueError(f"{spec}: expected uint8 [F,H,W,3], got {arr.dtype} {arr.shape}")
         frames = [np.ascontiguousarray(f) for f in arr[start_frame:start_frame + max_frames]]
+    elif _own_avi_reader(spec):
+        from storage import avi_reader
+        fps_default = avi_reader.probe(spec)["fps"] or fps_default
+        frames = avi_reader.read_frames(spec, start_frame, max_frames)
     else:
         try:
             import cv2
@@ -196,6 +219,112 @@ def render_output_path(args, fps, log=print):
     return output_path
 
 
+FLOW_INPUT_VARIANTS = {'motion-vectors-rg8': 'rg8', 'motion-vectors-rgb8': 'rgb8'}
+
+
+def check_flow_input(args):
+    """--flow-input's argument checks, before anything is computed or rendered (reference :648-650, :483-484)."""
+    if not os.path.exists(args.flow_input):
+        raise ValueError(f"Flow input video not found: {args.flow_input}")
+    if args.flow_format not in FLOW_INPUT_VARIANTS:
+        raise ValueError(f"Unsupported flow format: {args.flow_format}")
+
+
+class FlowInputVideo:
+    """The --flow-input video: frames in order from frame 0, one at a time (`.npy` stack, an AVI through
+    storage/avi_reader.py, anything else through OpenCV).  `total`, `width`, `height` come from the headers."""
+
+    def __init__(self, spec):
+        self.spec, self._arr, self._avi, self._cap, self._pos = spec, None, None, None, 0
+        if spec.endswith('.npy'):
+            arr = np.load(spec, mmap_mode='r')
+            if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
+                raise ValueError(f"{spec}: expected uint8 [F,H,W,3], got {arr.dtype} {arr.shape}")
+            self._arr, self.total, self.height, self.width = arr, *(int(v) for v in arr.shape[:3])
+        elif _own_avi_reader(spec):
+            from storage.avi_reader import AviReader
+            self._avi = AviReader(spec)
+            self.total, self.height, self.width = self._avi.frame_count, self._avi.height, self._avi.width
+        else:
+            try:
+                import cv2
+            except ImportError:
+                raise SystemExit(f"Cannot decode {spec}: OpenCV is not installed. Use a .npy frame stack or an .avi "
+                                 f"file (uncompressed or MJPG).")
+            self._cv2, self._cap = cv2, cv2.VideoCapture(spec)
+            self.total = int(self._cap.get(cv2.CAP_PROP_FRAME_COUNT))
+            self.height = int(self._cap.get(cv2.CAP_PROP_FRAME_HEIGHT))
+            self.width = int(self._cap.get(cv2.CAP_PROP_FRAME_WIDTH))
+
+    def read(self):
+        """-> the next RGB frame [H,W,3] uint8, or None after the last."""
+        if self._arr is not None:
+            frame = np.ascontiguousarray(self._arr[self._pos]) if self._pos < self.total else None
+        elif self._avi is not None:
+            frame = self._avi.read()
+        else:
+            ok, bgr = self._cap.read()
+            frame = self._cv2.cvtColor(bgr, self._cv2.COLOR_BGR2RGB) if ok else None
+        self._pos += frame is not None
+        return frame
+
+    def close(self):
+        if self._avi is not None:
+            self._avi.close()
+        if self._cap is not None:
+            self._cap.release()
+
+
+class _ExternalFlowSource:
+    """The encoded pictures of --flow-input, one per main frame (reference :724-765 and extract_flow_from_video
+    :436-488): taken from frame 0 of the flow video whatever the main clip's start frame is, rows H//2... of each frame;
+    a shorter flow video repeats its last picture.  The reference decodes the whole list up front; here the next
+    pictures are read ahead on one thread and decoded when their frame is rendered."""
+
+    def __init__(self, spec, n, width, height, log):
+        from concurrent.futures import ThreadPoolExecutor
+        log("[Flow Input] Extracting flow from external video...")
+        self.video = FlowInputVideo(spec)
+        try:
+            self.take = min(n, self.video.total)
+            log(f"  Flow input has {self.video.total} frames")
+            log(f"  Main video has {n} frames")
+            log(f"  Will extract {self.take} flow frames starting from frame 0")
+            self.top = self.video.height // 2
+            got = (self.video.height - self.top, self.video.width)
+            if got != (height, width):
+                raise ValueError(f"Flow input video is {self.video.width}x{self.video.height}: its encoded bottom half "
+                                 f"is {got[1]}x{got[0]}, the main video is {width}x{height}")
+            log(f"Extracting flow from {self.take} frames...")
+            if self.take == 0:
+                raise ValueError("No flow data could be extracted from flow input video")
+            if self.take < n:
+                log(f"  Warning: Flow input shorter than main video. Extended from {self.take} to {n} frames using last "
+                    f"frame.")
+            log(f"  Successfully prepared {n} flow frames")
+            log("")
+        except Exception:
+            self.video.close()
+            raise
+        self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="flow-input")
+        self.futs, self.next = {}, 0
+
+    def _read(self):
+        frame = self.video.read()
+        return None if frame is None else frame[self.top:]
+
+    def get(self, i, ahead=2):
+        """-> the encoded picture [h,w,3] uint8 of main frame i (i ascending), or None: repeat the one before."""
+        while self.next < min(self.take, i + ahead + 1):
+            self.futs[self.next] = self.pool.submit(self._read)
+            self.next += 1
+        return self.futs.pop(i).result() if i in self.futs else None
+
+    def close(self):
+        self.pool.shutdown(cancel_futures=True)
+        self.video.close()
+
+
 class _FieldReader:
     """Reads cache fields ahead of use on a small thread pool, in frame order."""
 
@@ -221,10 +350,13 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     its order): flow picture, the two TAA histories (--taa), the composed frame, the writer.  Device path: the frames
     are the clip on the device, each field goes up through a pinned ring, every step is a HIP kernel, and the composed
     frame - already in the AVI chunk's layout - comes back through a pinned ring one frame behind the GPU.  --device
-    cpu runs the same loop with the host implementations."""
+    cpu runs the same loop with the host implementations.  With --taa --flow-input the frame is the 2x3 grid: the
+    flow video's encoded half is decoded per frame (vfml_flow_decode), feeds a third TAA history and the difference
+    overlay (vfml_flow_diff_overlay), and its re-encoded picture takes the flow tile's place."""
     from effects.taa_processor import TAAProcessor
     from storage.avi_writer import AviWriter, dib_stride
-    from visualization.video_composer import compose_device, create_side_by_side
+    from visualization.video_composer import (compose_device, create_6_video_grid, create_difference_overlay,
+                                              create_side_by_side)
 
     n = len(frames)
     output_path = render_output_path(args, fps, log)
@@ -232,6 +364,16 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     log(f"Video FPS: {fps:.2f}")
     flow_only, taa = args.flow_only, args.taa and not args.flow_only     # --flow-only's stacked frame shows no TAA
     size = (width, height * 2) if args.flow_only else ((width * 2, height * 2) if args.taa else (width * 2, height))
+    external = None
+    if args.flow_input is not None:
+        check_flow_input(args)
+        if args.flow_only:
+            log("note: --flow-only writes the stacked frame without TAA, so --flow-input's 2x3 grid is not rendered")
+        elif not args.taa:
+            log("note: --flow-input is compared in the --taa grid only; without --taa the ordinary video is rendered")
+        else:
+            external = _ExternalFlowSource(args.flow_input, n, width, height, log)
+            size = (width * 2, height * 3)
     if args.uncompressed:
         log("Using uncompressed video codec. Output will be .avi and file size will be very large.")
     else:
@@ -242,16 +384,18 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     writer = AviWriter(output_path, 0 if args.uncompressed else 'MJPG', fps, size, workers=jpeg_workers,
                        depth=jpeg_workers + 1, log=log)
     encoder = render_encoder(args.flow_format, args.motion_vectors_clamp_range)
-    taa_flow, taa_simple = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
+    taa_flow, taa_simple, taa_external = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
+    variant = FLOW_INPUT_VARIANTS.get(args.flow_format)
     reader = _FieldReader(FlowCacheManager(), cache_dir, fmt, n)
     log(ENCODER_LINES.get(args.flow_format, ENCODER_LINES['gamedev']).format(c=args.motion_vectors_clamp_range))
     t0 = time.time()
     try:
         if not gpu:
-            prev = None
+            from encoding.flow_encoders import decode_motion_vectors
+            prev = ext_flow = None
             for i in range(n):
                 field = reader.get(i)
-                viz = encoder.encode(field, width, height)
+                viz = encoder.encode(field, width, height) if external is None else None
                 taa_frame = taa_simple_frame = None
                 if taa:
                     taa_frame = taa_flow.apply_taa(frames[i], flow_pixels=prev, alpha=0.1, use_flow=True,
@@ -259,12 +403,27 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
                     taa_simple_frame = taa_simple.apply_taa(frames[i], flow_pixels=None, alpha=0.1, use_flow=False,
                                                             sequence_id='simple_taa')
                 prev = field
+                if external is not None:
+                    # this frame's external flow from frame 0 on, where the computed-flow TAA uses the previous field
+                    picture = external.get(i)
+                    if picture is not None:
+                        ext_flow = decode_motion_vectors(picture, clamp_range=args.motion_vectors_clamp_range,
+                                                         format_variant=variant)
+                    taa_ext = taa_external.apply_taa(frames[i], flow_pixels=ext_flow, alpha=0.1, use_flow=True,
+                                                     sequence_id='external_taa')
+                    writer.write(create_6_video_grid(frames[i], encoder.encode(ext_flow, width, height), taa_frame,
+                                                     taa_simple_frame, taa_ext,
+                                                     create_difference_overlay(field, ext_flow)))
+                    continue
                 writer.write(create_side_by_side(frames[i], viz, flow_only=flow_only, taa_frame=taa_frame,
                                                  taa_simple_frame=taa_simple_frame, flow_format=args.flow_format))
         else:
             _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size,
-                           args.uncompressed, taa_flow, taa_simple, dib_stride, compose_device)
+                           args.uncompressed, taa_flow, taa_simple, dib_stride, compose_device, external=external,
+                           taa_external=taa_external, variant=variant, clamp_range=args.motion_vectors_clamp_range)
     finally:
+        if external is not None:
+            external.close()
         reader.close()
         writer.release()
     dt = time.time() - t0
@@ -273,7 +432,9 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
 
 
 def _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size, uncompressed,
-                   taa_flow, taa_simple, dib_stride, compose_device):
+                   taa_flow, taa_simple, dib_stride, compose_device, external=None, taa_external=None, variant=None,
+                   clamp_range=32.0):
+    from vfml import hip
     n = len(frames)
     if feeder is None:
         feeder = ClipFeeder(frames, device)
@@ -281,6 +442,12 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
     # fields: host -> pinned slot -> device; a slot is refilled once its copy has left it
     fslots = [torch.empty((height, width, 2), dtype=torch.float32).pin_memory() for _ in range(3)]
     fevents = [None] * len(fslots)
+    # --flow-input: the encoded pictures (3 bytes per pixel) take the same way and are decoded on the device
+    eslots = [torch.empty((height, width, 3), dtype=torch.uint8).pin_memory() for _ in range(3)] if external else []
+    eevents = [None] * len(eslots)
+    uploads = 0
+    ext_flow = None
+    decode_mode = hip.ENCODE_RG8 if variant == 'rg8' else hip.ENCODE_RGB8
     # composed frames: device -> pinned slot -> writer; a slot is reused once the writer no longer holds it
     stride = dib_stride(size[0]) if uncompressed else 3 * size[0]
     nslots = writer.in_flight_limit() + 3
@@ -299,15 +466,33 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         field = fslots[k].to(device, non_blocking=True)
         fevents[k] = torch.cuda.Event()
         fevents[k].record(stream)
-        viz = encoder.encode(field, width, height)
+        viz = encoder.encode(field, width, height) if external is None else None
         taa_frame = taa_simple_frame = None
         if taa:
             taa_frame = taa_flow.apply_taa(frame, flow_pixels=prev, alpha=0.1, use_flow=True, sequence_id='flow_taa')
             taa_simple_frame = taa_simple.apply_taa(frame, flow_pixels=None, alpha=0.1, use_flow=False,
                                                     sequence_id='simple_taa')
         prev = field
+        taa_ext = diff = None
+        if external is not None:
+            picture = external.get(i)
+            if picture is not None:
+                e = uploads % len(eslots)
+                uploads += 1
+                if eevents[e] is not None:
+                    eevents[e].synchronize()
+                np.copyto(eslots[e].numpy(), picture)
+                encoded = eslots[e].to(device, non_blocking=True)
+                eevents[e] = torch.cuda.Event()
+                eevents[e].record(stream)
+                ext_flow = hip.flow_decode(encoded, decode_mode, clamp_range)
+            taa_ext = taa_external.apply_taa(frame, flow_pixels=ext_flow, alpha=0.1, use_flow=True,
+                                             sequence_id='external_taa')
+            viz = encoder.encode(ext_flow, width, height)     # the flow tile shows the external flow, re-encoded
+            diff = hip.flow_diff_overlay(field, ext_flow)
         out = compose_device(frame, viz, taa_frame, taa_simple_frame, flow_only=flow_only, bgr=uncompressed,
-                             bottom_up=uncompressed, row_stride=stride)
+                             bottom_up=uncompressed, row_stride=stride, taa_external_frame=taa_ext,
+                             difference_overlay=diff)
         s = i % nslots
         writer.drain(keep=nslots - 2)        # the slot's previous frame is no longer in the writer's hands
         oslots[s].copy_(out, non_blocking=True)
@@ -331,9 +516,10 @@ def main(argv=None):
     rank, local_rank, world = vdist.init_distributed()
     log = print if rank == 0 else (lambda *a, **k: None)
 
-    for flag, on in (("--show-tiles", args.show_tiles), ("--flow-input", args.flow_input)):
-        if on:
-            log(f"note: {flag} concerns video composition / visualisation, which this build does not do; ignored")
+    if args.show_tiles:
+        log("note: --show-tiles concerns video composition / visualisation, which this build does not do; ignored")
+    if args.flow_input is not None:
+        check_flow_input(args)
     if not (args.input.startswith('synthetic:') or os.path.exists(args.input)):
         log(f"Error: Input video not found: {args.input}")
         return 1

@@ -9,6 +9,10 @@
 //
 // vfml_compose_frame: one thread per output dword of a row; each byte finds its tile, pixel and channel, so the buffer
 // handed to the AVI writer is the chunk payload itself (channel order, row order, padded row stride).
+//
+// vfml_flow_decode / vfml_flow_diff_overlay (the --flow-input comparison): one thread per pixel.  The decoder takes the
+// host decoders' float32 steps in their order; the overlay classifies |a - b| against the float32 thresholds and decides
+// the legend's squares from the pixel's coordinates in the same pass.
 #include "vfml_common.h"
 
 namespace {
@@ -158,10 +162,71 @@ __global__ void colorize_kernel(const float2* __restrict__ flow, int64_t n, cons
   }
 }
 
+// ---- external flow (--flow-input): decode and difference overlay -------------------------------------------------------
+// MotionVectorsRG8FlowEncoder.decode / MotionVectorsRGB8FlowEncoder.decode ('rgb+'), step by step in float32
+template <int MODE>
+__global__ void flow_decode_kernel(const unsigned char* __restrict__ enc, int64_t n, float clamp,
+                                   float2* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+    const float nr = div32((float)enc[3 * p], 255.0f), ng = div32((float)enc[3 * p + 1], 255.0f);
+    float2 f;
+    if constexpr (MODE == VFML_ENCODE_RG8) {
+      f.x = (nr * 2.0f) * clamp - clamp;
+      f.y = (ng * 2.0f) * clamp - clamp;
+    } else {
+      const float nb = div32((float)enc[3 * p + 2], 255.0f);
+      const float dx = nr * 2.0f - 1.0f, dy = ng * 2.0f - 1.0f;
+      const float xx = dx * dx, yy = dy * dy, bb = nb * nb;
+      const float mag = div32(1.0f, root32((xx + yy) + bb)) * clamp;
+      f.x = dx * mag;
+      f.y = dy * mag;
+    }
+    out[p] = f;
+  }
+}
+
+// radar colours of the difference classes, R | G << 8 | B << 16: green, yellow, orange, red, magenta
+__device__ __forceinline__ unsigned radar_colour(int k) {
+  return k == 0 ? 0x00ff00u : k == 1 ? 0x00ffffu : k == 2 ? 0x00a5ffu : k == 3 ? 0x0000ffu : 0xff00ffu;
+}
+
+__global__ void diff_overlay_kernel(const float2* __restrict__ fa, const float2* __restrict__ fb, int h, int w,
+                                    unsigned char* __restrict__ out) {
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)h * w;
+  const int y0 = h - 20;                                   // the legend's base line
+  for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+    const float2 a = fa[p], b = fb[p];
+    const float dx = a.x - b.x, dy = a.y - b.y;
+    const float xx = dx * dx, yy = dy * dy;
+    const float m = root32(xx + yy);
+    unsigned rgb = 0;                                      // NaN matches no class: black
+    if (m <= 0.1f) rgb = radar_colour(0);
+    else if (m <= 0.5f) rgb = radar_colour(1);
+    else if (m <= 1.0f) rgb = radar_colour(2);
+    else if (m <= 2.0f) rgb = radar_colour(3);
+    else if (m > 2.0f) rgb = radar_colour(4);
+    // legend square i: white (x-1, y0-13)..(x+13, y0+1), colour (x, y0-12)..(x+12, y0), x = 10 + 45 i, corners inclusive
+    const int y = (int)(p / w), x = (int)(p - (int64_t)y * w);
+    const int lx = x - 9;
+    if (lx >= 0 && y >= y0 - 13 && y <= y0 + 1) {
+      const int i = lx / 45, r = lx - 45 * i;
+      if (i < 5 && r <= 14) {
+        rgb = 0xffffffu;
+        if (r >= 1 && r <= 13 && y >= y0 - 12 && y <= y0) rgb = radar_colour(i);
+      }
+    }
+    out[3 * p] = (unsigned char)rgb;
+    out[3 * p + 1] = (unsigned char)(rgb >> 8);
+    out[3 * p + 2] = (unsigned char)(rgb >> 16);
+  }
+}
+
 // ---- frame composer ---------------------------------------------------------------------------------------------------
 struct ComposeArgs {
-  const void* tile[4];
-  int type[4];
+  const void* tile[6];
+  int type[6];
   int h, w;               // tile size
   int ow, oh;             // output frame in pixels
   int layout, bgr, bottom_up;
@@ -192,8 +257,8 @@ __device__ __forceinline__ unsigned char out_byte(const ComposeArgs& a, int y, i
   } else if (a.layout == VFML_COMPOSE_STACKED) {
     t = y >= a.h;
     sy = y - t * a.h;
-  } else {
-    const int tx = x >= a.w, tyy = y >= a.h;
+  } else {                                                 // GRID_2X2 and GRID_2X3: two tiles per tile row
+    const int tx = x >= a.w, tyy = (y >= a.h) + (y >= 2 * a.h);
     t = 2 * tyy + tx;
     sx = x - tx * a.w;
     sy = y - tyy * a.h;
@@ -244,16 +309,44 @@ extern "C" int vfml_flow_colorize(const float* flow, int h, int w, int mode, voi
   return vfml_check_launch("vfml_flow_colorize");
 }
 
+extern "C" int vfml_flow_decode(const unsigned char* encoded, int h, int w, int mode, float clamp, float* flow,
+                                void* stream) {
+  VFML_REQUIRE(encoded && flow && h > 0 && w > 0, "vfml_flow_decode: bad argument");
+  VFML_REQUIRE(mode == VFML_ENCODE_RG8 || mode == VFML_ENCODE_RGB8, "vfml_flow_decode: unknown mode %d", mode);
+  VFML_REQUIRE((reinterpret_cast<uintptr_t>(flow) & 7u) == 0, "vfml_flow_decode: flow must be 8-byte aligned");
+  const int64_t n = (int64_t)h * w;
+  float2* f2 = reinterpret_cast<float2*>(flow);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const dim3 block(256), grid(blocks_for(n, 256));
+  if (mode == VFML_ENCODE_RG8)
+    hipLaunchKernelGGL(flow_decode_kernel<VFML_ENCODE_RG8>, grid, block, 0, s, encoded, n, clamp, f2);
+  else
+    hipLaunchKernelGGL(flow_decode_kernel<VFML_ENCODE_RGB8>, grid, block, 0, s, encoded, n, clamp, f2);
+  return vfml_check_launch("vfml_flow_decode");
+}
+
+extern "C" int vfml_flow_diff_overlay(const float* flow_a, const float* flow_b, int h, int w, unsigned char* out,
+                                      void* stream) {
+  VFML_REQUIRE(flow_a && flow_b && out && h > 0 && w > 0, "vfml_flow_diff_overlay: bad argument");
+  VFML_REQUIRE(((reinterpret_cast<uintptr_t>(flow_a) | reinterpret_cast<uintptr_t>(flow_b)) & 7u) == 0,
+               "vfml_flow_diff_overlay: flows must be 8-byte aligned");
+  hipLaunchKernelGGL(diff_overlay_kernel, dim3(blocks_for((int64_t)h * w, 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const float2*>(flow_a),
+                     reinterpret_cast<const float2*>(flow_b), h, w, out);
+  return vfml_check_launch("vfml_flow_diff_overlay");
+}
+
 extern "C" int vfml_compose_frame(const void* const* tiles, const int* tile_types, int h, int w, int layout, int flags,
                                   int64_t row_stride, unsigned char* out, void* stream) {
   VFML_REQUIRE(tiles && tile_types && out && h > 0 && w > 0, "vfml_compose_frame: bad argument");
-  VFML_REQUIRE(layout == VFML_COMPOSE_SIDE_BY_SIDE || layout == VFML_COMPOSE_STACKED || layout == VFML_COMPOSE_GRID_2X2,
+  VFML_REQUIRE(layout == VFML_COMPOSE_SIDE_BY_SIDE || layout == VFML_COMPOSE_STACKED ||
+                   layout == VFML_COMPOSE_GRID_2X2 || layout == VFML_COMPOSE_GRID_2X3,
                "vfml_compose_frame: unknown layout %d", layout);
   VFML_REQUIRE((flags & ~(VFML_COMPOSE_BGR | VFML_COMPOSE_BOTTOM_UP)) == 0, "vfml_compose_frame: unknown flags 0x%x",
                flags);
   ComposeArgs a;
-  const int nt = layout == VFML_COMPOSE_GRID_2X2 ? 4 : 2;
-  for (int t = 0; t < 4; ++t) {
+  const int nt = layout == VFML_COMPOSE_GRID_2X3 ? 6 : (layout == VFML_COMPOSE_GRID_2X2 ? 4 : 2);
+  for (int t = 0; t < 6; ++t) {
     a.tile[t] = t < nt ? tiles[t] : nullptr;
     a.type[t] = t < nt ? tile_types[t] : VFML_PIX_U8;
     if (t < nt) {
@@ -264,7 +357,7 @@ extern "C" int vfml_compose_frame(const void* const* tiles, const int* tile_type
   }
   a.h = h; a.w = w;
   a.ow = layout == VFML_COMPOSE_STACKED ? w : 2 * w;
-  a.oh = layout == VFML_COMPOSE_SIDE_BY_SIDE ? h : 2 * h;
+  a.oh = layout == VFML_COMPOSE_SIDE_BY_SIDE ? h : (layout == VFML_COMPOSE_GRID_2X3 ? 3 * h : 2 * h);
   VFML_REQUIRE(row_stride >= 3 * (int64_t)a.ow && row_stride < ((int64_t)1 << 31),
                "vfml_compose_frame: row stride %lld below 3 * %d", (long long)row_stride, a.ow);
   VFML_REQUIRE(a.oh <= 65535, "vfml_compose_frame: output height %d above the grid's y limit", a.oh);

@@ -170,6 +170,8 @@ def lib():
                                     c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p,
                                     ctypes.c_int64, c_void_p, ctypes.c_size_t, c_void_p]
     L.vfml_flow_colorize.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.vfml_flow_decode.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p]
+    L.vfml_flow_diff_overlay.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vfml_compose_frame.argtypes = [POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int, c_int, c_int64, c_void_p,
                                      c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
@@ -187,7 +189,7 @@ EXPORTS = [
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
-    "vfml_flow_colorize", "vfml_compose_frame",
+    "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -764,15 +766,43 @@ def flow_colorize(flow, mode):
     return out
 
 
-COMPOSE_SIDE_BY_SIDE, COMPOSE_STACKED, COMPOSE_GRID_2X2 = 0, 1, 2
+def flow_decode(encoded, mode, clamp_range):
+    """Encoded motion vectors [H,W,3] uint8 (device tensor with contiguous rows: a whole picture or a row slice of an
+    uploaded frame) -> flow [H,W,2] float32 device tensor (vfml_flow_decode; ENCODE_RG8 or ENCODE_RGB8)."""
+    import numpy as np
+    e = _dev(encoded, torch.uint8)
+    if e.dim() != 3 or e.shape[2] != 3:
+        raise ValueError(f"flow_decode: [H,W,3] picture expected, got {tuple(e.shape)}")
+    h, w = e.shape[:2]
+    out = torch.empty((h, w, 2), dtype=torch.float32, device=e.device)
+    _check(lib().vfml_flow_decode(c_void_p(e.data_ptr()), h, w, mode, float(np.float32(clamp_range)), _ptr(out),
+                                  _stream()), "vfml_flow_decode")
+    return out
+
+
+def flow_diff_overlay(flow_a, flow_b):
+    """Two flows [H,W,2] float32 (device tensors) -> the radar picture of their difference with its legend squares,
+    [H,W,3] uint8 RGB device tensor (vfml_flow_diff_overlay)."""
+    a, b = _dev(flow_a.contiguous()), _dev(flow_b.contiguous())
+    if a.dim() != 3 or a.shape[2] != 2 or a.shape != b.shape:
+        raise ValueError(f"flow_diff_overlay: two [H,W,2] flows of one size expected, got {tuple(a.shape)} "
+                         f"{tuple(b.shape)}")
+    h, w = a.shape[:2]
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=a.device)
+    _check(lib().vfml_flow_diff_overlay(_ptr(a), _ptr(b), h, w, c_void_p(out.data_ptr()), _stream()),
+           "vfml_flow_diff_overlay")
+    return out
+
+
+COMPOSE_SIDE_BY_SIDE, COMPOSE_STACKED, COMPOSE_GRID_2X2, COMPOSE_GRID_2X3 = 0, 1, 2, 3
 COMPOSE_BGR, COMPOSE_BOTTOM_UP = 1, 2
 
 
 def compose_frame(tiles, layout, bgr=True, bottom_up=False, row_stride=None, out=None):
-    """One output frame (vfml_compose_frame): tiles = 2 (SIDE_BY_SIDE, STACKED) or 4 (GRID_2X2) device images [H,W,3],
+    """One output frame (vfml_compose_frame): tiles = 2 (SIDE_BY_SIDE, STACKED), 4 (GRID_2X2) or 6 (GRID_2X3) device images [H,W,3],
     uint8 or float32 / float64 TAA histories -> uint8 device buffer [rows, row_stride] (row_stride defaults to 3 x the
     output width).  `out`, when given, is a contiguous uint8 device tensor of at least rows x row_stride bytes."""
-    nt = 4 if layout == COMPOSE_GRID_2X2 else 2
+    nt = {COMPOSE_GRID_2X2: 4, COMPOSE_GRID_2X3: 6}.get(layout, 2)
     if len(tiles) != nt:
         raise ValueError(f"compose_frame: layout {layout} takes {nt} tiles, got {len(tiles)}")
     ts = [t.contiguous() for t in tiles]
@@ -782,7 +812,7 @@ def compose_frame(tiles, layout, bgr=True, bottom_up=False, row_stride=None, out
             raise ValueError(f"compose_frame: device [H,W,3] u8/f32/f64 tiles of one size expected, got "
                              f"{t.dtype} {tuple(t.shape)} on {t.device}")
     ow = w if layout == COMPOSE_STACKED else 2 * w
-    oh = h if layout == COMPOSE_SIDE_BY_SIDE else 2 * h
+    oh = h if layout == COMPOSE_SIDE_BY_SIDE else (3 * h if layout == COMPOSE_GRID_2X3 else 2 * h)
     stride = 3 * ow if row_stride is None else int(row_stride)
     if out is None:
         out = torch.empty((oh, stride), dtype=torch.uint8, device=ts[0].device)
