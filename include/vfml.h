@@ -474,6 +474,25 @@ enum { VFML_COMPOSE_BGR = 1, VFML_COMPOSE_BOTTOM_UP = 2 };
 int vfml_compose_frame(const void* const* tiles, const int* tile_types, int h, int w, int layout, int flags,
                        int64_t row_stride, unsigned char* out, void* stream);
 
+/* Turbulence map of a flow field (reference flow_visualizer.py: generate_turbulence_map :2997-3052): a heat map of the
+ * local standard deviation of the flow vectors, all on `stream`, no host synchronisation, no allocation.
+ * flow: [fh][fw][2] f32; when (fh, fw) != (h, w) it is first resized bilinearly to h x w with the taps of
+ * vfml_flow_quality_map and its x / y scaled by f32(w / fw) / f32(h / fh).  Then, per pixel:
+ *   four ksize x ksize box means (x, y, x*x, y*y; squares in f32), BORDER_REFLECT, each the f64 sum times
+ *   1.0 / ksize^2 rounded once to f32;  var = mean2 - mean * mean (f32, unfused);
+ *   tv = sqrt(max(0, var_x) + max(0, var_y)), correctly rounded.
+ * lo, hi = numpy.percentile(tv, 5 / 95) (method 'linear' on the f32 array as numpy 2 evaluates it, found by an exact
+ * radix selection on the device);  index = u8(clip((tv - lo) / (hi - lo), 0, 1) * 255) when hi - lo > 1e-6f, else 0;
+ * out_bgr: [h][w][3] u8 <- JET[index], B first.  The box filter, the resize and the JET table are this project's
+ * definitions of the OpenCV 4 algorithms, not pinned against cv2.
+ * ksize: odd, 1..63.  workspace: device, 256-byte aligned, the workspace_bytes function's count; not shared by calls
+ * that may run at once.  Optional outputs (null to skip): out_index [h][w] u8, out_tv [h][w] f32 (16-byte aligned),
+ * out_lohi [2] f32.  Non-finite vectors give an unspecified picture; every access stays in bounds.  SURVEY.md row 15. */
+size_t vfml_flow_turbulence_workspace_bytes(int h, int w);
+int vfml_flow_turbulence_map(const float* flow, int fh, int fw, int h, int w, int ksize, void* workspace,
+                             unsigned char* out_bgr, unsigned char* out_index, float* out_tv, float* out_lohi,
+                             void* stream);
+
 const char* vfml_last_error(void);
 int vfml_abi_version(void);
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -73,7 +73,7 @@ def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libvfml_hip.so (in-tree). Cross-compiles without a GPU."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "vfml_common.h"), os.path.join(CSRC, "conv_split_common.h"),
-            os.path.join(_HERE, "..", "..", "include", "vfml.h")]
+            os.path.join(CSRC, "jet_table.inc"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(
             os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -174,6 +174,10 @@ def lib():
     L.vfml_flow_diff_overlay.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vfml_compose_frame.argtypes = [POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int, c_int, c_int64, c_void_p,
                                      c_void_p]
+    L.vfml_flow_turbulence_workspace_bytes.argtypes = [c_int, c_int]
+    L.vfml_flow_turbulence_workspace_bytes.restype = ctypes.c_size_t
+    L.vfml_flow_turbulence_map.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -190,6 +194,7 @@ EXPORTS = [
     "vfml_ptr_table_set", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
+    "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -836,6 +841,44 @@ def flow_quality_map(frame1, frame2, flow, threshold):
     _check(lib().vfml_flow_quality_map(c_void_p(f1.data_ptr()), c_void_p(f2.data_ptr()), _ptr(fl), fl.shape[0], fl.shape[1],
                                        h, w, float(threshold), c_void_p(out.data_ptr()), _stream()), "vfml_flow_quality_map")
     return out
+
+
+_TURBULENCE_WS = {}
+
+
+def flow_turbulence_map(flow, height, width, kernel_size=25, want=()):
+    """flow [fh,fw,2] f32 device tensor -> the turbulence map of a height x width frame, uint8 [height,width,3] in cv2's
+    channel order (B first) on the device (vfml_flow_turbulence_map: stream-ordered, no host synchronisation).
+    want: names of further results, returned after the picture in the order given - "index" (uint8 [H,W], the JET entry
+    of each pixel), "tv" (float32 [H,W], the local deviation), "lohi" (float32 [2], its 5th and 95th percentile).
+    The workspace is kept per device, picture size and stream."""
+    f = _dev(flow.contiguous())
+    if f.dim() != 3 or f.shape[2] != 2 or f.shape[0] < 1 or f.shape[1] < 1:
+        raise ValueError(f"flow_turbulence_map: [fh,fw,2] flow expected, got {tuple(f.shape)}")
+    h, w, k = int(height), int(width), int(kernel_size)
+    if h < 1 or w < 1:
+        raise ValueError(f"flow_turbulence_map: frame {h}x{w}")
+    if k % 2 == 0 or not 1 <= k <= 63:
+        raise ValueError(f"flow_turbulence_map: kernel_size {k} is not an odd number in 1..63")
+    extra = {"index": ((h, w), torch.uint8), "tv": ((h, w), torch.float32), "lohi": ((2,), torch.float32)}
+    for name in want:
+        if name not in extra:
+            raise ValueError(f"flow_turbulence_map: want={name!r}; one of {sorted(extra)}")
+    L = lib()
+    key = (f.device.index, h, w, torch.cuda.current_stream().cuda_stream)
+    ws = _TURBULENCE_WS.get(key)
+    if ws is None:
+        ws = _TURBULENCE_WS[key] = torch.empty(L.vfml_flow_turbulence_workspace_bytes(h, w), dtype=torch.uint8,
+                                               device=f.device)
+    out = torch.empty((h, w, 3), dtype=torch.uint8, device=f.device)
+    more = {name: torch.empty(extra[name][0], dtype=extra[name][1], device=f.device) for name in want}
+
+    def opt(name):
+        return c_void_p(more[name].data_ptr()) if name in more else None
+    _check(L.vfml_flow_turbulence_map(_ptr(f), f.shape[0], f.shape[1], h, w, k, c_void_p(ws.data_ptr()),
+                                      c_void_p(out.data_ptr()), opt("index"), opt("tv"), opt("lohi"), _stream()),
+           "vfml_flow_turbulence_map")
+    return (out, *[more[name] for name in want]) if want else out
 
 
 def convex_upsample(coords1, coords_off, ch, mask, mask_off, ld_mask, h, w, out, out_off=0):
