@@ -283,6 +283,24 @@ int vfml_corr_lookup_indirect_bidir(const float* const* table, const int32_t* hl
                                     int vol_tile, void* stream);
 int vfml_ptr_table_set(void* table, const void* const* ptrs, int n, void* stream);
 
+/* Window set-up of the recurrent state, one launch: state is [ncentres * rows][ld_state] floats, centre frame c owns rows
+ * c * rows .. (c + 1) * rows - 1.  `cells` is a DEVICE table of three 8-byte cells per centre frame, read when the kernel
+ * runs (vfml_ptr_table_set writes them; a captured launch follows what they hold at replay):
+ *   cells[3c]     context map of the frame, [rows][ld_ctx] floats, or 0: its first `cols` columns are copied to columns
+ *                 h_off .. h_off + cols - 1 of the frame's state rows (h = the tanh half of the context map);
+ *   cells[3c + 1] the frame's slot, [rows][cols] floats, or 0;
+ *   cells[3c + 2] VFML_SEED_LOAD: the slot is copied to columns mf_off .. mf_off + cols - 1 of the frame's state rows,
+ *                 VFML_SEED_STORE: those columns are copied to the slot, VFML_SEED_NONE: neither.
+ * Plain copies of 16-byte quads, whatever activation format the rows hold: every pointer 16-byte aligned, cols, ld_state,
+ * ld_ctx, h_off and mf_off multiples of 4, the two column blocks disjoint.  Slots named by two centres of one launch must
+ * not be loaded by one and stored by the other.  Replaces the per-centre strided copies that seeded h, and carries a
+ * frame's first-iteration motion features from the window that computed them to the windows that reuse them. */
+#define VFML_SEED_NONE 0
+#define VFML_SEED_LOAD 1
+#define VFML_SEED_STORE 2
+int vfml_window_seed(const void* cells, int ncentres, int rows, int cols, float* state, int ld_state, int h_off, int mf_off,
+                     int ld_ctx, void* stream);
+
 /* The 7x7 convolution over the 4-channel flow map (motion encoder, convf1) as a 7x1 convolution over 32 channels: this pass
  * writes, per pixel, the seven horizontal taps' flow quads (zeros outside the image row) as one split-row block of 32
  * channels - channel kx*4 + c = flow[y][x + kx - 3][c], channels 28..31 zero - 12 MB at 1080p/8; the vertical taps are then

@@ -482,6 +482,27 @@ __global__ void ptr_table_kernel(const PtrTable t, int n, const void** dst) {
   if ((int)threadIdx.x < n) dst[threadIdx.x] = t.p[threadIdx.x];
 }
 
+// Window set-up of the recurrent state (vfml_window_seed): blockIdx.y = centre frame, whose three cells name its context
+// map, its iteration-zero slot and what to do with the slot.  Quads of four floats, 16-byte loads and stores; the cells
+// are read when the kernel runs, so a captured launch follows whatever they hold at replay.
+__global__ void window_seed_kernel(const int64_t* __restrict__ cells, int rows, int quads, float* __restrict__ state,
+                                   int ld_state, int h_off, int mf_off, int ld_ctx) {
+  const int c = blockIdx.y;
+  const float* ctx = reinterpret_cast<const float*>(cells[3 * c]);
+  float* slot = reinterpret_cast<float*>(cells[3 * c + 1]);
+  const int64_t mode = slot ? cells[3 * c + 2] : 0;
+  const int total = rows * quads;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const int r = i / quads, k = 4 * (i - r * quads);
+    float* srow = state + ((int64_t)c * rows + r) * ld_state;
+    if (ctx) *reinterpret_cast<f32x4*>(srow + h_off + k) = *reinterpret_cast<const f32x4*>(ctx + (int64_t)r * ld_ctx + k);
+    if (mode == VFML_SEED_LOAD)
+      *reinterpret_cast<f32x4*>(srow + mf_off + k) = *reinterpret_cast<const f32x4*>(slot + (int64_t)r * 4 * quads + k);
+    else if (mode == VFML_SEED_STORE)
+      *reinterpret_cast<f32x4*>(slot + (int64_t)r * 4 * quads + k) = *reinterpret_cast<const f32x4*>(srow + mf_off + k);
+  }
+}
+
 }  // namespace
 
 extern "C" int vfml_ptr_table_set(void* table, const void* const* ptrs, int n, void* stream) {
@@ -491,6 +512,24 @@ extern "C" int vfml_ptr_table_set(void* table, const void* const* ptrs, int n, v
   hipLaunchKernelGGL(ptr_table_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), t, n,
                      reinterpret_cast<const void**>(table));
   return vfml_check_launch("vfml_ptr_table_set");
+}
+
+extern "C" int vfml_window_seed(const void* cells, int ncentres, int rows, int cols, float* state, int ld_state, int h_off,
+                                int mf_off, int ld_ctx, void* stream) {
+  VFML_REQUIRE(cells && (reinterpret_cast<uintptr_t>(cells) & 7u) == 0, "vfml_window_seed: null / misaligned cells");
+  VFML_REQUIRE(ncentres >= 1 && 3 * ncentres <= MAX_TABLE, "vfml_window_seed: ncentres=%d out of [1,%d]", ncentres, MAX_TABLE / 3);
+  VFML_REQUIRE(state && vfml_aligned16(state), "vfml_window_seed: null / misaligned state");
+  VFML_REQUIRE(rows >= 1 && cols >= 4 && cols % 4 == 0 && (int64_t)rows * (cols / 4) <= (1 << 30),
+               "vfml_window_seed: rows >= 1, cols a multiple of 4, rows * cols / 4 <= 2^30");
+  VFML_REQUIRE(ld_state % 4 == 0 && h_off >= 0 && mf_off >= 0 && h_off % 4 == 0 && mf_off % 4 == 0 && h_off + cols <= ld_state &&
+               mf_off + cols <= ld_state && (h_off + cols <= mf_off || mf_off + cols <= h_off),
+               "vfml_window_seed: the two column blocks lie apart inside a state row, at multiples of 4 floats");
+  VFML_REQUIRE(ld_ctx >= cols && ld_ctx % 4 == 0, "vfml_window_seed: ld_ctx=%d (>= cols, a multiple of 4)", ld_ctx);
+  const int quads = cols / 4;
+  hipLaunchKernelGGL(window_seed_kernel, dim3(grid_for((int64_t)rows * quads, 256), ncentres), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const int64_t*>(cells), rows, quads, state,
+                     ld_state, h_off, mf_off, ld_ctx);
+  return vfml_check_launch("vfml_window_seed");
 }
 
 static int corr_lookup_impl(const float* const* pyr, const float* const* table, const int32_t* hl, const int32_t* wl,

@@ -147,6 +147,7 @@ def lib():
                                                   c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                   c_int, c_int, c_int, c_int, c_void_p]
     L.vfml_ptr_table_set.argtypes = [c_void_p, POINTER(c_void_p), c_int, c_void_p]
+    L.vfml_window_seed.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     L.vfml_tapsum3x3_update.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p,
                                         c_int, c_void_p, c_int, c_int, c_void_p]
     L.vfml_conv3x3_c64.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,
@@ -191,7 +192,7 @@ EXPORTS = [
     "vfml_conv2d", "vfml_conv2d_split", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
-    "vfml_ptr_table_set", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
+    "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map",
@@ -566,8 +567,21 @@ def ptr_table_set(table, tensors):
     n = len(tensors)
     if not (table.is_cuda and table.dtype == torch.int64 and table.numel() >= n):
         raise ValueError("ptr_table_set: table must be an int64 device tensor with room for the pointers")
-    ptrs = (c_void_p * n)(*[t.data_ptr() for t in tensors])
+    ptrs = (c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in tensors])     # (an int: the cell's value itself)
     _check(lib().vfml_ptr_table_set(c_void_p(table.data_ptr()), ptrs, n, _stream()), "vfml_ptr_table_set")
+
+
+SEED_NONE, SEED_LOAD, SEED_STORE = 0, 1, 2
+
+
+def window_seed(cells, ncentres, rows, cols, state, ld_state, h_off, mf_off, ld_ctx):
+    """Window set-up of the recurrent state as one launch (include/vfml.h vfml_window_seed): per centre frame the cells
+    (an int64 device tensor, three per frame: context map, slot, SEED_*; ptr_table_set writes them) name what is copied into
+    the h columns, and into or out of the mf columns, of the frame's state rows."""
+    if not (cells.is_cuda and cells.dtype == torch.int64 and cells.numel() >= 3 * ncentres):
+        raise ValueError("window_seed: cells must be an int64 device tensor, three per centre frame")
+    _check(lib().vfml_window_seed(c_void_p(cells.data_ptr()), ncentres, rows, cols, _ptr(_dev(state)), ld_state, h_off, mf_off,
+                                  ld_ctx, _stream()), "vfml_window_seed")
 
 
 def corr_lookup(pyrs, hl, wl, ld, radius, q_per_map, coords, coords_off, ld_coords, out, out_off, ld_out,

@@ -57,6 +57,78 @@ class _Holder(nn.Module):
         return self._modules[name]
 
 
+class Iter0Ring:
+    """Bookkeeping of the iteration-zero store (MOFNetHIP._iter0_store): which slot of a ring holds which centre frame's
+    first-iteration motion features.  No tensors here - slot numbers, keys and the cache dictionary the entries live in
+    (the engine's `_feat_cache`, kind "m": whatever clears that cache forgets the entries, and a slot handed out again
+    takes its old owner's entry along).
+
+    At iteration 0 the flow is zero, so a centre frame's motion features depend on its two correlation pyramids alone -
+    on the frame AND its two neighbours in the window.  The key is therefore the cache keys of all three: a window clamped
+    at the start of a clip gives frame 0 the neighbours (0, 0), the next one (0, 1) - different entries."""
+    _serials = 0
+
+    def __init__(self, slots, cache):
+        Iter0Ring._serials += 1
+        self.R, self.cache, self.next, self.owner, self.serial = slots, cache, 0, [None] * slots, Iter0Ring._serials
+
+    @staticmethod
+    def entry_key(keys, j, tail=()):
+        """Key of frame j (1 <= j <= len(keys) - 2) of a window whose frames have the cache keys `keys`."""
+        return ("m", keys[j - 1], keys[j], keys[j + 1]) + tuple(tail)
+
+    def lookup(self, ek):
+        ent = self.cache.get(ek)
+        if ent is not None and ent[1] == self.serial and self.owner[ent[0]] == ek:
+            return ent[0]
+        return None
+
+    def _take(self, ek, busy):
+        for _ in range(self.R):
+            s = self.next
+            self.next = (s + 1) % self.R
+            if s not in busy:
+                break
+        else:
+            raise RuntimeError("iteration-zero store: every slot is in use by the current window")
+        if self.owner[s] is not None:
+            self.cache.pop(self.owner[s], None)
+        self.owner[s] = ek
+        self.cache[ek] = (s, self.serial)
+        return s
+
+    def forget(self, eks):
+        for ek in eks:
+            s = self.lookup(ek)
+            if s is not None:
+                self.owner[s] = None
+                del self.cache[ek]
+
+    def plan(self, keys, tail=()):
+        """A window's slots: (warm, [(slot, mode)] per centre frame, keys of the entries this window fills).
+        warm: every centre but the newest (the last) has an entry - those are loaded (hip.SEED_LOAD) and only the newest is
+        computed, and stored unless it has an entry already.  Else every centre is computed and those without an entry are
+        stored (hip.SEED_STORE); a key that occurs twice in a window is stored once."""
+        M = len(keys) - 2
+        if M + 1 > self.R:
+            raise ValueError(f"iteration-zero store: {self.R} slots cannot serve {M} centre frames")
+        eks = [self.entry_key(keys, j, tail) for j in range(1, M + 1)]
+        found = [self.lookup(ek) for ek in eks]
+        warm = M >= 2 and all(s is not None for s in found[:-1])
+        busy = {s for s in found if s is not None}
+        out, new = [], []
+        for i, ek in enumerate(eks):
+            s = self.lookup(ek)           # (again: an earlier centre of this window may just have taken a slot for this key)
+            if s is not None:
+                out.append((s, hip.SEED_LOAD if warm and i < M - 1 else hip.SEED_NONE))
+            else:
+                s = self._take(ek, busy)
+                busy.add(s)
+                new.append(ek)
+                out.append((s, hip.SEED_STORE))
+        return warm, out, new
+
+
 class MOFNetHIP(_Holder):
     def __init__(self, cfg):
         super().__init__()
@@ -87,6 +159,8 @@ class MOFNetHIP(_Holder):
         self._pre_body = None          # event: the last field's inputs are ready, its iterations not yet queued
         import collections
         self._feat_cache = collections.OrderedDict()
+        self.iter0_stats = {"warm": 0, "cold": 0}       # windows that reused / filled the iteration-zero store
+        self.iter0_last = None                          # (warm, slots of the centre frames) of the last such window
 
     # ------------------------------------------------------------------ weights
     def _param(self, name):
@@ -304,6 +378,7 @@ class MOFNetHIP(_Holder):
         self._ws.clear()
         self._feat_cache.clear()
         self._ctx_store = None
+        self._it0_store = None
 
     # ------------------------------------------------------------------ per-frame context parts of the gate convolutions
     # The context part of the four GRU gate convolutions is computed once per frame and ADDED by the gate convolutions of
@@ -348,6 +423,30 @@ class MOFNetHIP(_Holder):
             self._feat_cache.pop(old, None)
         st["owner"][s] = cache_key
         return s
+
+    # ------------------------------------------------------------------ per-frame motion features of iteration 0
+    # At iteration 0 the flow is zero and the lookups, convc1, convc2, the flow half and encoder.conv act on every centre
+    # frame by itself: the `mf` columns of the state after them depend on the frame and its two neighbours only, and a frame
+    # is a centre of M consecutive windows of a sliding job.  Each centre's rows ([cells][128] floats in the update block's
+    # activation format, 16.6 MB at 1080p) are kept in a ring of slots (Iter0Ring); a window whose older centres all have
+    # theirs runs those five launches of iteration 0 on its newest centre alone ("warm").  The captured launch that moves the
+    # rows (vfml_window_seed) reaches the slots through device cells, so one graph serves every window.
+    # Eight slots: a sliding job takes one per field and reads the two taken before it.  Jobs that interleave more streams
+    # of windows than that (the six tiles of a 4K frame walked frame by frame) find their entries evicted and run cold - as
+    # before, plus the 25 us store.
+    ITER0_RING = 8
+    iter0_store = True       # False: every window computes iteration 0 for all its centres (tests, A/B runs)
+
+    def _iter0_store(self, dev, Pn, M):
+        st = getattr(self, "_it0_store", None)
+        if st is None or st["key"] != (str(dev), Pn) or st["ring"].R < M + 1:
+            self._join_prefetch()
+            for k in [k for k in self._feat_cache if k[0] == "m"]:     # (entries of another store)
+                del self._feat_cache[k]
+            R = max(self.ITER0_RING, M + 1)
+            st = self._it0_store = {"key": (str(dev), Pn), "ring": Iter0Ring(R, self._feat_cache),
+                                    "S": torch.empty(R * Pn * 128, device=dev)}
+        return st
 
     # ------------------------------------------------------------------ graph replay of the iteration body
     GRAPHS_KEPT = 8
@@ -846,9 +945,21 @@ class MOFNetHIP(_Holder):
             G = self._buf("gru_state", MP * GLD, dev)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
-            Gv = G.view(MP, GLD)
-            for c in range(1, N - 1):       # h = tanh half of the context map (the relu half reaches the gates as their addends)
-                Gv[(c - 1) * Pn:c * Pn, HH:HH + 128].copy_(ctx[c][0].view(Pn, 256)[:, :128])
+            # h = tanh half of the context map (the relu half reaches the gates as their addends), and the `mf` columns of the
+            # centres whose iteration 0 an earlier window ran: one launch inside the body (vfml_window_seed), told what to copy
+            # by three device cells per centre.  The store applies where iteration 0 covers every centre of a keyed window.
+            it0 = None
+            if (self.iter0_store and keys is not None and self._split() and not self.tri_frame and M >= 2
+                    and cfg.decoder_depth >= 1 and not (pick_only and cfg.decoder_depth + 1 < M)):
+                it0 = self._iter0_store(dev, Pn, M)
+                warm, seeds, it0_new = it0["ring"].plan(keys, tail=(R,))
+                self.iter0_stats["warm" if warm else "cold"] += 1
+                self.iter0_last = (warm, [s for s, _ in seeds])
+            else:
+                warm, seeds, it0_new = False, [(None, hip.SEED_NONE)] * M, []
+            seed_cells = self._buf("seed_cells", 64, dev, torch.int64)
+            hip.ptr_table_set(seed_cells, [v for i, (s, mode) in enumerate(seeds) for v in
+                                           (ctx[i + 1][0], it0["S"][s * Pn * 128:] if s is not None else 0, mode)])
             # the gates' context parts: the centre frames' slots, consecutive in a sliding job (through the mirror when the ring
             # wraps) - else gathered into the store's spare slots
             st = self._ctx_store
@@ -928,24 +1039,29 @@ class MOFNetHIP(_Holder):
                     # nothing of the correlation half (lookups -> convc1 -> convc2 -> channels 0..191): on a second stream
                     # its small MFMA-bound convolutions run BESIDE the HBM-bound lookups (a fork / join of two events; inside
                     # a captured graph, two branches).  Same kernels on the same inputs: bit-identical fields.
-                    def flow_half(nm=nm):
+                    # Iteration 0 of a warm window: the per-frame launches (lookups, motion encoder up to encoder.conv) run on
+                    # the newest centre alone - ne frames from row r0 on - and the seed pass brings the other centres' rows.
+                    ne, r0 = (1, (M - 1) * Pn) if warm and it == 0 else (nm, 0)
+
+                    def flow_half(ne=ne, r0=r0):
                         wgt, b = P[f"{ub}.encoder.convf1"]
                         wgt2, b2 = P[f"{ub}.encoder.convf2"]
                         if (fuse and self._rows7 and mf(f"{ub}.encoder.convf1") == 1 and mf(f"{ub}.encoder.convf2") == 1
                                 and getattr(wgt2, "order", None) == hip.KORDER_CBLOCK64 and wgt.kp == 224 and wgt2.kp == 1152):
                             # both layers in one launch, the 128-channel map between them in LDS (vfml_flow_half; same bits)
-                            hip.flow_half(flow4, nm, h, w, wgt, b, wgt2, b2, cf, 256, out_off=192)
+                            hip.flow_half(flow4[r0 * 4:], ne, h, w, wgt, b, wgt2, b2, cf, 256, out_off=r0 * 256 + 192)
                             return
                         if self._rows7:
-                            hip.flow_rows7(flow4, nm, h, w, frows)
-                            hip.conv2d(frows, 32, 32, nm, h, w, wgt, b, 128, 7, 1, f1, 128, pad_h=3, epilogue=hip.EPI_RELU,
-                                       in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
+                            hip.flow_rows7(flow4[r0 * 4:], ne, h, w, frows[r0 * 32:])
+                            hip.conv2d(frows, 32, 32, ne, h, w, wgt, b, 128, 7, 1, f1, 128, pad_h=3, epilogue=hip.EPI_RELU,
+                                       in0_off=r0 * 32, out_off=r0 * 128, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
                         else:
-                            hip.conv2d(flow4, 4, 4, nm, h, w, wgt, b, 128, 7, 7, f1, 128, pad_h=3, pad_w=3, epilogue=hip.EPI_RELU,
-                                       out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
+                            hip.conv2d(flow4, 4, 4, ne, h, w, wgt, b, 128, 7, 7, f1, 128, pad_h=3, pad_w=3, epilogue=hip.EPI_RELU,
+                                       in0_off=r0 * 4, out_off=r0 * 128, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
                         wgt, b = P[f"{ub}.encoder.convf2"]
-                        hip.conv2d(f1, 128, 128, nm, h, w, wgt, b, 64, 3, 3, cf, 256, out_off=192, pad_h=1, pad_w=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf2"))
+                        hip.conv2d(f1, 128, 128, ne, h, w, wgt, b, 64, 3, 3, cf, 256, in0_off=r0 * 128, out_off=r0 * 256 + 192,
+                                   pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF,
+                                   mfma=mf(f"{ub}.encoder.convf2"))
 
                     join = None
                     if branch is not None:
@@ -957,28 +1073,34 @@ class MOFNetHIP(_Holder):
                             join = torch.cuda.Event()
                             join.record()
                     # K5
+                    # (the tables from the first looked-up centre's pyramids on: the second direction's lie M maps behind still)
+                    t0 = r0 // Pn * L
                     if bidir:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF, table=tab_fb,
-                                        nmaps=nm, vol_fmt=VF, vol_tile=TILE, bidir=(2, cor_p, M))
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4, 4, corr, r0 * 2 * cor_p, 2 * cor_p, out_fmt=AF,
+                                        table=tab_fb[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE, bidir=(2, cor_p, M))
                     else:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF,
-                                        table=tab_f, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 2, 4, corr, cor_p, 2 * cor_p, out_fmt=AF,
-                                        table=tab_b, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4, 4, corr, r0 * 2 * cor_p, 2 * cor_p, out_fmt=AF,
+                                        table=tab_f[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE)
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4 + 2, 4, corr, r0 * 2 * cor_p + cor_p, 2 * cor_p,
+                                        out_fmt=AF, table=tab_b[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE)
                     # motion encoder
                     wgt, b = P[f"{ub}.encoder.convc1"]
-                    hip.conv2d(corr, 2 * cor_p, 2 * cor_p, nm, h, w, wgt, b, 256, 1, 1, c1, 256, epilogue=hip.EPI_RELU,
-                               in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc1"))
+                    hip.conv2d(corr, 2 * cor_p, 2 * cor_p, ne, h, w, wgt, b, 256, 1, 1, c1, 256, epilogue=hip.EPI_RELU,
+                               in0_off=r0 * 2 * cor_p, out_off=r0 * 256, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc1"))
                     wgt, b = P[f"{ub}.encoder.convc2"]
-                    hip.conv2d(c1, 256, 256, nm, h, w, wgt, b, 192, 3, 3, cf, 256, pad_h=1, pad_w=1, epilogue=hip.EPI_RELU,
-                               in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc2"))
+                    hip.conv2d(c1, 256, 256, ne, h, w, wgt, b, 192, 3, 3, cf, 256, in0_off=r0 * 256, out_off=r0 * 256,
+                               pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc2"))
                     if join is None:
                         flow_half()
                     else:
                         torch.cuda.current_stream(dev).wait_event(join)
                     wgt, b = P[f"{ub}.encoder.conv"]
-                    hip.conv2d(cf, 256, 256, nm, h, w, wgt, b, 124, 3, 3, G, GLD, out_off=MF, pad_h=1, pad_w=1,
-                               epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.conv"))
+                    hip.conv2d(cf, 256, 256, ne, h, w, wgt, b, 124, 3, 3, G, GLD, in0_off=r0 * 256, out_off=r0 * GLD + MF,
+                               pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.conv"))
+                    if it == 0:
+                        # h of every centre from its context map; mf rows (with the zero flow in channels 124..127) out of the
+                        # older centres' slots and into the new ones
+                        hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
                     # temporal stack fusion: 3x1 conv along the frame axis of the motion features
                     wgt, b = P[f"{ub}.tprop"]
                     if self.tri_frame:     # every centre frame is its own problem: its neighbours are the zero padding
@@ -1038,6 +1160,8 @@ class MOFNetHIP(_Holder):
                     hip.coords_update(coords1, delta, ng, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD,
                                       flow_b_off=MF + 124, fmt_b=AF)
 
+                if cfg.decoder_depth == 0:       # (no iteration ran the window set-up: h for the mask head)
+                    hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
                 # mask head on the final hidden state, then K8 for every flow of the output tensor (pick_only: of
                 # the first centre frame, and its backward flow alone)
                 wgt, b = P[f"{ub}.mask.0"]
@@ -1055,10 +1179,15 @@ class MOFNetHIP(_Holder):
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), vol16,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"))
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), warm)
             self._pre_body = torch.cuda.Event()
             self._pre_body.record(torch.cuda.current_stream(dev))      # (what a prefetch of the next window waits for)
-            self._run_body(body, gkey, dev)
+            try:
+                self._run_body(body, gkey, dev)
+            except BaseException:
+                if it0_new:      # (slots promised to this window's centres that may not have been filled)
+                    it0["ring"].forget(it0_new)
+                raise
             up = up_fixed.clone().view(nflows, H, W, 2)          # the caller owns its field; the fixed buffer is reused
             if pick_only and not self.tri_frame:
                 return up.permute(0, 3, 1, 2).unsqueeze(0), None        # [1, 1, 2, H, W]: flow M of the full output
