@@ -8,7 +8,7 @@ pytestmark = pytest.mark.gpu
 EPE_TOL = 1e-3  # px, mean over pixels of ||flow_engine - flow_oracle||_2
 
 
-def _pair(seed=0, **over):
+def _pair(seed=0, drift=0, **over):
     from oracle import mof_oracle as mo
     from vfml import build_network, get_cfg
     from vfml.weights import seeded_state_dict
@@ -17,6 +17,9 @@ def _pair(seed=0, **over):
         setattr(cfg, k, v)
         setattr(ocfg, k, v)
     sd = seeded_state_dict(cfg, seed)
+    if drift:
+        from tests_support import drift_state_dict
+        sd = drift_state_dict(sd, drift)
     net = build_network(cfg)
     net.load_state_dict(sd)
     net.cuda().eval()
@@ -80,15 +83,13 @@ def test_uint8_frames_equal_float_frames(gpu):
     assert torch.equal(a, b)
 
 
-def test_sliding_window_feature_cache_is_exact(gpu):
-    """Per-frame encoder outputs reused across overlapping windows (frame_keys) give bit-identical
-    fields to encoding every window from scratch; so does the resident-clip processor path."""
+def _sliding_window_feature_cache_is_exact(drift):
     import contextlib
     import io
     import numpy as np
     from processing.videoflow_processor import VideoFlowProcessor
     from vfml.synth import synthetic_clip
-    net, _ = _pair()
+    net, _ = _pair(drift=drift)
     frames = synthetic_clip(8, 128, 160)
     clip = torch.from_numpy(np.stack(frames)).cuda()
     with contextlib.redirect_stdout(io.StringIO()):
@@ -107,6 +108,20 @@ def test_sliding_window_feature_cache_is_exact(gpu):
     t1 = proc.compute_optical_flow_resident(clip, 3, tile=tile).clone()
     t2, _ = net.forward_u8(clip[proc.window_indices(8, 3)][:, 0:128, 32:160].contiguous())
     assert torch.equal(t1, t2[0, 3].permute(1, 2, 0))
+    return float(t1.abs().max())
+
+
+def test_sliding_window_feature_cache_is_exact(gpu):
+    """Per-frame encoder outputs reused across overlapping windows (frame_keys) give bit-identical
+    fields to encoding every window from scratch; so does the resident-clip processor path."""
+    _sliding_window_feature_cache_is_exact(0)
+
+
+def test_sliding_window_feature_cache_is_exact_at_large_flow(gpu):
+    """The same with flows of about 12 cells (tests_support.drift_state_dict, c = 1): the cached encoder outputs and the
+    stored first-iteration motion features are the recomputed ones bit for bit when the lookups leave the volume too."""
+    top = _sliding_window_feature_cache_is_exact(1)
+    assert top > 8 * 8.0, top          # px: the drift did reach the field (12 iterations x 1 cell, less the network's own)
 
 
 def test_context_store_ring_wraps_and_falls_back(gpu, monkeypatch):

@@ -11,6 +11,12 @@ The mixed plan rounds on purpose, so it is compared with an oracle of the plan (
 K = 8 times N_plan, the plan oracle's float32-against-float64 noise (which contains the f16 roundings that flip when the
 rounded value moves by a float32 ulp).
 
+The seeded weights' own flow stays within about one cell.  The `large_flow` cases add a constant drift to the flow head's
+bias (tests_support.drift_state_dict) in the oracle and in the engine alike, so the same comparison runs at flows of about
+12, 24 and 96 cells - lookups that leave the volume, the plain-f16 flow staging of the mixed plan, coordinates and the convex
+upsampler on large values - under the same K: K comes from operand widths, and N, computed for these very weights, grows with
+the flow on its own.
+
 Measured ratios engine / N: DESIGN.md, "Elementwise parity".  Every test prints its line (`PARITY|...`) before it asserts."""
 import time
 
@@ -69,9 +75,11 @@ def _run_engine(net, feed, entry):
     return got.cpu(), ts.engine_low(low.cpu())
 
 
-def _check(case, precision, seed=0, plan=None, corr_volume="f32"):
+def _check(case, precision, seed=0, plan=None, corr_volume="f32", drift=None):
     cid, kind, T, H, W, depth, entry = case
     sd = _state(seed)
+    if drift is not None:        # the same drifted weights for the oracle pair and for the engine
+        sd = ts.drift_state_dict(sd, drift)
     feed, x = _input(kind, T, H, W)
     ocfg = ts.oracle_cfg(decoder_depth=depth)
     t0 = time.time()
@@ -91,7 +99,7 @@ def _check(case, precision, seed=0, plan=None, corr_volume="f32"):
     assert torch.isfinite(got).all() and torch.isfinite(low).all()
     E, El = ts.error_stats(got, ref), ts.low_stats(low, ref_low)
     K = ts.K_OF[precision]
-    tag = f"{cid}|seed{seed}|{precision}"
+    tag = f"{cid}|seed{seed}|{precision}" + ("" if drift is None else f"|drift{drift:g}")
     for name, e, n in (("full", E, N), ("low", El, Nl)):
         print(f"PARITY|{tag}|{name}|N " + " ".join(f"{n[k]:.2e}" for k in ts.STAT_KEYS) + "|engine " +
               " ".join(f"{e[k]:.2e}" for k in ts.STAT_KEYS) + "|ratio " +
@@ -105,6 +113,31 @@ def _check(case, precision, seed=0, plan=None, corr_volume="f32"):
 @pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
 def test_field_within_k_times_the_oracles_own_noise(gpu, case, precision):
     _check(case, precision)
+
+
+# Large flow: tests_support.drift_state_dict adds c cells per iteration to the flow head's bias, so after 12 iterations
+# the 1/8-resolution flows reach about 12 c cells (the seeded weights alone: about one).  (T, H, W, c); at c = 8 every
+# lookup falls outside its volume and the correlation features are exactly zero.
+DRIFT = [(3, 128, 192, 1), (3, 128, 192, 2), (4, 136, 160, 1), (4, 136, 160, 2), (3, 128, 192, 8)]
+DRIFT_IDS = [f"T{T}-{H}x{W}-drift{c}" for T, H, W, c in DRIFT]
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+@pytest.mark.parametrize("T,H,W,c", DRIFT, ids=DRIFT_IDS)
+def test_large_flow_field_within_k_times_the_oracles_own_noise(gpu, T, H, W, c, precision):
+    """The same K as at small flow: K comes from operand widths, and N, computed for these weights, grows with the flow."""
+    _check((f"randf-T{T}-{H}x{W}", "randf", T, H, W, 12, "forward"), precision, drift=c)
+
+
+@pytest.mark.parametrize("T,H,W,c,seed", [d + (0,) for d in DRIFT] + [(5, 128, 192, 1, 1)],
+                         ids=[i + "-seed0" for i in DRIFT_IDS] + ["T5-128x192-drift1-seed1"])
+def test_large_flow_mixed_plan_field_within_k_times_the_plan_oracles_noise(gpu, T, H, W, c, seed):
+    """The shipped plan against its own oracle at large flow: the plain-f16 flow staging (vfml_flow_half), the gate
+    convolutions that read only the hi halves of the flow channels, lookups outside the volume.  T = 5: a window with more
+    than one centre."""
+    from vfml.cfg import DEFAULT_MIXED_CORR_VOLUME, DEFAULT_MIXED_PLAN
+    _check((f"randf-T{T}-{H}x{W}", "randf", T, H, W, 12, "forward"), "mixed", seed, DEFAULT_MIXED_PLAN,
+           DEFAULT_MIXED_CORR_VOLUME, drift=c)
 
 
 def test_full_size_field_within_k_times_the_oracles_own_noise(gpu):

@@ -1022,15 +1022,68 @@ def test_encoder_c64_kernel_is_the_general_convolution(gpu, n, H, W):
     assert rel_err(got, ref) < CONV_TOL["f16x3"], rel_err(got, ref)
 
 
-@pytest.mark.parametrize("n,H,W", [(3, 135, 240), (1, 5, 31), (2, 16, 24)])
-def test_flow_half_kernel_is_the_two_convolutions(gpu, n, H, W):
+MAGNITUDE_SHAPES = [(1, 5, 31), (2, 16, 24)]      # one ragged tile; two images of several tiles
+MAGNITUDES = [1, 16, 128, 1024]                   # cells: the seeded weights' flow, a moving 1080p clip, 4K, past any frame
+
+
+def _flow_of_magnitude(g, n, H, W, m):
+    """[n, 4, H, W] flow of magnitude m: m * (+-1) * U(0.5, 1), every element its own sign."""
+    sign = torch.randint(0, 2, (n, 4, H, W), generator=g).float() * 2 - 1
+    return m * sign * (0.5 + 0.5 * torch.rand(n, 4, H, W, generator=g))
+
+
+@pytest.mark.parametrize("m", MAGNITUDES)
+@pytest.mark.parametrize("n,H,W", MAGNITUDE_SHAPES)
+def test_flow_rows7_one_mfma_convolution_of_the_rounded_flow(gpu, n, H, W, m):
+    """vfml_flow_rows7 + the 7x1 convolution at one MFMA per product (what the shipped plan does to the flow, as launches of
+    their own), f32 output, against the float64 convolution of the operands the kernel multiplies: the flow rounded to one
+    f16 and the weight plane W.hi / scale.  Those products are exact in float32, so what is left is the float32 accumulation
+    of at most 7 x 32 = 224 terms in some order and one rounding of the biased result; per element
+        |got - ref| <= 224 * 2^-24 * (|flow16| conv |w16|) + 2^-23 * |ref|
+    at every flow magnitude (an f16 holds 1024 cells exactly enough: the rounding of the flow is in the reference)."""
+    from vfml import hip
+    from vfml.weights import pack_conv_weight
+    g = torch.Generator().manual_seed(1000 * m + H * W + n)
+    flow = _flow_of_magnitude(g, n, H, W, m)
+    wt = torch.randn(128, 4, 7, 7, generator=g) / math.sqrt(4 * 49)
+    b = torch.randn(128, generator=g) * 0.1
+    P = n * H * W
+    w7 = torch.zeros(128, 32, 7, 1)
+    w7[:, :28, :, 0] = wt.permute(0, 3, 1, 2).reshape(128, 28, 7)
+    W1 = as_weight(pack_conv_weight(w7, cblock=True), 128, "f16x3", order=hip.KORDER_CBLOCK)
+    # the weights as the kernel sees them: the hi plane is the f16 of scale * w, in the packed order
+    wq = _f16(wt * W1.scale) / W1.scale
+    w7q = torch.zeros(128, 32, 7, 1, dtype=torch.float64)
+    w7q[:, :28, :, 0] = wq.permute(0, 3, 1, 2).reshape(128, 28, 7)
+    assert W1.kp == 224 and torch.equal(W1.hi.cpu().double().view(128, 224) / W1.scale,
+                                        pack_conv_weight(w7q, cblock=True).double().view(128, 224))
+    flow16 = _f16(flow)
+    ref = F.conv2d(flow16, wq, b.double(), padding=3)
+    mag = F.conv2d(flow16.abs(), wq.abs(), None, padding=3)
+    rows = torch.zeros(P * 32, device=gpu)
+    hip.flow_rows7(nhwc(flow), n, H, W, rows)
+    out = torch.full((P * 128,), float("nan"), device=gpu)
+    hip.conv2d(rows, 32, 32, n, H, W, W1, b.cuda(), 128, 7, 1, out, 128, pad_h=3, in_fmt=hip.FMT_S16, mfma=1)
+    got = from_nhwc(out, n, H, W, 128).double()
+    assert torch.isfinite(got).all()
+    err, bound = (got - ref).abs(), 224 * 2.0 ** -24 * mag + 2.0 ** -23 * ref.abs()
+    print(f"flow_rows7 + 7x1 at one MFMA, m = {m}, {n}x{H}x{W}: worst |got - ref| / bound {float((err / bound).max()):.3f}, "
+          f"max |ref| {float(ref.abs().max()):.3g}")
+    assert (err <= bound).all(), float((err / bound).max())
+
+
+@pytest.mark.parametrize("n,H,W,m", [pytest.param(3, 135, 240, None, id="3-135-240"), pytest.param(1, 5, 31, None, id="1-5-31"),
+                                     pytest.param(2, 16, 24, None, id="2-16-24")] +
+                         [pytest.param(n, H, W, m, id=f"{n}-{H}-{W}-m{m}") for n, H, W in MAGNITUDE_SHAPES for m in MAGNITUDES])
+def test_flow_half_kernel_is_the_two_convolutions(gpu, n, H, W, m):
     """vfml_flow_half (7x7 over the flow + ReLU + 3x3 + ReLU, the 128-channel map in LDS) == vfml_flow_rows7 + the two
     one-MFMA convolutions, bit for bit - ragged tiles, image borders (the zero padding of the 128-channel map, not of the
-    flow) - and within plain-f16 tolerance of the float64 result."""
+    flow) - and within plain-f16 tolerance of the float64 result.  m: flows of that magnitude in cells instead of 3 x randn
+    (the kernel rounds the flow to one f16 while staging it: the same rounding as the hi halves of vfml_flow_rows7)."""
     from vfml import hip
     from vfml.weights import pack_conv_weight
     g = torch.Generator().manual_seed(H * W + n)
-    flow = (torch.randn(n, 4, H, W, generator=g) * 3.0)
+    flow = (torch.randn(n, 4, H, W, generator=g) * 3.0) if m is None else _flow_of_magnitude(g, n, H, W, m)
     w1 = torch.randn(128, 4, 7, 7, generator=g) / math.sqrt(4 * 49)
     b1 = torch.randn(128, generator=g) * 0.1
     w2 = torch.randn(64, 128, 3, 3, generator=g) / math.sqrt(128 * 9)
@@ -1133,6 +1186,51 @@ def test_tapsum_update_is_tapsum_then_coords_update(gpu, parts):
     for a, b in zip(*res):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32))
     assert res[0][1].abs().max() > 0
+
+
+@pytest.mark.parametrize("m", MAGNITUDES)
+@pytest.mark.parametrize("n,H,W", MAGNITUDE_SHAPES)
+@pytest.mark.parametrize("kernel", ["coords_update", "tapsum3x3_update"])
+def test_flow_copies_after_twelve_updates_of_large_flow(gpu, kernel, n, H, W, m):
+    """vfml_coords_update / vfml_tapsum3x3_update over 12 iterations that add up to about m cells: coords1 and the f32 flow
+    are the float32 recurrence exactly (coords += delta; flow = coords - grid, with the tap sum in the kernel's order), and
+    the split-row copy of the flow decodes to within 2^-21 |flow| + 2^-24 of it (test_lookup_and_flow_in_split_rows' bound:
+    hi + lo keep 22 bits, whatever the magnitude)."""
+    from oracle import mof_oracle as mo
+    from vfml import hip
+    g = torch.Generator().manual_seed(1000 * m + H * W + n + len(kernel))
+    P, ld = n * H * W, 36
+    sign = torch.randint(0, 2, (n, 1, 1, 4), generator=g).float() * 2 - 1      # one direction per image and channel
+    grid = mo.coords_grid(n, H, W).permute(0, 2, 3, 1)
+    grid = torch.cat([grid, grid], -1).contiguous()
+    c = grid.clone()
+    coords = torch.empty(P * 4, device=gpu)
+    hip.coords_init(coords, n, H, W)
+    flow = torch.zeros(P * 4, device=gpu)
+    wide = torch.zeros(P * 16, device=gpu)
+    for it in range(12):
+        if kernel == "coords_update":
+            delta = (m / 12.0) * sign * (0.5 + 0.5 * torch.rand(n, H, W, 4, generator=g))
+            hip.coords_update(coords, delta.cuda().reshape(-1), n, H, W, flow_a=flow, ld_a=4, flow_b=wide, ld_b=16,
+                              flow_b_off=12, fmt_b=hip.FMT_S16)
+        else:
+            taps = (m / 108.0) * sign[..., None, :] * (0.5 + 0.5 * torch.rand(n, H, W, 9, 4, generator=g))
+            bias = torch.randn(4, generator=g) * 0.01
+            hip.tapsum3x3_update(taps.cuda().reshape(-1), ld, bias.cuda(), n, H, W, coords, flow_a=flow, ld_a=4, flow_b=wide,
+                                 ld_b=16, flow_b_off=12, fmt_b=hip.FMT_S16)
+            delta = bias.expand(n, H, W, 4).clone()              # the kernel's order: bias, then the taps row by row
+            for ky in range(3):
+                for kx in range(3):
+                    src = F.pad(taps[:, :, :, ky * 3 + kx], (0, 0, 1, 1, 1, 1))[:, ky:ky + H, kx:kx + W]
+                    delta = delta + src
+        c = c + delta
+    assert torch.equal(coords.view(n, H, W, 4).cpu(), c)
+    want = c - grid
+    assert float(want.abs().max()) > 0.5 * m * (1.0 if kernel == "coords_update" else 4.0 / 9.0)
+    assert torch.equal(flow.view(n, H, W, 4).cpu(), want)
+    dec = s16_decode(wide, P, 16, 16)
+    assert (dec[:, :12] == 0).all()
+    assert ((dec[:, 12:16] - want.view(P, 4)).abs() <= 2.0 ** -21 * want.view(P, 4).abs() + 2.0 ** -24).all()
 
 
 @pytest.mark.parametrize("n,H,W,tile", [(3, 135, 240, None), (1, 17, 23, "3,2,2,2"), (2, 9, 14, "2,2,2,2")])

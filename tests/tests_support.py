@@ -159,6 +159,52 @@ def noise_floor_low(x, cfg, state_dict, plan=None, corr_volume="f32"):
     return low_stats(p["f32"][1], p["f64"][1])
 
 
+# ----------------------------------------------------------------------------- large flow from the seeded weights
+DRIFT_DIRECTION = (1.0, -0.5, -1.0, 0.75)       # forward x, forward y, backward x, backward y: cells per iteration and unit c
+DRIFT_KEY = "update_block.flow_head.conv2.bias"
+
+
+def drift_state_dict(sd, c):
+    """A copy of state dict `sd` whose flow head adds c * DRIFT_DIRECTION cells to the flow in every iteration: the seeded
+    weights' own flow stays near one cell, with this the 1/8-resolution flow reaches about depth * c cells (forward and
+    backward, x and y each another way).  Every other entry is the same tensor's clone; oracle and engine load the same
+    dict."""
+    out = {k: v.clone() for k, v in sd.items()}
+    b = out[DRIFT_KEY]
+    out[DRIFT_KEY] = b + float(c) * torch.tensor(DRIFT_DIRECTION, dtype=b.dtype, device=b.device)
+    return out
+
+
+_F64 = {}
+
+
+def oracle_f64_fields(x, cfg, state_dict, plan=None, corr_volume="f32"):
+    """(flow, low) of the float64 oracle alone - the plain one, or with `plan` the plan oracle - for frames x
+    [1, T, 3, H, W], computed once per session and input (half the work of oracle_pair where no float32 run is needed)."""
+    key = (_digest(x), repr(sorted(vars(cfg).items())), _digest(*state_dict.values()),
+           None if plan is None else repr(sorted((k, str(v)) for k, v in plan.items())), corr_volume)
+    ent = _F64.get(key)
+    if ent is None:
+        torch.set_num_threads(min(16, torch.get_num_threads()))
+        if plan is None:
+            net = oracle_f64(cfg, state_dict)
+        else:
+            from oracle import plan_oracle as po
+            net = po.build_network(cfg, plan, corr_volume).eval()
+            net.load_state_dict(state_dict)
+            net.double()
+        ent = _F64[key] = net(x.double(), {}, return_lowres=True)
+    return ent
+
+
+def plan_deviation(x, cfg, state_dict, plan, corr_volume="f32"):
+    """error_stats of the plan oracle's field against the plain oracle's, both in float64: what the plan's roundings cost
+    on this input with these weights, no engine involved.  Returns (stats, max |low| of the plain oracle in cells)."""
+    ref, low = oracle_f64_fields(x, cfg, state_dict)
+    got, _ = oracle_f64_fields(x, cfg, state_dict, plan, corr_volume)
+    return error_stats(got, ref), float(low.abs().max())
+
+
 # ----------------------------------------------------------------------------- input kinds
 INPUT_KINDS = ("rand", "clip", "letterbox", "patch", "black", "white")
 
