@@ -27,8 +27,8 @@
 extern "C" {
 #endif
 
-/* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay and VFML_COMPOSE_GRID_2X3: additions only, every earlier
- * entry point keeps its signature and its results, so the number did not move. */
+/* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3 and vfml_resize_u8: additions only,
+ * every earlier entry point keeps its signature and its results, so the number did not move. */
 #define VFML_ABI_VERSION 25
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -510,6 +510,23 @@ size_t vfml_flow_turbulence_workspace_bytes(int h, int w);
 int vfml_flow_turbulence_map(const float* flow, int fh, int fw, int h, int w, int ksize, void* workspace,
                              unsigned char* out_bgr, unsigned char* out_index, float* out_tv, float* out_lohi,
                              void* stream);
+
+/* Resize n RGB pictures [H][W][3] u8 into [h][w][3] u8: OpenCV's 8-bit INTER_LINEAR scheme as this project defines it
+ * (reference video/frame_extractor.py: cv2.resize of every --fast frame), not pinned against cv2.
+ * Rows are contiguous; picture f starts at src + f * src_frame_stride / dst + f * dst_frame_stride (bytes, any
+ * alignment), so a frame of a clip or a row slice of a larger frame is addressed in place.  All on `stream`, no
+ * allocation, no host synchronisation.
+ *   (h, w) == (H, W)        the pictures are copied unchanged (tables not read);
+ *   H == 2h and W == 2w     out = (a + b + c + d + 2) >> 2 over each 2x2 block (tables not read, may be null);
+ *   otherwise               separable, integer only: xtab [w][4] / ytab [h][4] are device tables of int32 rows
+ *                           (s, s1, a0, a1), 16-byte aligned, written by the host (vfml/hip.py resize_tables: the tap
+ *                           positions and the 11-bit weights, the only float work of the scheme);
+ *                           r_y = p[y][s] * a0 + p[y][s1] * a1 for the y table's two rows y0, y1 with weights b0, b1,
+ *                           out = u8((((b0 * (r_y0 >> 4)) >> 16) + ((b1 * (r_y1 >> 4)) >> 16) + 2) >> 2), arithmetic shifts.
+ * Tap positions are clamped to the picture on the device: every access stays in bounds whatever the tables hold.
+ * Sides up to 32768.  SURVEY.md row 11. */
+int vfml_resize_u8(const unsigned char* src, int n, int H, int W, int64_t src_frame_stride, unsigned char* dst, int h,
+                   int w, int64_t dst_frame_stride, const int32_t* xtab, const int32_t* ytab, void* stream);
 
 const char* vfml_last_error(void);
 int vfml_abi_version(void);

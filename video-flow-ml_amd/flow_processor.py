@@ -17,6 +17,9 @@ bottom half - the layout `--flow-only --flow-format motion-vectors-rg8|rgb8` wri
 original | external flow picture over TAA | TAA simple over TAA with the external flow | flow difference
 (vfml_flow_decode, vfml_flow_diff_overlay, the GRID_2X3 layout of vfml_compose_frame).  Out of scope:
 text labels on the tiles and the Tk/Qt tools; flags that only concern those are accepted and reported as skipped.
+With --fast the frames are first reduced by the reference's rule (video/frame_extractor.py: fit 256x256, at most a
+quarter / a half of the source, even sides, at least 64) and the whole job runs at that size: on a GPU the frames go up at
+source size and vfml_resize_u8 reduces them behind the upload (vfml.runner.ClipFeeder), --device cpu resizes on the host.
 Inputs: a `.npy` file holding uint8 frames [F,H,W,3]; `synthetic:WxHxF` (vfml.synth); an `.avi` file of the kinds
 storage/avi_writer.py writes (storage/avi_reader.py); or any video file when OpenCV is importable.
 """
@@ -38,6 +41,9 @@ from processing.memflow_inference import MemFlowInference
 from storage import AsyncFlowCacheWriter, FlowCacheManager
 from vfml import dist as vdist
 from vfml.runner import ClipFeeder, run_sharded
+from video.frame_extractor import fast_mode_dimensions, resize_frame
+from video.video_info import (SYNTHETIC_FPS, own_avi_reader, probe_video, read_frames, time_to_frame,
+                              validate_frame_range)
 
 
 def build_parser():
@@ -49,7 +55,7 @@ def build_parser():
     p.add_argument('--start-frame', type=int, default=0)
     p.add_argument('--start-time', type=float, default=None)
     p.add_argument('--duration', type=float, default=None)
-    p.add_argument('--fast', action='store_true', help='Fast mode (depth 6, 3 levels, radius 3)')
+    p.add_argument('--fast', action='store_true', help='Fast mode (reduced resolution; depth 6, 3 levels, radius 3)')
     p.add_argument('--flow-only', action='store_true')
     p.add_argument('--taa', action='store_true')
     p.add_argument('--flow-input', type=str, default=None)
@@ -75,56 +81,10 @@ def build_parser():
     return p
 
 
-SYNTHETIC_FPS = 30.0     # frame rate of `synthetic:` clips and .npy frame stacks (they carry none)
-
-
-def time_to_frame(time_seconds, fps):
-    """Seconds -> frame number, the reference's rule (flow_processor.py:137-139, video/video_info.py:80-93)."""
-    if fps <= 0:
-        raise ValueError("Cannot convert time to frame: invalid FPS")
-    return int(time_seconds * fps)
-
-
-def validate_frame_range(start_frame, frame_count, total_frames):
-    """The reference's clamp (video/video_info.py:110-132): negative starts become 0, a start past the end is an
-    error, the count is cut to what the clip holds."""
-    if start_frame < 0:
-        start_frame = 0
-    elif start_frame >= total_frames:
-        raise ValueError(f"Start frame {start_frame} exceeds total frames {total_frames}")
-    return start_frame, min(frame_count, total_frames - start_frame)
-
-
-def _own_avi_reader(spec):
-    """True when `spec` is an .avi file and OpenCV is not importable: storage/avi_reader.py reads it then."""
-    if not spec.lower().endswith('.avi'):
-        return False
-    try:
-        import cv2  # noqa: F401
-    except ImportError:
-        return True
-    return False
-
-
 def probe_input(spec):
     """-> (fps, total_frames) of an input without decoding it."""
-    if spec.startswith('synthetic:'):
-        w, h, n = (int(v) for v in spec.split(':', 1)[1].lower().split('x'))
-        return SYNTHETIC_FPS, n
-    if spec.endswith('.npy'):
-        return SYNTHETIC_FPS, int(np.load(spec, mmap_mode='r').shape[0])
-    if _own_avi_reader(spec):
-        from storage import avi_reader
-        info = avi_reader.probe(spec)
-        return info["fps"], info["frames"]
-    try:
-        import cv2
-    except ImportError:
-        raise SystemExit(f"Cannot decode {spec}: OpenCV is not installed. Use a .npy frame stack or synthetic:WxHxF.")
-    cap = cv2.VideoCapture(spec)
-    fps, n = cap.get(cv2.CAP_PROP_FPS), int(cap.get(cv2.CAP_PROP_FRAME_COUNT))
-    cap.release()
-    return fps, n
+    info = probe_video(spec)
+    return info["fps"], info["total_frames"]
 
 
 def resolve_frame_range(spec, start_frame, max_frames, start_time=None, duration=None, log=print):
@@ -146,39 +106,22 @@ def resolve_frame_range(spec, start_frame, max_frames, start_time=None, duration
 
 def load_frames(spec, start_frame, max_frames, fps_default=SYNTHETIC_FPS):
     """-> (frames list of uint8 [H,W,3], fps, width, height, start_frame): the 5-tuple shape of the
-    reference's FrameExtractor.extract_frames (video/frame_extractor.py:139)."""
-    if spec.startswith('synthetic:'):
-        from vfml.synth import synthetic_clip
-        w, h, n = (int(v) for v in spec.split(':', 1)[1].lower().split('x'))
-        frames = synthetic_clip(n, h, w)[start_frame:start_frame + max_frames]
-    elif spec.endswith('.npy'):
-        arr = np.load(spec, mmap_mode='r')
-        if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
-            raise ValueError(f"{spec}: expected uint8 [F,H,W,3], got {arr.dtype} {arr.shape}")
-        frames = [np.ascontiguousarray(f) for f in arr[start_frame:start_frame + max_frames]]
-    elif _own_avi_reader(spec):
-        from storage import avi_reader
-        fps_default = avi_reader.probe(spec)["fps"] or fps_default
-        frames = avi_reader.read_frames(spec, start_frame, max_frames)
-    else:
-        try:
-            import cv2
-        except ImportError:
-            raise SystemExit(f"Cannot decode {spec}: OpenCV is not installed. Use a .npy frame stack or synthetic:WxHxF.")
-        cap = cv2.VideoCapture(spec)
-        fps_default = cap.get(cv2.CAP_PROP_FPS) or fps_default
-        cap.set(cv2.CAP_PROP_POS_FRAMES, start_frame)
-        frames = []
-        while len(frames) < max_frames:
-            ok, bgr = cap.read()
-            if not ok:
-                break
-            frames.append(cv2.cvtColor(bgr, cv2.COLOR_BGR2RGB))
-        cap.release()
+    reference's FrameExtractor.extract_frames (video/frame_extractor.py:139), at the source's size."""
+    frames, fps = read_frames(spec, start_frame, max_frames, fps_default)
     if not frames:
         raise SystemExit(f"No frames read from {spec}")
     h, w = frames[0].shape[:2]
-    return frames, fps_default, w, h, start_frame
+    return frames, fps, w, h, start_frame
+
+
+def fast_mode_size(width, height, log=print):
+    """--fast's resolution rule on the source size (reference video/frame_extractor.py:26-62, :103-104, :129-130) ->
+    (width, height) the job runs at, with the reference's line.  Frames are resized only when the rule's factor is not
+    1.0; a source it leaves alone keeps its own size here (the reference reports the rule's sides even then, which for a
+    source under 64 pixels are not the frames')."""
+    w, h, scale = fast_mode_dimensions(width, height)
+    log(f"Fast mode: aggressive resolution reduction from {width}x{height} to {w}x{h} (scale: {scale:.2f})")
+    return (w, h) if scale != 1.0 else (width, height)
 
 
 ENCODER_LINES = {
@@ -241,7 +184,7 @@ class FlowInputVideo:
             if arr.ndim != 4 or arr.shape[3] != 3 or arr.dtype != np.uint8:
                 raise ValueError(f"{spec}: expected uint8 [F,H,W,3], got {arr.dtype} {arr.shape}")
             self._arr, self.total, self.height, self.width = arr, *(int(v) for v in arr.shape[:3])
-        elif _own_avi_reader(spec):
+        elif own_avi_reader(spec):
             from storage.avi_reader import AviReader
             self._avi = AviReader(spec)
             self.total, self.height, self.width = self._avi.frame_count, self._avi.height, self._avi.width
@@ -352,13 +295,21 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     frame - already in the AVI chunk's layout - comes back through a pinned ring one frame behind the GPU.  --device
     cpu runs the same loop with the host implementations.  With --taa --flow-input the frame is the 2x3 grid: the
     flow video's encoded half is decoded per frame (vfml_flow_decode), feeds a third TAA history and the difference
-    overlay (vfml_flow_diff_overlay), and its re-encoded picture takes the flow tile's place."""
+    overlay (vfml_flow_diff_overlay), and its re-encoded picture takes the flow tile's place.
+    width x height is the size the job ran at: the frames' own, or under --fast the reduced one - then `frames` are
+    already reduced (--device cpu) or still at the source's size on the host, and the ClipFeeder built here or handed in
+    resizes them on the device (vfml_resize_u8).  A cache whose fields have another size is refused."""
     from effects.taa_processor import TAAProcessor
     from storage.avi_writer import AviWriter, dib_stride
     from visualization.video_composer import (compose_device, create_6_video_grid, create_difference_overlay,
                                               create_side_by_side)
 
     n = len(frames)
+    cached = tuple(np.shape(FlowCacheManager().load_cached_flow(cache_dir, 0, fmt))[:2])
+    if cached != (height, width):
+        raise ValueError(f"Flow cache {cache_dir} holds {cached[1]}x{cached[0]} fields, the frames are {width}x{height}: "
+                         f"it was written at another resolution (a `fast` cache from before --fast reduced the "
+                         f"frames, or a foreign --use-flow-cache). Recompute it with --force-recompute.")
     output_path = render_output_path(args, fps, log)
     log(f"Processing: {args.input} -> {output_path}")
     log(f"Video FPS: {fps:.2f}")
@@ -437,7 +388,7 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
     from vfml import hip
     n = len(frames)
     if feeder is None:
-        feeder = ClipFeeder(frames, device)
+        feeder = ClipFeeder(frames, device, size=(height, width))      # (host frames of another size: --fast's source frames)
     stream = torch.cuda.current_stream()
     # fields: host -> pinned slot -> device; a slot is refilled once its copy has left it
     fslots = [torch.empty((height, width, 2), dtype=torch.float32).pin_memory() for _ in range(3)]
@@ -539,6 +490,12 @@ def main(argv=None):
         return 1
     frames, fps, width, height, start = load_frames(args.input, start_frame, max_frames)
     n = len(frames)
+    if args.fast:
+        # the whole job runs at the reduced size.  On a GPU the frames stay as they are on the host and every ClipFeeder
+        # resizes them behind their upload; --device cpu resizes them here
+        width, height = fast_mode_size(width, height, log)
+        if frames[0].shape[:2] != (height, width) and not str(device).startswith('cuda'):
+            frames = [resize_frame(f, (width, height)) for f in frames]
     mgr = FlowCacheManager()
     cache_src = args.input if not args.input.startswith('synthetic:') else os.path.join(args.output, args.input.replace(':', '_') + ".npy")
     memflow = args.model == 'memflow'
@@ -563,7 +520,8 @@ def main(argv=None):
                                  args.vf_architecture, args.vf_variant)
     eng.load_model()
     proc = eng.get_processor()
-    feeder = ClipFeeder(frames, device)     # frames go up through a pinned ring while earlier fields compute
+    # frames go up through a pinned ring while earlier fields compute (--fast: and are resized on the device behind it)
+    feeder = ClipFeeder(frames, device, size=(height, width))
     save_format = args.save_flow or 'npz'
     tiled = bool(args.tile and not memflow)
     num_lods = 0 if args.skip_lods else 5

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -179,6 +179,8 @@ def lib():
     L.vfml_flow_turbulence_workspace_bytes.restype = ctypes.c_size_t
     L.vfml_flow_turbulence_map.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]
+    L.vfml_resize_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
+                                 c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -195,7 +197,7 @@ EXPORTS = [
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
-    "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map",
+    "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -893,6 +895,89 @@ def flow_turbulence_map(flow, height, width, kernel_size=25, want=()):
                                       c_void_p(out.data_ptr()), opt("index"), opt("tv"), opt("lohi"), _stream()),
            "vfml_flow_turbulence_map")
     return (out, *[more[name] for name in want]) if want else out
+
+
+_RESIZE_TABLES = {}
+
+
+def resize_tables(S, D, device=None):
+    """Taps and weights of one axis of the picture resize: int32 [D, 4] rows (s, s1, a0, a1) for a
+    source of S and a destination of D pixels - the scheme's only float work, done here in numpy for the host path
+    (video.resize_frame) and the kernel (vfml_resize_u8) alike.  device=None: the numpy table (read-only); else the same
+    rows as a device tensor.  Cached per (S, D, device)."""
+    import numpy as np
+    S, D = int(S), int(D)
+    if S < 1 or D < 1:
+        raise ValueError(f"resize_tables: lengths {S} -> {D}")
+    if device is not None:
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+    key = (S, D, None if device is None else str(device))
+    tab = _RESIZE_TABLES.get(key)
+    if tab is not None:
+        return tab
+    if device is not None:
+        tab = torch.tensor(resize_tables(S, D)).to(device)
+    else:
+        scale = np.float64(S) / np.float64(D)
+        f = ((np.arange(D, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+        s = np.floor(f)
+        f = (f - s).astype(np.float32)                  # float32 - float32
+        s = s.astype(np.int64)
+        lo, hi = s < 0, s >= S - 1
+        s[lo], f[lo] = 0, 0
+        s[hi], f[hi] = S - 1, 0
+        tab = np.empty((D, 4), dtype=np.int32)
+        tab[:, 0] = s
+        tab[:, 1] = np.minimum(s + 1, S - 1)
+        tab[:, 2] = np.rint((np.float32(1) - f) * np.float32(2048))     # rint: half to even, in float32
+        tab[:, 3] = np.rint(f * np.float32(2048))
+        tab.setflags(write=False)
+    _RESIZE_TABLES[key] = tab
+    return tab
+
+
+def _pictures(t, name):
+    """(n, H, W, frame stride in bytes) of a uint8 device tensor [H,W,3] or [F,H,W,3] whose rows are contiguous."""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.dim() in (3, 4) and t.shape[-1] == 3):
+        raise ValueError(f"resize_u8: {name} must be a uint8 device tensor [H,W,3] or [F,H,W,3], got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    H, W = int(t.shape[-3]), int(t.shape[-2])
+    if H < 1 or W < 1 or (t.dim() == 4 and t.shape[0] < 1):
+        raise ValueError(f"resize_u8: empty {name} {tuple(t.shape)}")
+    if t.stride(-1) != 1 or t.stride(-2) != 3 or (H > 1 and t.stride(-3) != 3 * W):
+        raise ValueError(f"resize_u8: the rows of {name} must be contiguous (strides {t.stride()})")
+    if t.dim() == 3:
+        return 1, H, W, 3 * H * W
+    if t.shape[0] > 1 and t.stride(0) < 3 * H * W:
+        raise ValueError(f"resize_u8: the frames of {name} overlap (strides {t.stride()})")
+    return int(t.shape[0]), H, W, (int(t.stride(0)) if t.shape[0] > 1 else 3 * H * W)
+
+
+def resize_u8(src, size, out=None):
+    """uint8 RGB pictures [H,W,3] or [F,H,W,3] (a device tensor with contiguous rows: whole pictures, frames of a clip or
+    a row slice of a larger frame) -> [h,w,3] / [F,h,w,3], size = (h, w) (vfml_resize_u8: stream-ordered, no
+    synchronisation; the tap tables are uploaded the first time a pair of lengths is seen on a device).  `out`: a device
+    tensor of the result's shape with contiguous rows - a frame inside a clip, say - filled and returned."""
+    h, w = int(size[0]), int(size[1])
+    n, H, W, sstride = _pictures(src, "src")
+    if h < 1 or w < 1:
+        raise ValueError(f"resize_u8: size {(h, w)}")
+    shape = (h, w, 3) if src.dim() == 3 else (n, h, w, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=src.device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != shape or out.device != src.device:
+        raise ValueError(f"resize_u8: out must be a uint8 tensor {shape} on {src.device}, got "
+                         f"{tuple(getattr(out, 'shape', ()))} on {getattr(out, 'device', None)}")
+    dstride = _pictures(out, "out")[3]
+    xt = yt = None
+    if (h, w) != (H, W) and not (H == 2 * h and W == 2 * w):
+        xt = c_void_p(resize_tables(W, w, src.device).data_ptr())
+        yt = c_void_p(resize_tables(H, h, src.device).data_ptr())
+    _check(lib().vfml_resize_u8(c_void_p(src.data_ptr()), n, H, W, sstride, c_void_p(out.data_ptr()), h, w, dstride, xt, yt,
+                                _stream()), "vfml_resize_u8")
+    return out
 
 
 def convex_upsample(coords1, coords_off, ch, mask, mask_off, ld_mask, h, w, out, out_off=0):

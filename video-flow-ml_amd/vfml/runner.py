@@ -66,8 +66,24 @@ class _LazyMaxima:
     def __getitem__(self, i):
         v = self._vals.get(i)
         if v is None:
-            v = self._vals[i] = float(self._frames[i].max())
+            v = self._vals[i] = float(self._frame(i).max())
         return v
+
+    def _frame(self, i):
+        return self._frames[i]
+
+
+class _LazyResizedMaxima(_LazyMaxima):
+    """The same of the frames as a ClipFeeder with a target size holds them: the maximum of the host resize of the frame
+    (video.resize_frame, byte for byte what the device clip gets), so it can be asked while the clip is still filling."""
+
+    def __init__(self, frames, size):
+        super().__init__(frames)
+        self._size = size
+
+    def _frame(self, i):
+        from video.frame_extractor import resize_frame
+        return resize_frame(self._frames[i], (self._size[1], self._size[0]))
 
 
 class ClipFeeder:
@@ -77,22 +93,43 @@ class ClipFeeder:
     `skip_to` left out): frames not yet uploaded are copied into a pinned ring (host memcpy, 1 ms per 1080p frame) and
     from there to the device on a side stream; the current stream waits for those copies only.  The reference uploads T
     float32 frames per field from pageable memory (processing/videoflow_processor.py:161); here every frame crosses PCIe
-    once, as uint8, while the GPU computes earlier fields."""
+    once, as uint8, while the GPU computes earlier fields.
+
+    With a target `size` (h, w) - the --fast resolution - the clip is [F,h,w,3]: a frame still crosses PCIe once, as
+    uint8 at its source size, into a staging slot on the device, and vfml_resize_u8 writes clip[f] from there on the same
+    side stream before the frame counts as ready.  A CPU "device" resizes on the host (video.resize_frame; the same bytes)."""
 
     RING = 4
 
-    def __init__(self, frames, device):
+    def __init__(self, frames, device, size=None):
         """frames: list of uint8 [H,W,3] arrays; entries may be None where this process will never need the frame (another
-        rank's stretch of a sharded clip): those are never uploaded, and asking for one raises."""
+        rank's stretch of a sharded clip): those are never uploaded, and asking for one raises.
+        size: None, or the (h, w) the clip holds the frames at (the frames' own size means None)."""
         f0 = next(f for f in frames if f is not None)
         self.device = torch.device(device)
-        self.clip = torch.empty((len(frames),) + tuple(f0.shape), dtype=torch.uint8, device=self.device)
+        self.src_shape = tuple(f0.shape)
+        if size is not None:
+            size = (int(size[0]), int(size[1]))
+            if len(self.src_shape) != 3 or self.src_shape[2] != 3 or min(size) < 1:
+                raise ValueError(f"ClipFeeder: size {size} needs [H,W,3] frames, got {self.src_shape}")
+            if size == self.src_shape[:2]:
+                size = None
+        self.size = size
+        shape = self.src_shape if size is None else size + (3,)
+        self.clip = torch.empty((len(frames),) + shape, dtype=torch.uint8, device=self.device)
         self.on_gpu = self.device.type == "cuda"
         if self.on_gpu:
-            self.ring = [torch.empty(tuple(f0.shape), dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+            self.ring = [torch.empty(self.src_shape, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
             self.ring_np = [r.numpy() for r in self.ring]
             self.events = [None] * self.RING
             self.stream = torch.cuda.Stream(device=self.device)
+            if size is not None:
+                from . import hip
+                # source-size landing slots, one per ring slot; the tap tables go up now, not inside the first upload
+                self.staging = [torch.empty(self.src_shape, dtype=torch.uint8, device=self.device) for _ in range(self.RING)]
+                if not (self.src_shape[0] == 2 * size[0] and self.src_shape[1] == 2 * size[1]):
+                    hip.resize_tables(self.src_shape[1], size[1], self.device)
+                    hip.resize_tables(self.src_shape[0], size[0], self.device)
         self.reset(frames)
 
     def reset(self, frames):
@@ -101,14 +138,14 @@ class ClipFeeder:
         from .clip_id import new_id
         f0 = next(f for f in frames if f is not None)
         if (any(f is not None and (f.dtype != np.uint8 or f.shape != f0.shape) for f in frames) or len(frames) != self.clip.shape[0]
-                or tuple(f0.shape) != tuple(self.clip.shape[1:])):
+                or tuple(f0.shape) != self.src_shape):
             raise ValueError("ClipFeeder expects uint8 frames of one shape (and, on reset, the shape it was built for)")
         self.frames = frames
         self.lo = 0            # frames [lo, next) are in the clip; frames below lo were skipped, never uploaded
         self.next = 0
         # a frame never changes once it is uploaded: the token is fixed although uploads move clip._version
         self.clip._vfml_clip_token = (new_id(), "fed")
-        self.clip._vfml_frame_maxima = _LazyMaxima(frames)
+        self.clip._vfml_frame_maxima = _LazyMaxima(frames) if self.size is None else _LazyResizedMaxima(frames, self.size)
         self.clip._vfml_frames_ready = 0
         if self.on_gpu:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))   # earlier readers of the old frames
@@ -146,7 +183,11 @@ class ClipFeeder:
             return
         if not self.on_gpu:
             for f in range(self.next, upto + 1):
-                self.clip[f] = torch.from_numpy(np.ascontiguousarray(self.frames[f]))
+                frame = self.frames[f]
+                if self.size is not None:
+                    from video.frame_extractor import resize_frame
+                    frame = resize_frame(frame, (self.size[1], self.size[0]))
+                self.clip[f] = torch.from_numpy(np.ascontiguousarray(frame))
             self.next = upto + 1
             self.clip._vfml_frames_ready = self.next
             return
@@ -157,7 +198,14 @@ class ClipFeeder:
                 self.events[r].synchronize()          # the slot's previous upload has left the pinned buffer
             np.copyto(self.ring_np[r], self.frames[f])
             with torch.cuda.stream(self.stream):
-                self.clip[f].copy_(self.ring[r], non_blocking=True)
+                if self.size is None:
+                    self.clip[f].copy_(self.ring[r], non_blocking=True)
+                else:
+                    # the slot's event is recorded behind the resize: when it has passed, the copy has left the pinned buffer
+                    # AND the resize has read staging[r], so the next frame of this slot may overwrite both
+                    from . import hip
+                    self.staging[r].copy_(self.ring[r], non_blocking=True)
+                    hip.resize_u8(self.staging[r], self.size, out=self.clip[f])
                 last = torch.cuda.Event()
                 last.record(self.stream)
             self.events[r] = last

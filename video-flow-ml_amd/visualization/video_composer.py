@@ -141,16 +141,17 @@ class VideoComposer:
     def create_side_by_side(self, original, flow_viz, flow_only: bool = False, taa_frame=None, taa_simple_frame=None,
                             model_name: str = "VideoFlow", fast_mode: bool = False, flow_format: str = "gamedev"):
         """Side-by-side, flow-only (stacked) or TAA (2x2 grid; 3 wide with one TAA frame) composition, BGR, without
-        the reference's text labels."""
+        the reference's text labels.  A flow picture of another size than the frame is resized to it first."""
+        h, w = original.shape[:2]
+        if tuple(flow_viz.shape[:2]) != (h, w):
+            # the reference's cv2.resize(flow_viz, (w, h)): the project's uint8 resize (DESIGN.md section 11), host or device
+            from video.frame_extractor import resize_frame
+            flow_viz = resize_frame(flow_viz, (w, h))
         if _on_gpu(original):
             if taa_frame is not None and taa_simple_frame is None and not flow_only:
                 raise ValueError("create_side_by_side: the 3-wide single-TAA layout is host only")
             out = compose_device(original, flow_viz, taa_frame, taa_simple_frame, flow_only)
             return out.view(out.shape[0], -1, 3)
-        h, w = original.shape[:2]
-        if flow_viz.shape[:2] != (h, w):
-            raise ValueError(f"create_side_by_side: flow picture {flow_viz.shape[:2]} is not at the frame's size "
-                             f"{(h, w)} (the reference resizes it with OpenCV; not built)")
         orig_bgr = np.ascontiguousarray(original[:, :, ::-1])
         flow_bgr = np.ascontiguousarray(flow_viz[:, :, ::-1])
         if flow_only:
