@@ -27,8 +27,9 @@
 extern "C" {
 #endif
 
-/* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3 and vfml_resize_u8: additions only,
- * every earlier entry point keeps its signature and its results, so the number did not move. */
+/* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3, vfml_resize_u8 and the vfml_jpeg_*
+ * entry points: additions only, every earlier entry point keeps its signature and its results, so the number did not
+ * move. */
 #define VFML_ABI_VERSION 25
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -527,6 +528,30 @@ int vfml_flow_turbulence_map(const float* flow, int fh, int fw, int h, int w, in
  * Sides up to 32768.  SURVEY.md row 11. */
 int vfml_resize_u8(const unsigned char* src, int n, int H, int W, int64_t src_frame_stride, unsigned char* dst, int h,
                    int w, int64_t dst_frame_stride, const int32_t* xtab, const int32_t* ytab, void* stream);
+
+/* Baseline JPEG of an RGB picture (the output video's MJPG frames): 8-bit sequential DCT, YCbCr
+ * 4:2:0, the T.81 Annex K Huffman tables unoptimised, one MCU row (16 pixel rows) per restart interval.  All integer, all
+ * on `stream`, no host synchronisation, no allocation; tests/jpeg_oracle.py is the definition in numpy and the scan
+ * equals its scan byte for byte:
+ *   the picture is padded to multiples of 16 by edge replication;
+ *   Y  = (19595 R + 38470 G + 7471 B + 32768) >> 16,  Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16;  chroma = (a + b + c + d + 2) >> 2 over 2x2 cells;
+ *   per 8x8 block X - 128:  T = (C X + 1024) >> 11,  Y = (T C^T + 16384) >> 15  with
+ *   C[k][n] = rint(8192 c_k cos((2n + 1) k pi / 16));  q = sign(Y) ((|Y| + (Q >> 1)) / Q), AC clamped to +-1023 and the
+ *   DC difference to +-2047;  MCUs in raster order, each Y00 Y01 Y10 Y11 Cb Cr;  predictors zero at the start of every
+ *   interval, intervals padded with 1-bits, FF followed by 00, RSTm (m modulo 8) after every interval but the last.
+ * rgb: [h][row_stride] bytes, a row = w RGB triples (row_stride >= 3w: a row slice of a larger buffer is addressed in
+ * place).  qtables: device, [2][64] bytes, luma then chroma, natural order (storage/jpeg_tables.py quant_tables).
+ * workspace: device, 256-byte aligned, vfml_jpeg_workspace_bytes(h, w); not shared by calls that may run at once.
+ * scan: receives the entropy-coded data that goes between the SOS segment (storage/jpeg_tables.py jpeg_header) and EOI;
+ * *scan_bytes (device, 4-byte aligned) its length.  vfml_jpeg_scan_capacity(h, w) bytes always suffice; with a smaller
+ * scan_capacity nothing is written at or past scan + scan_capacity and *scan_bytes still holds the length the picture
+ * needs (the caller compares).  Sides of 1..65535 with a worst-case scan below 4 GiB; 0 from the size functions
+ * otherwise. */
+int64_t vfml_jpeg_workspace_bytes(int h, int w);
+int64_t vfml_jpeg_scan_capacity(int h, int w);
+int vfml_jpeg_encode_rgb(const unsigned char* rgb, int h, int w, int64_t row_stride, const unsigned char* qtables,
+                         void* workspace, unsigned char* scan, int64_t scan_capacity, uint32_t* scan_bytes, void* stream);
 
 const char* vfml_last_error(void);
 int vfml_abi_version(void);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Render-stage throughput: the visualiser's "Run TAA processor" command (flow_processor.py --taa --skip-lods --tile
 --flow-format hsv --use-flow-cache <cache>) on a synthetic:WxHxN clip with a complete cache of seeded fields, MJPG and
---uncompressed.  Prints one JSON line per codec: frames, seconds, frames/s, file size.  With --flow-input each codec gets
+--uncompressed.  Prints one JSON line per codec: frames, seconds, frames/s, file size, and for MJPG who encoded the frames
+("device": vfml_jpeg_encode_rgb behind the composer, only the scan copied back; "pillow": the host pool).  With --flow-input each codec gets
 a second job: the same cache rendered with --flow-only --flow-format motion-vectors-rg8 (the flow video), then
 --taa --flow-input <that video> --flow-format motion-vectors-rg8, the 2x3 comparison grid.
 
@@ -59,7 +60,10 @@ def main():
         dt = time.time() - t0
         line = [ln for ln in buf.getvalue().splitlines() if ln.startswith("Video written")]
         avi = [os.path.join(out, n) for n in os.listdir(out) if n.endswith(".avi")]
-        print(json.dumps({"job": job, "codec": codec, "size": a.size, "frames": a.frames, "rc": rc,
+        encoder = None
+        if codec == "mjpg":
+            encoder = "device" if str(a.device).startswith("cuda") and hasattr(fp, "DEVICE_MJPG") else "pillow"
+        print(json.dumps({"job": job, "codec": codec, "mjpg_encoder": encoder, "size": a.size, "frames": a.frames, "rc": rc,
                           "wall_s": round(dt, 3), "render_line": line[0] if line else None,
                           "bytes": os.path.getsize(avi[0]) if avi else None}), flush=True)
         if not keep:

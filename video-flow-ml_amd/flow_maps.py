@@ -88,9 +88,12 @@ def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', ker
     mgr = FlowCacheManager()
     cache_dir = os.path.normpath(str(cache_dir))
     h, w = frames[0].shape[:2]
-    writer = AviWriter(output, 0 if uncompressed else 'MJPG', fps, (2 * w, 2 * h), log=log)
-    uncompressed = not writer.mjpg
+    writer = AviWriter(output, 0 if uncompressed else 'MJPG', fps, (2 * w, 2 * h), log=log, encoder='external')
     stride = dib_stride(2 * w) if uncompressed else None
+    jpeg = None
+    if not uncompressed:           # MJPG frames are encoded on the device (vfml_jpeg_encode_rgb); only the scan comes back
+        from storage.device_mjpg import DeviceMjpgEncoder
+        jpeg = DeviceMjpgEncoder(writer, 2 * h, 2 * w, device)
     written = 0
     try:
         for i in frame_indices:
@@ -107,10 +110,13 @@ def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', ker
             fl = torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32)).to(device)
             out = hip.compose_frame(qa_tiles_resident(f1, f2, fl, k, threshold), hip.COMPOSE_GRID_2X2, bgr=uncompressed,
                                     bottom_up=uncompressed, row_stride=stride)
-            buf = out.cpu().numpy()
-            writer.write_payload(buf if uncompressed else buf.reshape(2 * h, 2 * w, 3))
-            writer.drain()
+            if jpeg is not None:
+                jpeg.submit(out.view(2 * h, 2 * w, 3))
+            else:
+                writer.write_payload(out.cpu().numpy())
             written += 1
+        if jpeg is not None:
+            jpeg.finish()
     finally:
         writer.release()
     return written

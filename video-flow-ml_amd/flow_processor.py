@@ -288,6 +288,11 @@ class _FieldReader:
         self.pool.shutdown(cancel_futures=True)
 
 
+# The device render path's MJPG frames are encoded on the GPU (vfml_jpeg_encode_rgb); False: its
+# composed frames go back uncompressed to the writer's Pillow pool, as --device cpu's do.
+DEVICE_MJPG = True
+
+
 def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=None, log=print):
     """Render the complete flow cache into the output AVI (reference process_video :958-1130, one frame at a time in
     its order): flow picture, the two TAA histories (--taa), the composed frame, the writer.  Device path: the frames
@@ -332,8 +337,9 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     gpu = str(device).startswith('cuda')
     from vfml.dist import host_cpu_share
     jpeg_workers = max(1, min(8, host_cpu_share()))
+    # MJPG on the device path: the frames are encoded on the GPU (vfml_jpeg_encode_rgb) and the writer takes finished JPEGs
     writer = AviWriter(output_path, 0 if args.uncompressed else 'MJPG', fps, size, workers=jpeg_workers,
-                       depth=jpeg_workers + 1, log=log)
+                       depth=jpeg_workers + 1, log=log, encoder='external' if gpu and DEVICE_MJPG else 'pillow')
     encoder = render_encoder(args.flow_format, args.motion_vectors_clamp_range)
     taa_flow, taa_simple, taa_external = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
     variant = FLOW_INPUT_VARIANTS.get(args.flow_format)
@@ -399,9 +405,14 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
     uploads = 0
     ext_flow = None
     decode_mode = hip.ENCODE_RG8 if variant == 'rg8' else hip.ENCODE_RGB8
-    # composed frames: device -> pinned slot -> writer; a slot is reused once the writer no longer holds it
+    # composed frames: device -> pinned slot -> writer; a slot is reused once the writer no longer holds it.  MJPG: the
+    # frame stays on the device, the JPEG encoder runs behind the composer and only its scan comes back
     stride = dib_stride(size[0]) if uncompressed else 3 * size[0]
-    nslots = writer.in_flight_limit() + 3
+    jpeg = None
+    if writer.external:
+        from storage.device_mjpg import DeviceMjpgEncoder
+        jpeg = DeviceMjpgEncoder(writer, size[1], size[0], device)
+    nslots = 0 if jpeg is not None else writer.in_flight_limit() + 3
     oslots = [torch.empty((size[1], stride), dtype=torch.uint8).pin_memory() for _ in range(nslots)]
     oevents = [None] * nslots
     pending = None              # (slot) composed on the device, not yet handed to the writer
@@ -444,6 +455,9 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         out = compose_device(frame, viz, taa_frame, taa_simple_frame, flow_only=flow_only, bgr=uncompressed,
                              bottom_up=uncompressed, row_stride=stride, taa_external_frame=taa_ext,
                              difference_overlay=diff)
+        if jpeg is not None:
+            jpeg.submit(out.view(size[1], size[0], 3))
+            continue
         s = i % nslots
         writer.drain(keep=nslots - 2)        # the slot's previous frame is no longer in the writer's hands
         oslots[s].copy_(out, non_blocking=True)
@@ -454,6 +468,8 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         pending = s
     if pending is not None:
         _hand_over(writer, oslots[pending], oevents[pending], size, uncompressed)
+    if jpeg is not None:
+        jpeg.finish()
 
 
 def _hand_over(writer, slot, event, size, uncompressed):

@@ -2,7 +2,8 @@
 uncompressed, flow_processor.py:876-897).  No OpenCV.
 
 * MJPG: each frame a baseline JPEG at quality 95, encoded with Pillow on a thread pool (frames stay in order).  Without
-  Pillow the writer says so and writes uncompressed frames instead.
+  Pillow the writer says so and writes uncompressed frames instead.  `encoder='external'`: the caller hands in finished
+  JPEG files (`write_encoded`: the device encoder's frames, vfml_jpeg_encode_rgb) - no Pillow, no pool.
 * uncompressed: 24-bit BI_RGB DIB frames - BGR, bottom-up rows, each row padded to 4 bytes.
 * Files larger than one RIFF segment are OpenDML (AVI 2.0): `AVIX` segments, an `indx` super index pointing at one
   `ix00` standard index per segment, the total frame count in `odml/dmlh`, and a legacy `idx1` for the first segment.
@@ -54,15 +55,21 @@ def _jpeg(rgb):
 
 
 class AviWriter:
-    """cv2.VideoWriter-like AVI writer (one video stream).  `fourcc`: 'MJPG' or 0 / None (uncompressed)."""
+    """cv2.VideoWriter-like AVI writer (one video stream).  `fourcc`: 'MJPG' or 0 / None (uncompressed).
+    `encoder`: who makes the JPEGs of an MJPG file - 'pillow' (write / write_payload, on the writer's pool) or
+    'external' (the caller, through write_encoded)."""
 
-    def __init__(self, path, fourcc, fps, size, segment_bytes=1 << 30, workers=None, depth=None, log=print):
+    def __init__(self, path, fourcc, fps, size, segment_bytes=1 << 30, workers=None, depth=None, log=print,
+                 encoder='pillow'):
         self.path, self.fps = path, float(fps)
         self.width, self.height = (int(v) for v in size)
         self.mjpg = fourcc not in (0, None)
         if self.mjpg and fourcc != 'MJPG':
             raise ValueError(f"AviWriter: fourcc {fourcc!r}; 'MJPG' or 0 (uncompressed) are built")
-        if self.mjpg and _pillow() is None:
+        if encoder not in ('pillow', 'external'):
+            raise ValueError(f"AviWriter: encoder {encoder!r}; 'pillow' or 'external'")
+        self.external = self.mjpg and encoder == 'external'
+        if self.mjpg and not self.external and _pillow() is None:
             log("Warning: Pillow is not installed; writing uncompressed frames instead of MJPG")
             self.mjpg = False
         self.ckid = b'00dc' if self.mjpg else b'00db'
@@ -74,7 +81,7 @@ class AviWriter:
         self._seg = []                # (absolute data offset, size) of the current segment's chunks
         self.frames = 0
         self._max_chunk = 0
-        if self.mjpg:
+        if self.mjpg and not self.external:
             if workers is None:
                 from vfml.dist import host_cpu_share
                 workers = host_cpu_share()
@@ -198,6 +205,8 @@ class AviWriter:
     def write_payload(self, buf):
         """A frame in the chunk's layout: uncompressed - the DIB bytes (height x dib_stride(width)); MJPG - an RGB
         [H,W,3] uint8 image (encoded on the pool; the buffer must stay unchanged until `drain` says it was used)."""
+        if self.external:
+            raise ValueError("AviWriter: encoder='external' takes finished JPEGs through write_encoded")
         if not self.mjpg:
             data = np.asarray(buf).reshape(-1)
             if data.size != self.frame_bytes:
@@ -208,24 +217,30 @@ class AviWriter:
         while len(self._pending) > self._depth:
             self._chunk(self._pending.popleft().result())
 
+    def write_encoded(self, data):
+        """One finished JPEG file (bytes-like) as the next frame of an encoder='external' writer."""
+        if not self.external:
+            raise ValueError("AviWriter: write_encoded needs an MJPG writer with encoder='external'")
+        self._chunk(data)
+
     def drain(self, keep=0):
         """Write encoded frames until at most `keep` are still in flight."""
-        if self.mjpg:
+        if self.mjpg and not self.external:
             while len(self._pending) > keep:
                 self._chunk(self._pending.popleft().result())
 
     def in_flight(self):
-        return len(self._pending) if self.mjpg else 0
+        return len(self._pending) if self.mjpg and not self.external else 0
 
     def in_flight_limit(self):
         """Most payload buffers the writer may still hold after write_payload returns."""
-        return self._depth if self.mjpg else 0
+        return self._depth if self.mjpg and not self.external else 0
 
     def release(self):
         if self._f is None:
             return
         self.drain()
-        if self.mjpg:
+        if self.mjpg and not self.external:
             self._pool.shutdown()
         self._close_segment()
         self._patch_main_headers()

@@ -1,0 +1,84 @@
+"""MJPG frames encoded on the device (vfml_jpeg_encode_rgb) on their way into an
+AviWriter(encoder='external'): the composed frame never leaves the device uncompressed, only its scan comes back.
+
+Per frame, all on the caller's current stream: the encoder runs behind the kernel that wrote the picture; the length
+cell is copied to pinned memory; one frame later the host reads it and copies exactly that many bytes into a pinned slot
+that already holds the file header; one frame after that the slot - header, scan, EOI - is appended to the AVI.  The
+host therefore never waits for the frame the GPU is working on, and never copies the worst-case capacity.
+"""
+import torch
+
+from .avi_writer import JPEG_QUALITY
+
+SLOTS = 3      # a slot is encoded into at frame i, fetched at i + 1, written at i + 2 and free again at i + 3
+
+
+class DeviceMjpgEncoder:
+    def __init__(self, writer, height, width, device, quality=JPEG_QUALITY):
+        from vfml import hip
+        if not getattr(writer, "external", False):
+            raise ValueError("DeviceMjpgEncoder: the writer must be an MJPG AviWriter with encoder='external'")
+        if (writer.height, writer.width) != (height, width):
+            raise ValueError(f"DeviceMjpgEncoder: frames of {width}x{height} for a {writer.width}x{writer.height} writer")
+        self._hip, self._writer, self._quality = hip, writer, int(quality)
+        self._header = hip.jpeg_header(height, width, self._quality)
+        capacity = hip.jpeg_scan_capacity(height, width)
+        self._scan = [torch.empty(capacity, dtype=torch.uint8, device=device) for _ in range(SLOTS)]
+        self._length = [torch.empty(1, dtype=torch.int32).pin_memory() for _ in range(SLOTS)]
+        self._host = [self._slot(max(4096, 3 * height * width // 6)) for _ in range(SLOTS)]
+        self._bytes = [0] * SLOTS
+        self._length_event = [None] * SLOTS
+        self._copy_event = [None] * SLOTS
+        self._encoded = self._copying = None      # slots whose length / whose scan is on its way to the host
+        self._frames = 0
+
+    def _slot(self, scan_bytes):
+        """Pinned bytes for a file with a scan of `scan_bytes`: header in place, room for the scan and EOI."""
+        n = len(self._header)
+        t = torch.empty(n + scan_bytes + 2, dtype=torch.uint8).pin_memory()
+        t[:n] = torch.frombuffer(bytearray(self._header), dtype=torch.uint8)
+        return t
+
+    def submit(self, rgb):
+        """rgb: the frame, uint8 device tensor [H,W,3] with contiguous rows, written on the current stream."""
+        s = self._frames % SLOTS
+        self._frames += 1
+        _, length = self._hip.jpeg_encode(rgb, self._quality, out=self._scan[s])
+        self._length[s].copy_(length, non_blocking=True)
+        self._length_event[s] = torch.cuda.Event()
+        self._length_event[s].record()
+        self._advance()
+        self._encoded = s
+
+    def _advance(self):
+        if self._copying is not None:
+            self._write(self._copying)
+        self._copying = self._encoded
+        self._encoded = None
+        if self._copying is not None:
+            self._fetch(self._copying)
+
+    def _fetch(self, s):
+        self._length_event[s].synchronize()
+        n = int(self._length[s][0]) & 0xFFFFFFFF
+        if n > self._scan[s].numel():
+            raise RuntimeError(f"DeviceMjpgEncoder: the scan needs {n} bytes, its buffer holds {self._scan[s].numel()}")
+        at = len(self._header)
+        if at + n + 2 > self._host[s].numel():      # a frame that outgrows its pinned slot grows the slot
+            self._host[s] = self._slot(n + n // 4)
+        self._host[s][at:at + n].copy_(self._scan[s][:n], non_blocking=True)
+        self._copy_event[s] = torch.cuda.Event()
+        self._copy_event[s].record()
+        self._bytes[s] = n
+
+    def _write(self, s):
+        self._copy_event[s].synchronize()
+        buf = self._host[s].numpy()
+        end = len(self._header) + self._bytes[s]
+        buf[end], buf[end + 1] = 0xFF, 0xD9         # EOI
+        self._writer.write_encoded(buf[:end + 2])
+
+    def finish(self):
+        """Write the frames still on their way."""
+        self._advance()
+        self._advance()

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -73,7 +73,7 @@ def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libvfml_hip.so (in-tree). Cross-compiles without a GPU."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "vfml_common.h"), os.path.join(CSRC, "conv_split_common.h"),
-            os.path.join(CSRC, "jet_table.inc"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
+            os.path.join(CSRC, "jet_table.inc"), os.path.join(CSRC, "jpeg_tables.inc"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(
             os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -181,6 +181,12 @@ def lib():
                                            c_void_p, c_void_p]
     L.vfml_resize_u8.argtypes = [c_void_p, c_int, c_int, c_int, c_int64, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p,
                                  c_void_p]
+    L.vfml_jpeg_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_workspace_bytes.argtypes = [c_int, c_int]
+    L.vfml_jpeg_scan_capacity.restype = c_int64
+    L.vfml_jpeg_scan_capacity.argtypes = [c_int, c_int]
+    L.vfml_jpeg_encode_rgb.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -198,6 +204,7 @@ EXPORTS = [
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
+    "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -978,6 +985,78 @@ def resize_u8(src, size, out=None):
     _check(lib().vfml_resize_u8(c_void_p(src.data_ptr()), n, H, W, sstride, c_void_p(out.data_ptr()), h, w, dstride, xt, yt,
                                 _stream()), "vfml_resize_u8")
     return out
+
+
+_JPEG_WS = {}
+_JPEG_QT = {}
+
+
+def jpeg_header(h, w, quality=95):
+    """The bytes in front of the scan that jpeg_encode writes (storage/jpeg_tables.py jpeg_header)."""
+    from storage import jpeg_tables
+    return jpeg_tables.jpeg_header(h, w, quality)
+
+
+def jpeg_file(header, scan_bytes):
+    """header + scan + EOI: a complete JPEG file."""
+    from storage import jpeg_tables
+    return jpeg_tables.jpeg_file(header, scan_bytes)
+
+
+def jpeg_scan_capacity(h, w):
+    """Bytes that hold the scan of any h x w picture (vfml_jpeg_scan_capacity)."""
+    return int(lib().vfml_jpeg_scan_capacity(int(h), int(w)))
+
+
+def jpeg_encode(rgb, quality=95, out=None):
+    """RGB picture, uint8 device tensor [H,W,3] whose rows are contiguous (a row slice of a larger or wider buffer
+    included: the row stride is the tensor's) -> (scan, length): the entropy-coded data of its baseline JPEG (DESIGN.md
+    section 12) in a uint8 device tensor and its byte count in a uint32-valued int32 device cell [1]
+    (vfml_jpeg_encode_rgb: stream-ordered, no synchronisation).  jpeg_header(H, W, quality) + the first `length` bytes of
+    the scan + EOI is the file (jpeg_file); jpeg_scan reads them back and checks the length.
+    out: a contiguous uint8 device tensor that receives the scan - its size is the capacity, nothing is written past
+    it; None: one of the worst-case size is allocated.  The workspace and the quantisation tables are kept per device,
+    picture size / quality and stream."""
+    from storage import jpeg_tables
+    if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 3 and rgb.shape[2] == 3
+            and rgb.shape[0] >= 1 and rgb.shape[1] >= 1 and rgb.stride(2) == 1 and rgb.stride(1) == 3
+            and (rgb.shape[0] == 1 or rgb.stride(0) >= 3 * rgb.shape[1])):
+        raise ValueError(f"jpeg_encode: a uint8 device picture [H,W,3] with contiguous rows expected, got "
+                         f"{getattr(rgb, 'dtype', type(rgb))} {tuple(getattr(rgb, 'shape', ()))}")
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    stride = int(rgb.stride(0)) if h > 1 else 3 * w
+    L = lib()
+    need = int(L.vfml_jpeg_workspace_bytes(h, w))
+    if need == 0:
+        raise ValueError(f"jpeg_encode: picture {w}x{h} is too large for a JPEG")
+    stream = torch.cuda.current_stream().cuda_stream
+    key = (rgb.device.index, h, w, stream)
+    ws = _JPEG_WS.get(key)
+    if ws is None:
+        ws = _JPEG_WS[key] = torch.empty(need, dtype=torch.uint8, device=rgb.device)
+    qkey = (rgb.device.index, int(quality))
+    qt = _JPEG_QT.get(qkey)
+    if qt is None:
+        qt = _JPEG_QT[qkey] = torch.from_numpy(jpeg_tables.quant_tables(quality).copy()).to(rgb.device)
+    if out is None:
+        out = torch.empty(jpeg_scan_capacity(h, w), dtype=torch.uint8, device=rgb.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == rgb.device and out.dim() == 1
+              and out.is_contiguous()):
+        raise ValueError("jpeg_encode: out must be a contiguous one-dimensional uint8 tensor on the picture's device")
+    length = torch.empty(1, dtype=torch.int32, device=rgb.device)
+    _check(L.vfml_jpeg_encode_rgb(c_void_p(rgb.data_ptr()), h, w, stride, c_void_p(qt.data_ptr()), c_void_p(ws.data_ptr()),
+                                  c_void_p(out.data_ptr()), out.numel(), c_void_p(length.data_ptr()), _stream()),
+           "vfml_jpeg_encode_rgb")
+    return out, length
+
+
+def jpeg_scan(scan, length):
+    """The scan bytes of a jpeg_encode result on the host (synchronises).  A scan that did not fit its tensor raises and
+    names the size it needs."""
+    n = int(length.item()) & 0xFFFFFFFF
+    if n > scan.numel():
+        raise RuntimeError(f"jpeg_encode: the scan needs {n} bytes, its buffer holds {scan.numel()}")
+    return scan[:n].cpu().numpy().tobytes()
 
 
 def convex_upsample(coords1, coords_off, ch, mask, mask_off, ld_mask, h, w, out, out_off=0):
