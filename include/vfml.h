@@ -28,8 +28,8 @@ extern "C" {
 #endif
 
 /* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3, vfml_resize_u8 and the vfml_jpeg_*
- * entry points: additions only, every earlier entry point keeps its signature and its results, so the number did not
- * move. */
+ * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
+ * the number did not move. */
 #define VFML_ABI_VERSION 25
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -552,6 +552,46 @@ int64_t vfml_jpeg_workspace_bytes(int h, int w);
 int64_t vfml_jpeg_scan_capacity(int h, int w);
 int vfml_jpeg_encode_rgb(const unsigned char* rgb, int h, int w, int64_t row_stride, const unsigned char* qtables,
                          void* workspace, unsigned char* scan, int64_t scan_capacity, uint32_t* scan_bytes, void* stream);
+
+/* Decoder of baseline JPEG files (the MJPG frames the drop-in reads): sequential DCT, 8-bit, three
+ * components sampled 2x2 / 1x1 / 1x1 in one interleaved scan, any Huffman tables, any restart interval.  All integer, all
+ * on `stream`, no host synchronisation, no allocation, no host pass over the entropy data; the picture equals libjpeg's
+ * (Pillow's) decode byte for byte and tests/jpeg_decode_oracle.py is the definition in numpy:
+ *   entropy  T.81 F.2.2: canonical codes from BITS / HUFFVAL, EXTEND, ZRL = 16 zeros, EOB; DC predictors per component,
+ *            zero at the start of every interval; FF 00 is the byte FF, FF D0..D7 ends an interval; ceil(MCUs / Ri)
+ *            intervals with markers m = 0, 1, ... modulo 8; MCUs in raster order, each Y00 Y01 Y10 Y11 Cb Cr.
+ *   IDCT     coefficient x table entry, then libjpeg's jidctint "islow" butterfly in int32, columns first: pass 1 keeps
+ *            (x + 1024) >> 11, pass 2 gives clamp(((x + (1 << 17)) >> 18) + 128, 0, 255).
+ *   chroma   libjpeg's h2v2 "fancy" triangle filter on the planes of ceil(h/2) x ceil(w/2): for output row 2r the
+ *            neighbour row is r - 1, for 2r + 1 it is r + 1 (clamped); s[c] = 3 C[r][c] + C[nb][c];
+ *            out[2c] = (3 s[c] + s[c-1] + 8) >> 4, out[2c+1] = (3 s[c] + s[c+1] + 7) >> 4 (columns clamped).
+ *   colour   cb, cr less 128:  R = Y + ((91881 cr + 32768) >> 16),  G = Y + ((-22554 cb - 46802 cr + 32768) >> 16),
+ *            B = Y + ((116130 cb + 32768) >> 16), clamped to 0..255.
+ * scan: device, the scan_bytes of entropy-coded data between the SOS segment and EOI.  restart_interval: the file's Ri, 0:
+ * one interval.  qtables: device, [3][64] bytes, the table of Y, Cb, Cr in natural order.  tables: device, 392 int32
+ * (storage/jpeg_parse.py decode_tables): tables[2c], tables[2c+1] = which of the four Huffman tables (0..3 = DC0 AC0 DC1
+ * AC1) component c's DC and AC codes use; from tables[8] on, 96 ints per table: limit[16], offset[16] and HUFFVAL as 256
+ * bytes - a code has the first length l whose limit[l-1] exceeds the next 16 bits v of the stream and the symbol
+ * HUFFVAL[offset[l-1] + (v >> (16 - l))].
+ * Rows y0 <= y < y1 of the picture are written, row y at rgb + (y - y0) * row_stride as w RGB triples (row_stride >= 3w:
+ * a row slice of a larger buffer is a valid destination).  When Ri is a positive multiple of the MCUs per MCU row, only
+ * the intervals that hold those luma rows and chroma rows (y0 >> 1) - 1 .. ((y1 - 1) >> 1) + 1 are read at all.
+ * workspace: device, 256-byte aligned, vfml_jpeg_decode_workspace_bytes(h, w, scan_bytes) (every region sized for the
+ * worst case of h, w and scan_bytes; 0: sides outside 1..65535 or a scan of 2 GiB or more); not shared by calls that may
+ * run at once.  *status (device, 4-byte aligned) receives 0 or the OR of VFML_JPEG_ERR_*: a damaged scan is a defined
+ * result - every index is clamped or checked on the device, nothing is written outside the workspace and the output
+ * rows, whose content is then unspecified. */
+enum {
+  VFML_JPEG_ERR_INTERVALS = 1,   /* the scan does not hold ceil(MCUs / Ri) intervals          */
+  VFML_JPEG_ERR_SEQUENCE = 2,    /* restart markers out of sequence                           */
+  VFML_JPEG_ERR_CODE = 4,        /* a code that is in no Huffman table                        */
+  VFML_JPEG_ERR_INDEX = 8,       /* a coefficient index past 63                               */
+  VFML_JPEG_ERR_DATA = 16        /* an interval's bits ran out before its MCUs did            */
+};
+int64_t vfml_jpeg_decode_workspace_bytes(int h, int w, int64_t scan_bytes);
+int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
+                         const unsigned char* qtables, const int32_t* tables, int y0, int y1, void* workspace,
+                         unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
 
 const char* vfml_last_error(void);
 int vfml_abi_version(void);

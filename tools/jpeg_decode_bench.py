@@ -1,0 +1,95 @@
+"""vfml_jpeg_decode_rgb on device-resident files: time per picture at 1920x1080, at 1920x2160 with rows=(1080, 2160) (the
+--flow-input window of a 1080p job) next to the full decode of the same file, and at 3840x2160 - each beside Pillow's
+decode of the same bytes on the same box (dev tool, GPU only; not bench.py).
+
+Protocol (that of tools/jpeg_bench.py): the scene of jpeg_bench.picture encoded by the device encoder at quality 95,
+every case warmed up, device events around windows of `--calls` back-to-back decodes of the one file - its bytes
+already on the device, so a window holds the five kernels and the upload of nothing - `--windows` windows, median and
+spread.  Pillow: the median of `--windows` single decodes on one host thread.  The kernels' own times come from a
+separate run under the profiler, whose tracing slows the host:
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/jpeg_decode_bench.py --size 1920x1080 --windows 1
+
+`--size WxH` runs that one size only (full decode), so the profile's per-kernel averages belong to it."""
+import argparse
+import io
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "video-flow-ml_amd"), ROOT, os.path.join(ROOT, "tools")):
+    sys.path.insert(0, p)
+
+import numpy as np
+import torch
+
+from jpeg_bench import picture
+
+CASES = [(1920, 1080, None), (1920, 2160, None), (1920, 2160, (1080, 2160)), (3840, 2160, None)]
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--calls", type=int, default=20)
+    ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--size", default=None, help="WxH: the full decode of this size only")
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("jpeg_decode_bench: needs a GPU; nothing is measured without one")
+    from storage import jpeg_parse
+    from vfml import hip
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    cases = [(*(int(v) for v in args.size.lower().split("x")), None)] if args.size else CASES
+    out = {"calls_per_window": args.calls}
+    files = {}
+    for w, h, rows in cases:
+        if (w, h) not in files:
+            img = torch.from_numpy(picture(w, h)).cuda()
+            files[(w, h)] = hip.jpeg_file(hip.jpeg_header(h, w, 95), hip.jpeg_scan(*hip.jpeg_encode(img)))
+            del img
+        data = files[(w, h)]
+        info = jpeg_parse.parse(data)
+        dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+        y0, y1 = rows or (0, h)
+        rgb = torch.empty((y1 - y0, w, 3), dtype=torch.uint8, device="cuda")
+        for _ in range(3):
+            _, status = hip.jpeg_decode(dev, rows=rows, out=rgb, info=info)
+        hip.jpeg_decode_check(status)
+        us = []
+        for _ in range(args.windows):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.calls):
+                hip.jpeg_decode(dev, rows=rows, out=rgb, info=info)
+            e1.record()
+            torch.cuda.synchronize()
+            us.append(e0.elapsed_time(e1) / args.calls * 1e3)
+        med = statistics.median(us)
+        name = f"{w}x{h}" + (f" rows {y0}..{y1}" if rows else "")
+        line = f"{name}: {med:9.1f} us per picture (windows {min(us):.1f} .. {max(us):.1f}); file {len(data) / 1e6:.3f} MB, " \
+               f"{info.intervals} intervals"
+        res = {"us_median": med, "us_windows": us, "file_bytes": len(data), "intervals": info.intervals}
+        if Image is not None:
+            pil = []
+            for _ in range(args.windows):
+                t0 = time.perf_counter()
+                ref = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+                pil.append((time.perf_counter() - t0) * 1e6)
+            same = bool(np.array_equal(rgb.cpu().numpy(), ref[y0:y1]))
+            line += f"; Pillow (whole picture) {statistics.median(pil):9.1f} us ({min(pil):.1f} .. {max(pil):.1f}); " \
+                    f"same bytes: {same}"
+            res.update(pillow_us_median=statistics.median(pil), pillow_us=pil, same_bytes=same)
+        print(line)
+        out[name] = res
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -211,6 +211,20 @@ class FlowInputVideo:
         self._pos += frame is not None
         return frame
 
+    @property
+    def mjpg_chunks(self):
+        """True when the frames can be handed out undecoded, as JPEG files (an MJPG .avi read by storage/avi_reader.py)."""
+        return self._avi is not None and self._avi._mjpg
+
+    def read_chunk(self):
+        """-> the next frame's JPEG file (b'': repeat the frame before it) or None after the last."""
+        data = self._avi.read_chunk()
+        self._pos += data is not None
+        return data
+
+    def decode_chunk(self, data):
+        return self._avi._decode(data)
+
     def close(self):
         if self._avi is not None:
             self._avi.close()
@@ -222,9 +236,12 @@ class _ExternalFlowSource:
     """The encoded pictures of --flow-input, one per main frame (reference :724-765 and extract_flow_from_video
     :436-488): taken from frame 0 of the flow video whatever the main clip's start frame is, rows H//2... of each frame;
     a shorter flow video repeats its last picture.  The reference decodes the whole list up front; here the next
-    pictures are read ahead on one thread and decoded when their frame is rendered."""
+    pictures are read ahead on one thread and decoded when their frame is rendered.
+    device: the job's GPU.  The frames of an MJPG .avi then stay JPEG files: the thread reads a chunk's bytes and parses
+    its header, and the render loop decodes rows H//2... on the device (DESIGN.md section 13).  A frame the device
+    decoder does not take, or one without restart intervals, is decoded on the host as before."""
 
-    def __init__(self, spec, n, width, height, log):
+    def __init__(self, spec, n, width, height, log, device=None):
         from concurrent.futures import ThreadPoolExecutor
         log("[Flow Input] Extracting flow from external video...")
         self.video = FlowInputVideo(spec)
@@ -251,13 +268,31 @@ class _ExternalFlowSource:
             raise
         self.pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="flow-input")
         self.futs, self.next = {}, 0
+        self.files = device is not None and str(device).startswith('cuda') and self.video.mjpg_chunks
+        self.rows = (self.top, self.video.height)
+        self._seen = False
 
     def _read(self):
+        """-> the picture [h,w,3] uint8; or (file bytes, JpegInfo): a JPEG the device decodes; or None: no new picture."""
+        if self.files:
+            from storage.jpeg_parse import JpegUnsupported, parse
+            data = self.video.read_chunk()
+            if data is None or (not data and self._seen):
+                return None
+            self._seen = True
+            try:
+                info = parse(data)
+                if info.restart_interval > 0 and (info.h, info.w) == (self.video.height, self.video.width):
+                    return data, info
+            except JpegUnsupported:
+                pass
+            return self.video.decode_chunk(data)[self.top:]
         frame = self.video.read()
         return None if frame is None else frame[self.top:]
 
     def get(self, i, ahead=2):
-        """-> the encoded picture [h,w,3] uint8 of main frame i (i ascending), or None: repeat the one before."""
+        """-> the encoded picture [h,w,3] uint8 of main frame i (i ascending) - or its JPEG file and header, see _read -
+        or None: repeat the one before."""
         while self.next < min(self.take, i + ahead + 1):
             self.futs[self.next] = self.pool.submit(self._read)
             self.next += 1
@@ -328,7 +363,7 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
         elif not args.taa:
             log("note: --flow-input is compared in the --taa grid only; without --taa the ordinary video is rendered")
         else:
-            external = _ExternalFlowSource(args.flow_input, n, width, height, log)
+            external = _ExternalFlowSource(args.flow_input, n, width, height, log, device=device)
             size = (width * 2, height * 3)
     if args.uncompressed:
         log("Using uncompressed video codec. Output will be .avi and file size will be very large.")
@@ -400,10 +435,10 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
     fslots = [torch.empty((height, width, 2), dtype=torch.float32).pin_memory() for _ in range(3)]
     fevents = [None] * len(fslots)
     # --flow-input: the encoded pictures (3 bytes per pixel) take the same way and are decoded on the device
-    eslots = [torch.empty((height, width, 3), dtype=torch.uint8).pin_memory() for _ in range(3)] if external else []
-    eevents = [None] * len(eslots)
+    eslots, eevents = [], []    # (made when the first picture comes: a flow video of JPEG files does not need them)
     uploads = 0
     ext_flow = None
+    mjpg = None                 # --flow-input from an MJPG .avi: its frames are decoded here (DeviceMjpgDecoder)
     decode_mode = hip.ENCODE_RG8 if variant == 'rg8' else hip.ENCODE_RGB8
     # composed frames: device -> pinned slot -> writer; a slot is reused once the writer no longer holds it.  MJPG: the
     # frame stays on the device, the JPEG encoder runs behind the composer and only its scan comes back
@@ -438,7 +473,17 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         taa_ext = diff = None
         if external is not None:
             picture = external.get(i)
-            if picture is not None:
+            if isinstance(picture, tuple):
+                # the JPEG file goes up instead of the picture; rows H//2... are decoded into the tensor flow_decode reads
+                if mjpg is None:
+                    from storage.device_mjpg import DeviceMjpgDecoder
+                    mjpg = DeviceMjpgDecoder(device)
+                encoded = mjpg.submit(picture[0], picture[1], rows=external.rows)
+                ext_flow = hip.flow_decode(encoded, decode_mode, clamp_range)
+            elif picture is not None:
+                if not eslots:
+                    eslots = [torch.empty((height, width, 3), dtype=torch.uint8).pin_memory() for _ in range(3)]
+                    eevents = [None] * len(eslots)
                 e = uploads % len(eslots)
                 uploads += 1
                 if eevents[e] is not None:
@@ -470,6 +515,8 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         _hand_over(writer, oslots[pending], oevents[pending], size, uncompressed)
     if jpeg is not None:
         jpeg.finish()
+    if mjpg is not None:
+        mjpg.finish()
 
 
 def _hand_over(writer, slot, event, size, uncompressed):

@@ -186,6 +186,18 @@ class AviReader:
         self._last = None
         return k
 
+    def read_chunk(self):
+        """-> the next frame chunk's bytes, undecoded (an MJPG stream's JPEG file), or None after the last one.  An
+        empty chunk (b'') still means: repeat the frame before it."""
+        at = self._next_chunk()
+        if at is None:
+            return None
+        self._f.seek(at[0])
+        data = self._f.read(at[1])
+        self._last = None
+        self.pos += 1
+        return data
+
     def read(self):
         """-> the next frame, RGB [H,W,3] uint8, or None after the last one.  An empty chunk repeats the frame before it
         (a dropped frame)."""
@@ -221,8 +233,83 @@ class AviReader:
         self.close()
 
 
-def read_frames(path, start=0, count=None):
-    """-> list of RGB frames [start, start + count) of the file."""
+def _read_frames_device(path, start, count, device):
+    """read_frames with an MJPG stream's frames decoded on `device` (storage/device_mjpg.py DeviceMjpgDecoder); None:
+    the file is not for it - no MJPG stream, or a first frame the device decoder does not take or that has no restart
+    intervals (one serial interval is Pillow's to decode).  Later frames of that kind, and frames whose scan turns out
+    damaged, go to Pillow one by one."""
+    import torch
+
+    from .device_mjpg import DeviceMjpgDecoder
+    from .jpeg_parse import JpegUnsupported, parse
+
+    def parsed(chunk):
+        try:
+            info = parse(chunk)
+        except JpegUnsupported:
+            return None
+        return info if info.restart_interval > 0 else None
+
+    with AviReader(path) as r:
+        if not r._mjpg:
+            return None
+        r.skip(start)
+        chunk = r.read_chunk()
+        if not chunk or parsed(chunk) is None:
+            return None
+        h, w = r.height, r.width
+        out, chunks, redo, repeats = [], {}, [], []
+        dec = DeviceMjpgDecoder(device, on_error=lambda tag, e: redo.append(tag))
+        slots = [torch.empty((h, w, 3), dtype=torch.uint8).pin_memory() for _ in range(3)]
+        events, waiting = [None] * len(slots), []       # (index in out, slot) on their way to the host, oldest first
+        sent = 0                                         # frames given to the device: they alone take turns at the slots
+
+        def collect(keep):
+            while len(waiting) > keep:
+                k, s = waiting.pop(0)
+                events[s].synchronize()
+                out[k] = slots[s].numpy().copy()
+
+        with torch.cuda.device(device):
+            while chunk is not None and (count is None or len(out) < count):
+                k = len(out)
+                info = parsed(chunk) if chunk else None
+                if not chunk and out:
+                    repeats.append(k)                    # an empty chunk repeats the frame before it, once that is final
+                    out.append(None)
+                elif info is None:
+                    out.append(r._decode(chunk))
+                elif (info.h, info.w) != (h, w):
+                    raise AviError(f"{path}: JPEG of {info.w}x{info.h} in a {w}x{h} stream")
+                else:
+                    collect(len(slots) - 1)              # the slots in flight are the last ones used: the next is free
+                    s = sent % len(slots)
+                    sent += 1
+                    chunks[k] = chunk
+                    slots[s].copy_(dec.submit(chunk, info, tag=k), non_blocking=True)
+                    events[s] = torch.cuda.Event()
+                    events[s].record()
+                    waiting.append((k, s))
+                    out.append(None)
+                    for j in [j for j in chunks if j != k and j not in redo]:
+                        del chunks[j]                    # submit looked at the status of the frame before: it is whole
+                chunk = r.read_chunk() if count is None or len(out) < count else None
+            collect(0)
+            dec.finish()
+        for k in redo:                                   # a damaged scan: what Pillow makes of it, as without a device
+            out[k] = r._decode(chunks[k])
+        for k in repeats:
+            out[k] = out[k - 1]
+        return out
+
+
+def read_frames(path, start=0, count=None, device=None):
+    """-> list of RGB frames [start, start + count) of the file.  device: a GPU that decodes an MJPG stream's frames
+    (the pictures are Pillow's byte for byte); None: everything on the host."""
+    if device is not None and str(device).startswith('cuda'):
+        frames = _read_frames_device(path, start, count, device)
+        if frames is not None:
+            return frames
     with AviReader(path) as r:
         r.skip(start)
         out = []

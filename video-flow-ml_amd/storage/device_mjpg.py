@@ -1,11 +1,18 @@
-"""MJPG frames encoded on the device (vfml_jpeg_encode_rgb) on their way into an
+"""MJPG frames encoded and decoded on the device.
+
+DeviceMjpgEncoder: MJPG frames encoded on the device (vfml_jpeg_encode_rgb) on their way into an
 AviWriter(encoder='external'): the composed frame never leaves the device uncompressed, only its scan comes back.
 
 Per frame, all on the caller's current stream: the encoder runs behind the kernel that wrote the picture; the length
 cell is copied to pinned memory; one frame later the host reads it and copies exactly that many bytes into a pinned slot
 that already holds the file header; one frame after that the slot - header, scan, EOI - is appended to the AVI.  The
 host therefore never waits for the frame the GPU is working on, and never copies the worst-case capacity.
+
+DeviceMjpgDecoder is its mirror for the MJPG frames that are read (vfml_jpeg_decode_rgb): the
+file's bytes go up through a small ring of pinned slots, the picture is decoded where it is used, and the status cell of
+a frame comes back and is looked at while the next frame is on its way.
 """
+import numpy as np
 import torch
 
 from .avi_writer import JPEG_QUALITY
@@ -82,3 +89,64 @@ class DeviceMjpgEncoder:
         """Write the frames still on their way."""
         self._advance()
         self._advance()
+
+
+class DeviceMjpgDecoder:
+    """JPEG files decoded on `device`, in order, on the caller's current stream.  submit() never waits for the frame it
+    starts; a damaged scan is reported one submit later (or by finish) through `on_error(tag, RuntimeError)` - raised
+    when there is no such callback."""
+
+    def __init__(self, device, slots=SLOTS, on_error=None):
+        from vfml import hip
+        self._hip, self._device, self._on_error = hip, torch.device(device), on_error
+        self._host = [torch.empty(1 << 16, dtype=torch.uint8).pin_memory() for _ in range(slots)]
+        self._status = [torch.empty(1, dtype=torch.int32).pin_memory() for _ in range(slots)]
+        self._event = [None] * slots
+        self._tag = [None] * slots
+        self._frames = 0
+        self._unchecked = None                    # the slot whose status has not been looked at
+
+    def submit(self, data, info=None, rows=None, out=None, tag=None):
+        """data: the file's bytes (bytes-like); info: storage.jpeg_parse.parse(data) when the caller has it.  -> the
+        picture (rows y0 <= y < y1 of it), a uint8 device tensor, valid in stream order."""
+        from storage import jpeg_parse
+        if info is None:
+            info = jpeg_parse.parse(data)
+        s = self._frames % len(self._host)
+        self._frames += 1
+        if self._event[s] is not None:
+            self._event[s].synchronize()          # the slot's last upload and decode have run
+            if self._unchecked == s:
+                self._check(s)
+        n = len(data)
+        if n > self._host[s].numel():             # a file that outgrows its pinned slot grows the slot
+            self._host[s] = torch.empty(n + n // 4, dtype=torch.uint8).pin_memory()
+        self._host[s].numpy()[:n] = np.frombuffer(data, np.uint8)
+        rgb, status = self._hip.jpeg_decode(self._host[s][:n], rows=rows, out=out, device=self._device, info=info)
+        self._status[s].copy_(status, non_blocking=True)
+        self._event[s] = torch.cuda.Event()
+        self._event[s].record()
+        self._tag[s] = tag
+        previous, self._unchecked = self._unchecked, s
+        if previous is not None:
+            self._event[previous].synchronize()
+            self._check(previous)
+        return rgb
+
+    def _check(self, s):
+        try:
+            self._hip.jpeg_decode_check(int(self._status[s][0]))
+        except RuntimeError as e:
+            if self._on_error is None:
+                raise
+            self._on_error(self._tag[s], e)
+        finally:
+            if self._unchecked == s:
+                self._unchecked = None
+
+    def finish(self):
+        """Wait for the frames still on their way and look at their status."""
+        if self._unchecked is not None:
+            s = self._unchecked
+            self._event[s].synchronize()
+            self._check(s)

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -187,6 +187,10 @@ def lib():
     L.vfml_jpeg_scan_capacity.argtypes = [c_int, c_int]
     L.vfml_jpeg_encode_rgb.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                        c_void_p]
+    L.vfml_jpeg_decode_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_decode_workspace_bytes.argtypes = [c_int, c_int, c_int64]
+    L.vfml_jpeg_decode_rgb.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_void_p, c_int64, c_void_p, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -205,6 +209,7 @@ EXPORTS = [
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
+    "vfml_jpeg_decode_workspace_bytes", "vfml_jpeg_decode_rgb",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -1057,6 +1062,106 @@ def jpeg_scan(scan, length):
     if n > scan.numel():
         raise RuntimeError(f"jpeg_encode: the scan needs {n} bytes, its buffer holds {scan.numel()}")
     return scan[:n].cpu().numpy().tobytes()
+
+
+_JPEG_DEC_WS = {}
+_JPEG_DEC_TABLES = {}
+JPEG_DECODE_ERRORS = ((1, "the scan does not hold the header's number of restart intervals"),
+                      (2, "restart markers out of sequence"), (4, "a code that is in no Huffman table"),
+                      (8, "a coefficient index past 63"), (16, "an interval's bits ran out before its MCUs did"))
+
+
+def _jpeg_decode_tables(info, device):
+    """The quantisation and Huffman lookup tables of `info` on the device ([192] uint8, [392] int32), kept per device
+    and table content: the frames of an MJPG stream share theirs, and a frame whose tables are known costs one
+    dictionary lookup.  Tables seen for the first time are built (jpeg_parse.decode_tables) and uploaded from pageable
+    memory, which waits for the copy: a stream whose every frame brings Huffman tables of its own (optimize=True) pays
+    that once per frame.  The oldest of 32 entries makes room for a new one."""
+    from storage import jpeg_parse
+    key = (device.index, info.qtables.tobytes(), info.huffman, info.selectors)
+    got = _JPEG_DEC_TABLES.get(key)
+    if got is None:
+        if len(_JPEG_DEC_TABLES) >= 32:
+            del _JPEG_DEC_TABLES[next(iter(_JPEG_DEC_TABLES))]
+        qt, tables = jpeg_parse.decode_tables(info)
+        got = _JPEG_DEC_TABLES[key] = (torch.from_numpy(qt.reshape(-1).copy()).to(device),
+                                       torch.from_numpy(tables.copy()).to(device))
+    return got
+
+
+def jpeg_decode(data, rows=None, out=None, device=None, info=None):
+    """A baseline JPEG file -> (rgb, status): the picture, uint8 device tensor [H,W,3], decoded on the device byte for
+    byte as libjpeg (Pillow) decodes it (vfml_jpeg_decode_rgb, DESIGN.md section 13: stream-ordered, no
+    synchronisation once the file's tables are on the device, see _jpeg_decode_tables), and the int32 device cell [1] that holds 0 or the error bits of a damaged scan
+    (jpeg_decode_check reads it).
+    data: the file's bytes - uploaded here - or a uint8 tensor that holds them, pinned (uploaded asynchronously; the
+    caller keeps it unchanged until the copy has run) or on the device, together with info = storage.jpeg_parse.parse
+    of them; a file the decoder does not take raises jpeg_parse.JpegUnsupported before anything is launched.
+    rows=(y0, y1): rows y0 <= y < y1 of the picture alone ([y1-y0,W,3]); with one or more whole MCU rows per restart
+    interval the other intervals are not read.  out: a uint8 device tensor [rows,W,3] with contiguous pixels and a row
+    stride of at least 3 W (a row slice of a larger buffer) that receives the picture.  The workspace is kept per
+    device, picture size and stream."""
+    from storage import jpeg_parse
+    if torch.is_tensor(data):
+        if info is None:
+            raise ValueError("jpeg_decode: a tensor of file bytes needs info=storage.jpeg_parse.parse(...) of them")
+        if not (data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
+            raise ValueError("jpeg_decode: the file bytes must be a contiguous one-dimensional uint8 tensor")
+        if data.is_cuda:
+            device = data.device
+        elif not data.is_pinned():
+            raise ValueError("jpeg_decode: a host tensor of file bytes must be pinned")
+    else:
+        if info is None:
+            info = jpeg_parse.parse(data)
+        data = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise ValueError(f"jpeg_decode: device {device} is no GPU")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    s0, s1 = info.scan
+    if not 0 <= s0 <= s1 <= data.numel():
+        raise ValueError(f"jpeg_decode: scan range {info.scan} outside the {data.numel()} bytes given")
+    h, w = info.h, info.w
+    y0, y1 = (0, h) if rows is None else (int(rows[0]), int(rows[1]))
+    if not 0 <= y0 < y1 <= h:
+        raise ValueError(f"jpeg_decode: rows {rows!r} of a picture of {h}")
+    if out is None:
+        out = torch.empty((y1 - y0, w, 3), dtype=torch.uint8, device=device)
+    elif not (torch.is_tensor(out) and out.is_cuda and out.device == device and out.dtype == torch.uint8
+              and tuple(out.shape) == (y1 - y0, w, 3) and out.stride(2) == 1 and out.stride(1) == 3
+              and (out.shape[0] == 1 or out.stride(0) >= 3 * w)):
+        raise ValueError(f"jpeg_decode: out must be a uint8 tensor [{y1 - y0},{w},3] on {device} with contiguous rows")
+    stride = int(out.stride(0)) if y1 - y0 > 1 else 3 * w
+    L = lib()
+    scan = data[s0:s1].to(device, non_blocking=True)
+    # the workspace grows with the scan in powers of two, so the frames of a stream share one
+    cap = 1 << max(12, int(s1 - s0 - 1).bit_length()) if s1 > s0 else 4096
+    need = int(L.vfml_jpeg_decode_workspace_bytes(h, w, cap))
+    if need == 0:
+        raise ValueError(f"jpeg_decode: picture {w}x{h} with a scan of {s1 - s0} bytes is too large")
+    key = (device.index, h, w, torch.cuda.current_stream(device).cuda_stream)
+    ws = _JPEG_DEC_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _JPEG_DEC_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
+    qt, tables = _jpeg_decode_tables(info, device)
+    status = torch.empty(1, dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        _check(L.vfml_jpeg_decode_rgb(c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0, h, w,
+                                      int(info.restart_interval), c_void_p(qt.data_ptr()), c_void_p(tables.data_ptr()),
+                                      y0, y1, c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), stride,
+                                      c_void_p(status.data_ptr()), _stream()), "vfml_jpeg_decode_rgb")
+    return out, status
+
+
+def jpeg_decode_check(status):
+    """Reads a jpeg_decode status cell (synchronises; a device cell or its pinned copy); a damaged scan raises
+    RuntimeError and names what was found."""
+    v = int(status.item()) if torch.is_tensor(status) else int(status)
+    if v:
+        found = [text for bit, text in JPEG_DECODE_ERRORS if v & bit] or [f"status {v}"]
+        raise RuntimeError("jpeg_decode: damaged scan: " + "; ".join(found))
 
 
 def convex_upsample(coords1, coords_off, ch, mask, mask_off, ld_mask, h, w, out, out_off=0):
