@@ -593,6 +593,24 @@ int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_bytes, int h, i
                          const unsigned char* qtables, const int32_t* tables, int y0, int y1, void* workspace,
                          unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
 
+/* The same decoder with an entropy stage that does not take its parallelism from restart markers (DESIGN.md section
+ * 13.1; tests/jpeg_selfsync_oracle.py is the definition): the scan is cut into subsequences of subseq_bytes raw bytes (a
+ * power of two, 16..1024), one lane each.  Every lane decodes its subsequence from a guessed state (block 0, DC next, at
+ * its first bit); a lane decodes again whenever the exit state of the subsequence in front of it is not the state it
+ * decoded from, until nothing changes - the fixed point is the serial decode, whether or not a guess was ever right; a
+ * prefix sum of completed blocks places every subsequence; a last decode writes coefficients and DC differences, and a
+ * prefix sum per component and interval makes the DC values.  Any Ri, 0 included: a marker is a known state inside its
+ * subsequence.  A fixed number of launches; every loop is bounded by a count (rounds by subsequences in scope, a decode
+ * by the symbols that 8 subseq_bytes + 31 bits hold, blocks by the interval's 6 MCUs).  Arguments, picture, status bits
+ * and guarantees are those of vfml_jpeg_decode_rgb (status: the bit of the first error in stream order is set, others
+ * may be); the whole scan is entropy-decoded whatever the rows, only the transform is windowed.
+ * workspace: vfml_jpeg_decode_sync_workspace_bytes(h, w, scan_bytes, subseq_bytes) = that of vfml_jpeg_decode_rgb plus
+ * 20 bytes per subsequence, each region rounded up to 256 (0: as there, or subseq_bytes no such power of two). */
+int64_t vfml_jpeg_decode_sync_workspace_bytes(int h, int w, int64_t scan_bytes, int subseq_bytes);
+int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
+                              const unsigned char* qtables, const int32_t* tables, int y0, int y1, int subseq_bytes,
+                              void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
+
 const char* vfml_last_error(void);
 int vfml_abi_version(void);
 

@@ -10,7 +10,13 @@ separate run under the profiler, whose tracing slows the host:
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/jpeg_decode_bench.py --size 1920x1080 --windows 1
 
-`--size WxH` runs that one size only (full decode), so the profile's per-kernel averages belong to it."""
+`--size WxH` runs that one size only (full decode), so the profile's per-kernel averages belong to it.
+
+`--restart 0`: the files are Pillow's instead (quality 95, no DRI segment: the scan is one interval, as OpenCV's and
+ffmpeg's MJPG writers leave it) at 1920x1080 and 1920x2160, and every window measures, one after the other on the same
+bytes, the self-synchronising kernel (`--plan sync`) at each `--subseq` size, the interval
+kernel (`--plan interval`: one wave walks the whole scan; `--interval-calls` decodes per window) and one Pillow decode.
+`--plan` picks one of the two kernels."""
 import argparse
 import io
 import json
@@ -31,11 +37,66 @@ from jpeg_bench import picture
 CASES = [(1920, 1080, None), (1920, 2160, None), (1920, 2160, (1080, 2160)), (3840, 2160, None)]
 
 
+def norestart(args, hip, jpeg_parse, Image):
+    if Image is None:
+        raise SystemExit("jpeg_decode_bench --restart 0: the files are Pillow's; Pillow is not installed")
+    sizes = [tuple(int(v) for v in args.size.lower().split("x"))] if args.size else [(1920, 1080), (1920, 2160)]
+    configs = []
+    if args.plan in (None, "sync"):
+        configs += [(f"sync S={int(v)}", dict(plan="sync", subseq_bytes=int(v)), args.calls) for v in args.subseq.split(",")]
+    if args.plan in (None, "interval"):
+        configs.append(("interval", dict(plan="interval"), args.interval_calls))
+    out = {"calls_per_window": args.calls, "interval_calls_per_window": args.interval_calls}
+    for w, h in sizes:
+        buf = io.BytesIO()
+        Image.fromarray(picture(w, h), "RGB").save(buf, format="JPEG", quality=95)
+        data = buf.getvalue()
+        info = jpeg_parse.parse(data)
+        assert info.restart_interval == 0
+        dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+        rgb = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+        ref = np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+        res = {"file_bytes": len(data), "scan_bytes": info.scan[1] - info.scan[0]}
+        for name, kw, _ in configs:
+            _, status = hip.jpeg_decode(dev, out=rgb, info=info, **kw)
+            hip.jpeg_decode_check(status)
+            res[name] = {"us_windows": [], "same_bytes": bool(np.array_equal(rgb.cpu().numpy(), ref))}
+        pil = []
+        for _ in range(args.windows):
+            for name, kw, calls in configs:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(calls):
+                    hip.jpeg_decode(dev, out=rgb, info=info, **kw)
+                e1.record()
+                torch.cuda.synchronize()
+                res[name]["us_windows"].append(e0.elapsed_time(e1) / calls * 1e3)
+            t0 = time.perf_counter()
+            np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+            pil.append((time.perf_counter() - t0) * 1e6)
+        print(f"{w}x{h}, Pillow's file without restart markers: {len(data) / 1e6:.3f} MB")
+        for name, _, _ in configs:
+            us = res[name]["us_windows"]
+            res[name]["us_median"] = statistics.median(us)
+            print(f"  {name:12s} {statistics.median(us):10.1f} us per picture (windows {min(us):.1f} .. {max(us):.1f}); "
+                  f"same bytes: {res[name]['same_bytes']}")
+        print(f"  {'Pillow':12s} {statistics.median(pil):10.1f} us per picture ({min(pil):.1f} .. {max(pil):.1f})")
+        res["pillow_us_median"], res["pillow_us"] = statistics.median(pil), pil
+        out[f"{w}x{h}"] = res
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--size", default=None, help="WxH: the full decode of this size only")
+    ap.add_argument("--restart", type=int, default=None, choices=[0],
+                    help="0: Pillow-written files without restart markers, both kernels and Pillow alternating")
+    ap.add_argument("--plan", default=None, choices=["interval", "sync"], help="with --restart 0: that kernel only")
+    ap.add_argument("--subseq", default="64,128,256", help="with --restart 0: the sync kernel's subsequence sizes")
+    ap.add_argument("--interval-calls", type=int, default=2)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_decode_bench: needs a GPU; nothing is measured without one")
@@ -45,6 +106,8 @@ def main(argv=None):
         from PIL import Image
     except ImportError:
         Image = None
+    if args.restart == 0:
+        return norestart(args, hip, jpeg_parse, Image)
     cases = [(*(int(v) for v in args.size.lower().split("x")), None)] if args.size else CASES
     out = {"calls_per_window": args.calls}
     files = {}

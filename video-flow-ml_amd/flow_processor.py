@@ -238,8 +238,9 @@ class _ExternalFlowSource:
     a shorter flow video repeats its last picture.  The reference decodes the whole list up front; here the next
     pictures are read ahead on one thread and decoded when their frame is rendered.
     device: the job's GPU.  The frames of an MJPG .avi then stay JPEG files: the thread reads a chunk's bytes and parses
-    its header, and the render loop decodes rows H//2... on the device (DESIGN.md section 13).  A frame the device
-    decoder does not take, or one without restart intervals, is decoded on the host as before."""
+    its header, and the render loop decodes rows H//2... on the device (DESIGN.md section 13; a frame without restart
+    intervals, as OpenCV writes them, by the self-synchronising kernel of section 13.1).  A frame the device decoder
+    does not take is decoded on the host as before."""
 
     def __init__(self, spec, n, width, height, log, device=None):
         from concurrent.futures import ThreadPoolExecutor
@@ -282,7 +283,7 @@ class _ExternalFlowSource:
             self._seen = True
             try:
                 info = parse(data)
-                if info.restart_interval > 0 and (info.h, info.w) == (self.video.height, self.video.width):
+                if (info.h, info.w) == (self.video.height, self.video.width):
                     return data, info
             except JpegUnsupported:
                 pass

@@ -235,9 +235,9 @@ class AviReader:
 
 def _read_frames_device(path, start, count, device):
     """read_frames with an MJPG stream's frames decoded on `device` (storage/device_mjpg.py DeviceMjpgDecoder); None:
-    the file is not for it - no MJPG stream, or a first frame the device decoder does not take or that has no restart
-    intervals (one serial interval is Pillow's to decode).  Later frames of that kind, and frames whose scan turns out
-    damaged, go to Pillow one by one."""
+    the file is not for it - no MJPG stream, or a first frame the device decoder does not take.  Later frames of that
+    kind, and frames whose scan turns out damaged, go to Pillow one by one.  A frame without restart intervals (Pillow's,
+    OpenCV's, ffmpeg's) is decoded on the device like any other, by the kernel jpeg_parse.decode_plan names."""
     import torch
 
     from .device_mjpg import DeviceMjpgDecoder
@@ -245,10 +245,9 @@ def _read_frames_device(path, start, count, device):
 
     def parsed(chunk):
         try:
-            info = parse(chunk)
+            return parse(chunk)
         except JpegUnsupported:
             return None
-        return info if info.restart_interval > 0 else None
 
     with AviReader(path) as r:
         if not r._mjpg:

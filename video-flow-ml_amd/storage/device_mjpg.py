@@ -94,7 +94,7 @@ class DeviceMjpgEncoder:
 class DeviceMjpgDecoder:
     """JPEG files decoded on `device`, in order, on the caller's current stream.  submit() never waits for the frame it
     starts; a damaged scan is reported one submit later (or by finish) through `on_error(tag, RuntimeError)` - raised
-    when there is no such callback."""
+    when there is no such callback.  stats: frames submitted per kernel, {'interval': n, 'sync': n}."""
 
     def __init__(self, device, slots=SLOTS, on_error=None):
         from vfml import hip
@@ -105,10 +105,13 @@ class DeviceMjpgDecoder:
         self._tag = [None] * slots
         self._frames = 0
         self._unchecked = None                    # the slot whose status has not been looked at
+        self.stats = {"interval": 0, "sync": 0}
 
-    def submit(self, data, info=None, rows=None, out=None, tag=None):
+    def submit(self, data, info=None, rows=None, out=None, tag=None, plan=None, subseq_bytes=None):
         """data: the file's bytes (bytes-like); info: storage.jpeg_parse.parse(data) when the caller has it.  -> the
-        picture (rows y0 <= y < y1 of it), a uint8 device tensor, valid in stream order."""
+        picture (rows y0 <= y < y1 of it), a uint8 device tensor, valid in stream order.  plan, subseq_bytes: the
+        kernel, as hip.jpeg_decode takes them (None: by the file's restart interval; subseq_bytes is then left unused by a
+        file that the rule gives to 'interval')."""
         from storage import jpeg_parse
         if info is None:
             info = jpeg_parse.parse(data)
@@ -122,7 +125,13 @@ class DeviceMjpgDecoder:
         if n > self._host[s].numel():             # a file that outgrows its pinned slot grows the slot
             self._host[s] = torch.empty(n + n // 4, dtype=torch.uint8).pin_memory()
         self._host[s].numpy()[:n] = np.frombuffer(data, np.uint8)
-        rgb, status = self._hip.jpeg_decode(self._host[s][:n], rows=rows, out=out, device=self._device, info=info)
+        if plan is None:
+            plan = jpeg_parse.decode_plan(info)
+            if plan == "interval":
+                subseq_bytes = None               # as hip.jpeg_decode(plan=None) does: it raises for a named 'interval' alone
+        rgb, status = self._hip.jpeg_decode(self._host[s][:n], rows=rows, out=out, device=self._device, info=info,
+                                            plan=plan, subseq_bytes=subseq_bytes)
+        self.stats[plan] += 1
         self._status[s].copy_(status, non_blocking=True)
         self._event[s] = torch.cuda.Event()
         self._event[s].record()

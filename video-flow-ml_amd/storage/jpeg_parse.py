@@ -199,6 +199,14 @@ def huffman_lookup(table):
     return limit, offset
 
 
+def decode_plan(info):
+    """The device kernel a file gets: 'interval' - one restart interval per wave - when an
+    interval holds at most one MCU row of MCUs, as in this project's own files; 'sync' - the self-synchronising decoder,
+    one lane per subsequence of the scan - when it holds more: Ri = 0 (Pillow, OpenCV, ffmpeg) or Ri above a row."""
+    ri = info.restart_interval
+    return "sync" if ri == 0 or ri > info.mcu_grid[1] else "interval"
+
+
 TABLE_INTS = 8 + 4 * 96
 
 

@@ -21,40 +21,18 @@
 // at most 64 symbols of at most 31 bits (less than the 320 bytes staged ahead), a coefficient index is checked against
 // 63 before it is used, table indices are masked to the table.  What is wrong ends in the status cell, and nothing is
 // written outside the workspace and the output rows.
-#include "vfml_common.h"
+// jpeg_decode_sync.hip is the same decoder with another entropy stage (a lane per subsequence of the scan, for files
+// whose intervals are long or missing); it launches count / place and transform / colour through jpeg_decode_common.h.
+#include "jpeg_decode_common.h"
+
+using namespace vfml_jpeg;
 
 namespace {
 
 #include "jpeg_tables.inc"
 
-constexpr int kChunk = 4096;              // bytes of the scan per workgroup of the marker kernels
-constexpr int kChunkThreads = 256;        // 16 bytes each
 constexpr int kRing = 1024;               // bytes of an interval staged in LDS (a power of two)
 constexpr int kStageAhead = 320;          // staged before a block: 64 symbols of 31 bits are 248 bytes, + the bit buffer
-constexpr int kTableInts = 8 + 4 * 96;
-
-enum { kErrCount = 1, kErrSequence = 2, kErrCode = 4, kErrIndex = 8, kErrData = 16 };
-
-struct DecArgs {
-  const unsigned char* scan;
-  unsigned n;                             // bytes of the scan
-  int h, w, rows, cols;                   // picture; MCU rows, MCUs per row
-  int ri, nint;                           // MCUs per interval (the whole picture when the file's Ri is 0), intervals
-  const unsigned char* qt;                // [3][64] natural order
-  const int* tables;                      // [kTableInts]
-  int y0, y1;                             // output rows
-  int int0;                               // first interval that is decoded
-  int mrow0, mrows;                       // MCU rows that are transformed
-  unsigned* bcount;                       // [chunks] markers per chunk
-  unsigned* mpos;                         // [nint - 1] offset of the marker behind interval i
-  short* coef;                            // [MCUs][6][64] natural order
-  unsigned char *py, *pcb, *pcr;          // planes [16 rows][16 cols], [8 rows][8 cols] x 2
-  unsigned char* rgb;                     // row y0
-  int64_t stride;
-  int* status;
-};
-
-__host__ __device__ inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 // ---- markers -----------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool is_rst(const DecArgs& a, unsigned p) {
@@ -383,28 +361,18 @@ __global__ __launch_bounds__(256) void jpeg_dec_colour_kernel(const DecArgs a) {
   }
 }
 
-struct DecLayout {
-  int rows, cols;
-  int64_t chunks, bcount, mpos, coef, py, pcb, pcr, bytes;
-};
+}  // namespace
 
-bool dec_layout(int h, int w, int64_t scan_bytes, DecLayout& L) {
-  if (h < 1 || w < 1 || h > 65535 || w > 65535 || scan_bytes < 0 || scan_bytes > 0x7FFFFFFFll) return false;
-  L.rows = (h + 15) / 16, L.cols = (w + 15) / 16;
-  const int64_t nmcu = (int64_t)L.rows * L.cols;
-  L.chunks = scan_bytes > 0 ? (scan_bytes + kChunk - 1) / kChunk : 1;
-  int64_t at = 0;
-  L.bcount = at, at += align256(L.chunks * 4);
-  L.mpos = at, at += align256(nmcu * 4);                        // Ri = 1: a marker per MCU
-  L.coef = at, at += align256(nmcu * 6 * 64 * 2);
-  L.py = at, at += align256(nmcu * 256);
-  L.pcb = at, at += align256(nmcu * 64);
-  L.pcr = at, at += align256(nmcu * 64);
-  L.bytes = at;
-  return true;
+void vfml_jpeg::dec_launch_markers(const DecArgs& a, unsigned chunks, hipStream_t s) {
+  hipLaunchKernelGGL(jpeg_dec_count_kernel, dim3(chunks), dim3(kChunkThreads), 0, s, a);
+  hipLaunchKernelGGL(jpeg_dec_place_kernel, dim3(chunks), dim3(kChunkThreads), 0, s, a);
 }
 
-}  // namespace
+void vfml_jpeg::dec_launch_picture(const DecArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(jpeg_dec_transform_kernel, dim3((unsigned)((a.mrows * a.cols + 3) / 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((a.w + 1) / 2 + 255) / 256), (unsigned)(a.y1 - a.y0)),
+                     dim3(256), 0, s, a);
+}
 
 extern "C" int64_t vfml_jpeg_decode_workspace_bytes(int h, int w, int64_t scan_bytes) {
   DecLayout L;
@@ -438,13 +406,8 @@ extern "C" int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_byte
   a.coef = reinterpret_cast<short*>(ws + L.coef);
   a.py = ws + L.py, a.pcb = ws + L.pcb, a.pcr = ws + L.pcr;
   a.rgb = rgb, a.stride = row_stride, a.status = status;
-  // the MCU rows the window needs: its luma rows and the chroma rows the triangle filter reads
-  const int ch = (h + 1) / 2;
-  const int c0 = (y0 >> 1) - 1 > 0 ? (y0 >> 1) - 1 : 0;
-  const int c1 = ((y1 - 1) >> 1) + 1 < ch - 1 ? ((y1 - 1) >> 1) + 1 : ch - 1;
-  const int mlo = y0 / 16 < c0 / 8 ? y0 / 16 : c0 / 8;
-  const int mhi = (y1 - 1) / 16 > c1 / 8 ? (y1 - 1) / 16 : c1 / 8;
-  a.mrow0 = mlo, a.mrows = mhi - mlo + 1;
+  dec_window(a, h, y0, y1);
+  const int mlo = a.mrow0, mhi = a.mrow0 + a.mrows - 1;
   int ilo = 0, ihi = a.nint - 1;          // intervals are skipped when each is a whole number of MCU rows
   if (restart_interval > 0 && restart_interval % L.cols == 0) {
     const int k = restart_interval / L.cols;
@@ -452,11 +415,8 @@ extern "C" int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_byte
   }
   a.int0 = ilo;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(jpeg_dec_count_kernel, dim3((unsigned)L.chunks), dim3(kChunkThreads), 0, s, a);
-  hipLaunchKernelGGL(jpeg_dec_place_kernel, dim3((unsigned)L.chunks), dim3(kChunkThreads), 0, s, a);
+  dec_launch_markers(a, (unsigned)L.chunks, s);
   hipLaunchKernelGGL(jpeg_dec_entropy_kernel, dim3((unsigned)(ihi - ilo + 1)), dim3(64), 0, s, a);
-  hipLaunchKernelGGL(jpeg_dec_transform_kernel, dim3((unsigned)((a.mrows * L.cols + 3) / 4)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((w + 1) / 2 + 255) / 256), (unsigned)(y1 - y0)), dim3(256), 0,
-                     s, a);
+  dec_launch_picture(a, s);
   return vfml_check_launch("vfml_jpeg_decode_rgb");
 }

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -73,7 +73,8 @@ def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libvfml_hip.so (in-tree). Cross-compiles without a GPU."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "vfml_common.h"), os.path.join(CSRC, "conv_split_common.h"),
-            os.path.join(CSRC, "jet_table.inc"), os.path.join(CSRC, "jpeg_tables.inc"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
+            os.path.join(CSRC, "jet_table.inc"), os.path.join(CSRC, "jpeg_tables.inc"), os.path.join(CSRC, "jpeg_decode_common.h"),
+            os.path.join(CSRC, "jpeg_sync_steps.h"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(
             os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -191,6 +192,10 @@ def lib():
     L.vfml_jpeg_decode_workspace_bytes.argtypes = [c_int, c_int, c_int64]
     L.vfml_jpeg_decode_rgb.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                        c_void_p, c_int64, c_void_p, c_void_p]
+    L.vfml_jpeg_decode_sync_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_decode_sync_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int]
+    L.vfml_jpeg_decode_rgb_sync.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -210,6 +215,7 @@ EXPORTS = [
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
     "vfml_jpeg_decode_workspace_bytes", "vfml_jpeg_decode_rgb",
+    "vfml_jpeg_decode_sync_workspace_bytes", "vfml_jpeg_decode_rgb_sync",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -1089,7 +1095,26 @@ def _jpeg_decode_tables(info, device):
     return got
 
 
-def jpeg_decode(data, rows=None, out=None, device=None, info=None):
+JPEG_SUBSEQ_BYTES = 128     # bytes of the scan per lane of the 'sync' plan (not measured yet)
+
+
+def jpeg_subseq_bytes(scan_bytes):
+    """The subsequence size jpeg_decode(plan='sync', subseq_bytes=None) uses for a scan: JPEG_SUBSEQ_BYTES, doubled (up
+    to 1024) while the scan would hold more than 65536 subsequences - the chain kernel walks the groups of 256 in
+    series on one workgroup, so their number is kept to a few hundred wherever the size allows it."""
+    sub = JPEG_SUBSEQ_BYTES
+    while sub < 1024 and int(scan_bytes) > sub << 16:
+        sub <<= 1
+    return sub
+
+
+def jpeg_decode_plan(info):
+    """'interval' or 'sync': the kernel jpeg_decode(plan=None) picks for a parsed file (storage.jpeg_parse.decode_plan)."""
+    from storage import jpeg_parse
+    return jpeg_parse.decode_plan(info)
+
+
+def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, subseq_bytes=None):
     """A baseline JPEG file -> (rgb, status): the picture, uint8 device tensor [H,W,3], decoded on the device byte for
     byte as libjpeg (Pillow) decodes it (vfml_jpeg_decode_rgb, DESIGN.md section 13: stream-ordered, no
     synchronisation once the file's tables are on the device, see _jpeg_decode_tables), and the int32 device cell [1] that holds 0 or the error bits of a damaged scan
@@ -1100,7 +1125,15 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None):
     rows=(y0, y1): rows y0 <= y < y1 of the picture alone ([y1-y0,W,3]); with one or more whole MCU rows per restart
     interval the other intervals are not read.  out: a uint8 device tensor [rows,W,3] with contiguous pixels and a row
     stride of at least 3 W (a row slice of a larger buffer) that receives the picture.  The workspace is kept per
-    device, picture size and stream."""
+    device, picture size, plan and stream.
+    plan: 'interval' (vfml_jpeg_decode_rgb: a wave per restart interval), 'sync' (vfml_jpeg_decode_rgb_sync, section
+    13.1: a lane per subseq_bytes of the scan, whatever the restart interval) or None: jpeg_decode_plan(info).  Both
+    give the same bytes.  subseq_bytes: a power of two 16..1024, None: jpeg_subseq_bytes of the scan's size rounded up
+    to a power of two, as the workspace is (128 up to 8 MiB)."""
+    if plan not in (None, "interval", "sync"):
+        raise ValueError(f"jpeg_decode: plan {plan!r}; 'interval', 'sync' or None")
+    if subseq_bytes is not None and plan == "interval":
+        raise ValueError("jpeg_decode: subseq_bytes belongs to plan='sync'")
     from storage import jpeg_parse
     if torch.is_tensor(data):
         if info is None:
@@ -1138,15 +1171,30 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None):
     scan = data[s0:s1].to(device, non_blocking=True)
     # the workspace grows with the scan in powers of two, so the frames of a stream share one
     cap = 1 << max(12, int(s1 - s0 - 1).bit_length()) if s1 > s0 else 4096
-    need = int(L.vfml_jpeg_decode_workspace_bytes(h, w, cap))
+    if plan is None:
+        plan = jpeg_parse.decode_plan(info)
+    sync = plan == "sync"
+    sub = jpeg_subseq_bytes(cap) if subseq_bytes is None else int(subseq_bytes)
+    if sync and (sub < 16 or sub > 1024 or sub & (sub - 1)):
+        raise ValueError(f"jpeg_decode: subseq_bytes {sub}; a power of two 16..1024")
+    need = int(L.vfml_jpeg_decode_sync_workspace_bytes(h, w, cap, sub) if sync else
+               L.vfml_jpeg_decode_workspace_bytes(h, w, cap))
     if need == 0:
         raise ValueError(f"jpeg_decode: picture {w}x{h} with a scan of {s1 - s0} bytes is too large")
-    key = (device.index, h, w, torch.cuda.current_stream(device).cuda_stream)
+    key = (device.index, h, w, torch.cuda.current_stream(device).cuda_stream) + ((sub,) if sync else ())
     ws = _JPEG_DEC_WS.get(key)
     if ws is None or ws.numel() < need:
         ws = _JPEG_DEC_WS[key] = torch.empty(need, dtype=torch.uint8, device=device)
     qt, tables = _jpeg_decode_tables(info, device)
     status = torch.empty(1, dtype=torch.int32, device=device)
+    if sync:
+        with torch.cuda.device(device):
+            _check(L.vfml_jpeg_decode_rgb_sync(c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0,
+                                               h, w, int(info.restart_interval), c_void_p(qt.data_ptr()),
+                                               c_void_p(tables.data_ptr()), y0, y1, sub, c_void_p(ws.data_ptr()),
+                                               c_void_p(out.data_ptr()), stride, c_void_p(status.data_ptr()), _stream()),
+                   "vfml_jpeg_decode_rgb_sync")
+        return out, status
     with torch.cuda.device(device):
         _check(L.vfml_jpeg_decode_rgb(c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0, h, w,
                                       int(info.restart_interval), c_void_p(qt.data_ptr()), c_void_p(tables.data_ptr()),
