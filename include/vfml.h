@@ -30,7 +30,7 @@ extern "C" {
 /* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3, vfml_resize_u8 and the vfml_jpeg_*
  * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
  * the number did not move. */
-#define VFML_ABI_VERSION 25
+#define VFML_ABI_VERSION 26
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
 enum {
@@ -144,6 +144,14 @@ enum { VFML_CONV_SWAP_CROSS = 1,
        VFML_CONV_PER_TAP = 16 };
 
 int vfml_conv2d(const vfml_conv_desc* d, void* stream);
+
+/* The kernel the same vfml_conv2d / vfml_conv2d_split call would launch, as a profiler prints it (for instance
+ * "conv_gemm_dma_kernel<2, 1, 2, 2, false, true, false, 3, true, false>"), written to buf[len]: the call is validated and
+ * planned, nothing is launched.  A descriptor the launching call rejects is rejected here with the same error.  Needs
+ * no GPU: pointers are compared and checked for alignment, never followed. */
+int vfml_conv2d_variant(const vfml_conv_desc* d, char* buf, int len);
+int vfml_conv2d_split_variant(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
+                              int in_fmt, int out_fmt, int aux_fmt, int k_order, char* buf, int len);
 
 /* Same contract on the f16 matrix cores with fp32-grade accuracy ("split-f16": x = hi + lo with
  * hi = f16(x), lo = f16(x - hi); a*b ~= ah*bh + ah*bl + al*bh, 3 MFMAs per product, ~22 mantissa

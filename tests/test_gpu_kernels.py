@@ -1536,3 +1536,63 @@ def test_stem_kernel_matches_the_general_convolution(gpu, n, H, W):
             torch.cuda.synchronize()
             us = e0.elapsed_time(e1) / 20 * 1e3
             print(f"stem 1080p: {name} {us:.1f} us per launch = {2.0 * hw * 196 * 64 / us / 1e6:.1f} TFLOP/s algorithmic")
+
+
+def test_profile_names_each_launch_as_the_library_plans_it(gpu):
+    """hip.profile_begin() .. profile_end() around one call per kernel family: the outputs are bitwise those of the same
+    calls outside profiling, the keys are the names vfml_conv2d_variant / vfml_conv2d_split_variant give for the same
+    descriptors (the library's own plan, not a copy of it), they split as bench.py's roofline leg splits them, and the
+    launch / FLOP / byte sums are the accounting of hip.conv2d."""
+    from vfml import hip
+    from vfml.weights import pack_conv_weight
+    g = torch.Generator().manual_seed(5)
+
+    def call(family, targs, nm_pos, cin, cout, k, h, w, precision, src16, cblock=False):
+        x = torch.randn(1, cin, h, w, generator=g)
+        wt = torch.randn(cout, cin, k, k, generator=g) / math.sqrt(cin * k * k)
+        src = nhwc(x)
+        if src16:
+            src = torch.empty(h * w * cin, device=gpu)
+            hip.to_s16(nhwc(x), h * w, cin, cin, src, cin)
+        return dict(family=family, targs=targs, nm_pos=nm_pos, cin=cin, cout=cout, k=k, h=h, w=w, src=src,
+                    fmt=hip.FMT_S16 if src16 else hip.FMT_F32,
+                    weight=as_weight(pack_conv_weight(wt, cblock=cblock), cout, precision, order=int(cblock)))
+
+    calls = [
+        call("conv_gemm_kernel", ["64", "2", "2"], None, 32, 64, 1, 16, 16, "f32", False),
+        call("conv_gemm_split_kernel", None, 5, 32, 128, 1, 16, 16, "f16x3", False),
+        call("conv_gemm_dma_kernel", ["2", "1", "2", "2", "false"], 7, 64, 64, 1, 16, 16, "f16x3", True),
+        call("conv_gemm_dma_kernel", ["2", "2", "2", "2", "true"], 7, 64, 1024, 1, 16, 16, "f16x3", True),      # GEMM form, kp 64
+        # 3x3 64 -> 64 on 336 x 336: 441 tiles of 256 rows, the smallest map past the shared-stage kernel's 85 % fill rule
+        call("conv_gemm_tapx_kernel", ["2", "2", "4", "1"], 4, 64, 64, 3, 336, 336, "f16x3", True, cblock=True),
+    ]
+
+    def run(c, **kw):
+        out = torch.full((c["h"] * c["w"] * c["cout"],), float("nan"), device=gpu)
+        r = hip.conv2d(c["src"], c["cin"], c["cin"], 1, c["h"], c["w"], c["weight"], None, c["cout"], c["k"], c["k"], out, c["cout"],
+                       pad_h=c["k"] // 2, pad_w=c["k"] // 2, in_fmt=c["fmt"], **kw)
+        return r if kw else out
+
+    plain = [run(c) for c in calls]
+    names = [run(c, variant_only=True) for c in calls]
+    assert len(set(names)) == len(calls), names
+    hip.profile_begin()
+    profiled = [run(c) for c in calls]
+    prof = hip.profile_end()
+    for a, b in zip(plain, profiled):
+        assert torch.isfinite(a).all() and torch.equal(a, b)
+    assert sorted(prof) == sorted(names)
+    for c, name in zip(calls, names):
+        assert name.startswith(c["family"] + "<"), name
+        targs = [t.strip() for t in name[name.index("<") + 1:name.rindex(">")].split(",")]      # (bench.py's split)
+        if c["targs"]:
+            assert targs[:len(c["targs"])] == c["targs"], name
+        if c["nm_pos"] is not None:
+            assert int(targs[c["nm_pos"]]) == 3, name
+        m, kk = c["h"] * c["w"], c["k"] * c["k"] * c["cin"]
+        want = {"launches": 1, "flops": 2.0 * m * kk * c["cout"], "bytes": 4.0 * (m * c["cin"] + m * c["cout"] + c["cout"] * kk)}
+        d = prof[name]
+        assert sorted(d) == ["bytes", "flops", "launches", "ms", "shapes"] and d["ms"] > 0
+        assert list(d["shapes"]) == [f"{c['k']}x{c['k']} {c['cin']}->{c['cout']}"]
+        for t in (d, d["shapes"][f"{c['k']}x{c['k']} {c['cin']}->{c['cout']}"]):
+            assert {k: t[k] for k in want} == want, (name, t)

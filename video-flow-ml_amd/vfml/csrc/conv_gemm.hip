@@ -14,6 +14,7 @@
 //     k-permutation is the same for A and B, so the sum over k is unchanged.
 // Two LDS buffers, one barrier per K step; next tile's global loads are issued before the
 // MFMAs of the current one.
+#include <stdio.h>
 #include "vfml_common.h"
 
 namespace {
@@ -219,16 +220,16 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(const ConvArgs a) {
 }
 
 template <int BN, int WM, int WN>
-int launch(const ConvArgs& a, hipStream_t s) {
+int launch(ConvArgs& a, hipStream_t s) {
+  a.ntiles = (a.cout + BN - 1) / BN;
   constexpr size_t lds = 2 * (KG * (BM + 1) + KG * (BN + 1)) * sizeof(f32x4);
   if (const int rc = vfml_lds_cap(reinterpret_cast<const void*>(&conv_gemm_kernel<BN, WM, WN>), (int)lds, "vfml_conv2d")) return rc;
   hipLaunchKernelGGL((conv_gemm_kernel<BN, WM, WN>), dim3(a.mtiles * a.ntiles), dim3(256), lds, s, a);
   return vfml_check_launch("vfml_conv2d");
 }
 
-}  // namespace
-
-extern "C" int vfml_conv2d(const vfml_conv_desc* d, void* stream) {
+// validate the descriptor and fill the kernel's argument block
+int conv_fill(const vfml_conv_desc* d, ConvArgs& a) {
   VFML_REQUIRE(d != nullptr, "vfml_conv2d: null descriptor");
   VFML_REQUIRE(d->out_t == nullptr && d->flags == 0, "vfml_conv2d: out_t / flags are vfml_conv2d_split (GEMM form) features");
   VFML_REQUIRE(d->stats_part == nullptr, "vfml_conv2d: stats_part is a vfml_conv2d_split feature");
@@ -254,7 +255,6 @@ extern "C" int vfml_conv2d(const vfml_conv_desc* d, void* stream) {
   if (d->epilogue == VFML_EPI_GRU_Q) VFML_REQUIRE(d->aux0 && d->aux1, "vfml_conv2d: GRU_Q needs aux0 and aux1");
   VFML_REQUIRE(d->epilogue >= VFML_EPI_NONE && d->epilogue <= VFML_EPI_ADD_AUX, "vfml_conv2d: bad epilogue");
 
-  ConvArgs a;
   a.in0 = d->in0; a.in1 = two ? d->in1 : d->in0;
   a.weight = d->weight; a.bias = d->bias; a.aux0 = d->aux0; a.aux1 = d->aux1; a.out = d->out;
   a.addend = d->addend; a.ld_addend = d->ld_addend;
@@ -267,14 +267,55 @@ extern "C" int vfml_conv2d(const vfml_conv_desc* d, void* stream) {
   a.ldo = d->ldo; a.ld_aux0 = d->ld_aux0; a.ld_aux1 = d->ld_aux1;
   a.epilogue = d->epilogue; a.split = d->split; a.out_scale = d->out_scale;
   a.mtiles = (a.M + BM - 1) / BM;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (d->cout > 64) {
-    a.ntiles = (d->cout + 127) / 128;
-    return launch<128, 2, 2>(a, s);
-  } else if (d->cout > 32) {
-    a.ntiles = 1;
-    return launch<64, 2, 2>(a, s);
-  }
-  a.ntiles = 1;
-  return launch<32, 4, 1>(a, s);
+  return 0;
+}
+
+// Which instantiation runs a call: by output width alone (a row of the table below, or none)
+struct ConvPlan {
+  int bn, wm, wn;
+};
+ConvPlan plan_conv(const ConvArgs& a) {
+  if (a.cout > 64) return {128, 2, 2};
+  if (a.cout > 32) return {64, 2, 2};
+  return {32, 4, 1};
+}
+
+struct ConvVariant {
+  ConvPlan key;
+  int (*launch)(ConvArgs& a, hipStream_t s);     // sets a.ntiles
+};
+#define CONV_ROW(...) {{__VA_ARGS__}, &launch<__VA_ARGS__>}
+const ConvVariant CONV_VARIANTS[] = {CONV_ROW(128, 2, 2), CONV_ROW(64, 2, 2), CONV_ROW(32, 4, 1)};
+#undef CONV_ROW
+
+// validate + fill, plan, and the plan's row
+int conv_prepare(const vfml_conv_desc* d, ConvArgs& a, const ConvVariant*& row) {
+  if (const int rc = conv_fill(d, a)) return rc;
+  const ConvPlan p = plan_conv(a);
+  for (const ConvVariant& v : CONV_VARIANTS)
+    if (v.key.bn == p.bn && v.key.wm == p.wm && v.key.wn == p.wn) {
+      row = &v;
+      return 0;
+    }
+  vfml_set_error("vfml_conv2d: no such variant: conv_gemm_kernel<%d, %d, %d>", p.bn, p.wm, p.wn);
+  return 1;
+}
+
+}  // namespace
+
+extern "C" int vfml_conv2d(const vfml_conv_desc* d, void* stream) {
+  ConvArgs a;
+  const ConvVariant* row;
+  if (const int rc = conv_prepare(d, a, row)) return rc;
+  return row->launch(a, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int vfml_conv2d_variant(const vfml_conv_desc* d, char* buf, int len) {
+  VFML_REQUIRE(buf && len > 0, "vfml_conv2d_variant: no buffer");
+  ConvArgs a;
+  const ConvVariant* row;
+  if (const int rc = conv_prepare(d, a, row)) return rc;
+  VFML_REQUIRE(snprintf(buf, len, "conv_gemm_kernel<%d, %d, %d>", row->key.bn, row->key.wm, row->key.wn) < len,
+               "vfml_conv2d_variant: the name needs more than %d bytes", len);
+  return 0;
 }

@@ -997,58 +997,9 @@ int launch_dma_k(SplitArgs& a, hipStream_t s) {
   return vfml_check_launch("vfml_conv2d_split");
 }
 
-template <int TM, int TN, int WM, int WN>
-int launch_dma(SplitArgs& a, hipStream_t s) {
-  if (a.direct) {   // (128 x 128: the one persistent tile shape that does not spill)
-    // The GEMM forms stay on 32x32x16: measured with 16x16x32 (an experiment since removed) the 32400^2 volume gains 4 %, the
-    // MemFlow read-out 2 %, the 1080p field nothing - and v_mfma_f32_16x16x32_f16 is NOT symmetric in its operands to the
-    // last bit (a volume stored transposed and the reverse problem computed directly differ in the last ulp, which the
-    // 32x32x16 form never does: tests/test_gpu_kernels.py::test_wide_gemm_with_transposed_second_output), so the
-    // sliding job's "volume + transposed volume from one pass" would stop being bit-identical to from-scratch fields.
-    if (a.out_h16) {      // VFML_FMT_F16 outputs (host: implies fastk)
-      if (a.cswap) return launch_dma_k<2, 2, 2, 2, true, true, true, 3, false, true>(a, s);
-      if (a.nm == 2) return launch_dma_k<2, 2, 2, 2, true, true, false, 2, false, true>(a, s);
-      if (a.nm == 1) return launch_dma_k<2, 2, 2, 2, true, true, false, 1, false, true>(a, s);
-      if (a.nm == 5) return launch_dma_k<2, 2, 2, 2, true, true, false, 5, false, true>(a, s);
-      a.nm = 3;
-      return launch_dma_k<2, 2, 2, 2, true, true, false, 3, false, true>(a, s);
-    }
-    if (a.cswap) return launch_dma_k<2, 2, 2, 2, true, true, true>(a, s);     // (host: cswap implies fastk and nm == 3)
-    if (a.fastk && a.nm == 2) return launch_dma_k<2, 2, 2, 2, true, true, false, 2>(a, s);  // (host: bhi implies fastk, nm <= 2)
-    if (a.fastk && a.nm == 1) return launch_dma_k<2, 2, 2, 2, true, true, false, 1>(a, s);
-    if (a.fastk && a.nm == 5) return launch_dma_k<2, 2, 2, 2, true, true, false, 5>(a, s);
-    if (a.nm == 2 && a.bhi) { vfml_set_error("vfml_conv2d_split: a weight operand without lo plane needs the uniform-step GEMM form"); return 1; }
-    a.nm = 3;       // (the general-loader GEMM form exists at full precision only: never less accurate than asked)
-    return a.fastk ? launch_dma_k<2, 2, 2, 2, true, true>(a, s) : launch_dma_k<2, 2, 2, 2, true, false>(a, s);
-  }
-  if constexpr (WM * WN == 4) {   // the shapes the dispatcher picks by itself: 16x16x32 MFMAs (MF16)
-    // (measured against the 32x32x16 shape for the full-precision uniform-step variants: MF16 is 9-12 % faster on the
-    // 1080p update-block shapes - the chip holds a higher clock on it)
-    if constexpr (TM * TN >= 2) {
-      if (a.fastk) {
-        if (a.nm == 2) return launch_dma_k<TM, TN, WM, WN, false, true, false, 2, true>(a, s);
-        if (a.nm == 4) return launch_dma_k<TM, TN, WM, WN, false, true, false, 4, true>(a, s);
-        if (a.nm == 1) return launch_dma_k<TM, TN, WM, WN, false, true, false, 1, true>(a, s);
-        if (a.nm == 5) return launch_dma_k<TM, TN, WM, WN, false, true, false, 5, true>(a, s);
-        return launch_dma_k<TM, TN, WM, WN, false, true, false, 3, true>(a, s);
-      }
-    }
-    if (a.nm == 5) {     // (cannot happen: the host picks 64-channel steps only where a uniform-step variant exists)
-      vfml_set_error("vfml_conv2d_split: no 64-channel-step variant for this tile shape");
-      return 1;
-    }
-    a.fastk = 0; a.abias = 0;
-    if (a.nm == 2) return launch_dma_k<TM, TN, WM, WN, false, false, false, 2, true>(a, s);
-    if (a.nm == 4) return launch_dma_k<TM, TN, WM, WN, false, false, false, 4, true>(a, s);
-    if (a.nm == 1) return launch_dma_k<TM, TN, WM, WN, false, false, false, 1, true>(a, s);
-    return launch_dma_k<TM, TN, WM, WN, false, false, false, 3, true>(a, s);
-  }
-  vfml_set_error("vfml_conv2d_split: no such tile shape");
-  return 1;
-}
-
 template <int BN, int WM, int WN, bool BIGC, bool IN16, int NM>
-int launch_nm(const SplitArgs& a, hipStream_t s) {
+int launch_nm(SplitArgs& a, hipStream_t s) {
+  a.ntiles = (a.cout + BN - 1) / BN;
   constexpr size_t stage = 2 * 2 * (KG * (BM + 2) + KG * (BN + 2)) * 16;
   constexpr size_t ctile = (size_t)BM * (BN + 4) * 4;
   constexpr size_t lds = stage > ctile ? stage : ctile;
@@ -1059,13 +1010,38 @@ int launch_nm(const SplitArgs& a, hipStream_t s) {
   return vfml_check_launch("vfml_conv2d_split");
 }
 
-template <int BN, int WM, int WN, bool BIGC, bool IN16>
-int launch(const SplitArgs& a, hipStream_t s) {
-  if (a.nm == 1) return launch_nm<BN, WM, WN, BIGC, IN16, 1>(a, s);
-  if (a.nm == 2) return launch_nm<BN, WM, WN, BIGC, IN16, 2>(a, s);
-  if (a.nm == 4) return launch_nm<BN, WM, WN, BIGC, IN16, 4>(a, s);
-  return launch_nm<BN, WM, WN, BIGC, IN16, 3>(a, s);
-}
+// The instantiations that exist, one table per kernel family (what runs a call: vfml_detail::plan_split).
+#define REG_ROW(...) {vfml_detail::reg_plan(__VA_ARGS__), &launch_nm<__VA_ARGS__>}
+#define REG_ROWS(BN, WM, WN, BIGC) \
+  REG_ROW(BN, WM, WN, BIGC, false, 1), REG_ROW(BN, WM, WN, BIGC, false, 2), REG_ROW(BN, WM, WN, BIGC, false, 4), REG_ROW(BN, WM, WN, BIGC, false, 3)
+const SplitVariant REG_VARIANTS[] = {REG_ROWS(128, 2, 2, true), REG_ROWS(128, 2, 2, false), REG_ROWS(64, 2, 2, true),
+                                     REG_ROWS(64, 2, 2, false), REG_ROWS(32, 4, 1, true), REG_ROWS(32, 4, 1, false)};
+
+//              TM TN WM WN  PERSIST FASTK CSWAP NM MF16 H16
+#define DMA_ROW(...) {vfml_detail::dma_plan(__VA_ARGS__), &launch_dma_k<__VA_ARGS__>}
+#define DMA_GENERAL_ROWS(TM, TN, WM, WN) \
+  DMA_ROW(TM, TN, WM, WN, false, false, false, 2, true, false), DMA_ROW(TM, TN, WM, WN, false, false, false, 4, true, false), \
+  DMA_ROW(TM, TN, WM, WN, false, false, false, 1, true, false), DMA_ROW(TM, TN, WM, WN, false, false, false, 3, true, false)
+#define DMA_PER_TAP_ROWS(TM, TN, WM, WN) \
+  DMA_ROW(TM, TN, WM, WN, false, true, false, 2, true, false), DMA_ROW(TM, TN, WM, WN, false, true, false, 4, true, false), \
+  DMA_ROW(TM, TN, WM, WN, false, true, false, 1, true, false), DMA_ROW(TM, TN, WM, WN, false, true, false, 5, true, false), \
+  DMA_ROW(TM, TN, WM, WN, false, true, false, 3, true, false), DMA_GENERAL_ROWS(TM, TN, WM, WN)
+const SplitVariant DMA_VARIANTS[] = {
+    // the GEMM form: VFML_FMT_F16 outputs, then plain f32
+    DMA_ROW(2, 2, 2, 2, true, true, true, 3, false, true), DMA_ROW(2, 2, 2, 2, true, true, false, 2, false, true),
+    DMA_ROW(2, 2, 2, 2, true, true, false, 1, false, true), DMA_ROW(2, 2, 2, 2, true, true, false, 5, false, true),
+    DMA_ROW(2, 2, 2, 2, true, true, false, 3, false, true),
+    DMA_ROW(2, 2, 2, 2, true, true, true, 3, false, false), DMA_ROW(2, 2, 2, 2, true, true, false, 2, false, false),
+    DMA_ROW(2, 2, 2, 2, true, true, false, 1, false, false), DMA_ROW(2, 2, 2, 2, true, true, false, 5, false, false),
+    DMA_ROW(2, 2, 2, 2, true, true, false, 3, false, false), DMA_ROW(2, 2, 2, 2, true, false, false, 3, false, false),
+    // 192 x 128, 128 x 192, 128 x 128, 128 x 64 (2 workgroups per CU), and 128 x 32 on the general loader only
+    DMA_PER_TAP_ROWS(3, 2, 2, 2), DMA_PER_TAP_ROWS(2, 3, 2, 2), DMA_PER_TAP_ROWS(2, 2, 2, 2), DMA_PER_TAP_ROWS(2, 1, 2, 2),
+    DMA_GENERAL_ROWS(1, 1, 4, 1)};
+#undef REG_ROW
+#undef REG_ROWS
+#undef DMA_ROW
+#undef DMA_GENERAL_ROWS
+#undef DMA_PER_TAP_ROWS
 
 // f32 [rows][k] (row stride ld) * scale -> hi/lo f16 planes [rows][kp], zero padded to kp
 __global__ void split_f16_kernel(const float* __restrict__ src, int64_t rows, int k, int ld, int kp, float scale,
@@ -1398,8 +1374,10 @@ __global__ void add_rows_kernel(float* __restrict__ out, const float* __restrict
 // narrowest plain-f32 output the GEMM form (a.direct) writes straight from its accumulators
 constexpr int DIRECT_MIN_COUT = 1024;
 
-extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
-                                 int in_fmt, int out_fmt, int aux_fmt, int k_order, void* stream) {
+// Step 1 of a call: validate the descriptor and fill the kernels' argument block (which kernel takes it is step 2:
+// vfml_detail::plan_split)
+static int split_fill(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale, int in_fmt, int out_fmt,
+                      int aux_fmt, int k_order, SplitArgs& a) {
   VFML_REQUIRE(d != nullptr, "vfml_conv2d_split: null descriptor");
   {
     const int pbits = d->flags & (VFML_CONV_MFMA2 | VFML_CONV_MFMA1 | VFML_CONV_MFMA2A);
@@ -1487,7 +1465,6 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
   if (d->epilogue == VFML_EPI_GRU_Q) VFML_REQUIRE(d->aux0 && d->aux1, "vfml_conv2d_split: GRU_Q needs aux0 and aux1");
   VFML_REQUIRE(d->epilogue >= VFML_EPI_NONE && d->epilogue <= VFML_EPI_ADD_AUX, "vfml_conv2d_split: bad epilogue");
 
-  SplitArgs a;
   a.wbase = nullptr; a.whi_off = a.wlo_off = a.bytesb = 0; a.korder = k_order; a.direct = 0; a.fastk = 0; a.abias = 0; a.src1_delta = 0; a.out_t = nullptr; a.ld_out_t = 0; a.cswap = 0; a.bhi = 0;
   a.stats_part = d->stats_part;
   a.ksplit = 1; a.out_k1 = nullptr; a.out_t_k1 = nullptr;
@@ -1528,184 +1505,159 @@ extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, cons
   a.out16 = out_fmt == VFML_FMT_S16;
   a.out_h16 = out_fmt == VFML_FMT_F16;
   a.aux16 = aux_fmt == VFML_FMT_S16;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const bool bigc = a.ctot >= BK;
-  // Tile width: 128 columns per workgroup unless 64-wide tiles use the machine better.  Efficiency
-  // model = (useful columns / padded columns) x (workgroups / slots of the last partial round) x a
-  // 0.7 handicap for the narrower tile (half the MFMAs per loaded A element; measured: 64-wide tiles lose more than the tail round gains on the 1080p shapes); 2 workgroups per CU.
-  int bn = d->cout > 64 ? 128 : (d->cout > 32 ? 64 : 32);
-  if (d->cout > 64) {
-    auto eff = [&](int w) {
-      const int nt = (d->cout + w - 1) / w;
-      const int64_t wg = (int64_t)a.mtiles * nt, slots = 512;
-      const int64_t rounds = (wg + slots - 1) / slots;
-      return ((double)d->cout / (nt * w)) * ((double)wg / (rounds * slots)) * (w == 64 ? 0.7 : 1.0);
-    };
-    if (eff(64) > eff(128)) bn = 64;
+  if (!in16) {
+    VFML_REQUIRE(!d->proj_out, "vfml_conv2d_split: proj_out is implemented for split-row (VFML_FMT_S16) sources only");
+    return 0;
   }
-  if (in16) {   // split-row sources: every slice is a multiple of 8 channels and >= one K step wide
-    // LDS-DMA kernel when both weight planes fit one descriptor window (< 1 GiB)
-    const char* ph = (const char*)w_hi;
-    const char* pl = bhi ? ph : (const char*)w_lo;
-    const char* wb = ph < pl ? ph : pl;
-    const int64_t ext = (ph < pl ? pl - ph : ph - pl) + (int64_t)d->cout * kp * 2;
-    // (a single plane may span up to 2 GiB: its lanes' out-of-range marker is 0x7ffffff0 instead of 1 GiB)
-    const bool dma_ok = bhi ? ext <= 0x7ffffff0ll : ext < (1ll << 30);
-    if (dma_ok) {   // every split-row source goes through the LDS-DMA kernel
-      a.wbase = wb; a.whi_off = (int)(ph - wb); a.wlo_off = (int)(pl - wb); a.bytesb = (int)ext;
-      a.bhi = bhi ? 1 : 0;
-      a.tilebase = tilebase;
-      {
-        const int64_t abias = ((int64_t)d->pad_h * d->w + d->pad_w) * d->ld0 * 4;
-        // (for a 1x1 convolution over whole 32-channel blocks the two K orders are the same bytes)
-        const bool cblock = k_order == VFML_KORDER_CBLOCK || k_order == VFML_KORDER_CBLOCK64 ||
-                            (a.pointwise && (d->c0 + d->c1) % BK == 0);
-        a.fastk = cblock && d->c0 % BK == 0 && (d->c0 + d->c1) % BK == 0 &&
-                  (!two || (d->ld1 == d->ld0 && a.d1off >= a.d0off)) && d->kh * d->kw <= 32 &&
-                  (int64_t)a.bytes0 + abias < (1ll << 31);
-        VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.fastk,
-                     "vfml_conv2d_split: VFML_KORDER_CBLOCK64 needs the uniform-step loader (one row stride for both sources, kh*kw <= 32)");
-        if (a.fastk) a.korder = VFML_KORDER_CBLOCK;
-        // one MFMA per product over whole 64-channel blocks: 64-channel steps of hi halves (NM 5) - for 1x1 kernels in
-        // any weight order (the K axis is the channel axis), else with the weights in 64-channel-block order
-        // (cout > 32: the 128 x 32 tile of narrower outputs has no uniform-step instantiation)
-        if (a.nm == 1 && a.fastk && d->c0 % 64 == 0 && (d->c0 + d->c1) % 64 == 0 && d->cout > 32 &&
-            (k_order == VFML_KORDER_CBLOCK64 || a.pointwise))
-          a.nm = 5;
-        VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.nm == 5, "vfml_conv2d_split: VFML_KORDER_CBLOCK64 weights need the 64-channel-step kernel");
-        a.abias = a.fastk ? (int)abias : 0;
-        a.src1_delta = two ? (a.d1off - a.d0off) * 4 : 0;
-      }
-      // (VFML_FMT_F16 outputs exist in this form only: any width)
-      a.direct = (d->epilogue == VFML_EPI_NONE || d->epilogue == VFML_EPI_RELU) && !d->addend &&
-                 (out_fmt == VFML_FMT_F32 || out_fmt == VFML_FMT_F16) && !d->stats_part &&
-                 (d->cout >= DIRECT_MIN_COUT || out_fmt == VFML_FMT_F16) && d->cout % 4 == 0 && d->ldo % 4 == 0 && vfml_aligned16(d->out) &&
-                 (!d->bias || vfml_aligned16(d->bias));
-      VFML_REQUIRE(out_fmt != VFML_FMT_F16 || (a.direct && a.fastk),
-                   "vfml_conv2d_split: VFML_FMT_F16 outputs are written by the GEMM form only (1x1 over whole 32-channel blocks, no "
-                   "addend / activation beyond ReLU, cout %% 4 == 0, ldo %% 4 == 0, 16-byte aligned out)");
-      if (d->flags & VFML_CONV_SWAP_CROSS) {
-        VFML_REQUIRE(a.direct && a.fastk, "vfml_conv2d_split: VFML_CONV_SWAP_CROSS is implemented by the GEMM form only "
-                                          "(1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024, cout %% 4 == 0)");
-        a.cswap = 1;
-      }
-      if (bhi)
-        VFML_REQUIRE(a.direct && a.fastk && !a.cswap, "vfml_conv2d_split: a weight operand without lo plane is implemented by the "
-                                                        "GEMM form only (1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024)");
-      if (d->out_t) {
-        VFML_REQUIRE(a.direct && a.fastk && a.pointwise && !d->bias && d->epilogue == VFML_EPI_NONE && a.M % 4 == 0 &&
-                     d->ld_out_t % 4 == 0 && d->ld_out_t >= a.M && vfml_aligned16(d->out_t),
-                     "vfml_conv2d_split: out_t needs the GEMM form (1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024, cout %% 4 == 0), no bias / "
-                     "epilogue, pixels %% 4 == 0, ld_out_t %% 4 == 0 and >= pixels, 16-byte alignment");
-        a.out_t = d->out_t; a.ld_out_t = d->ld_out_t;
-      }
-      // A GEMM with few tiles and a long K axis (the MemFlow read-out: 254 tiles of 128 x 128 on 512 resident slots, one
-      // workgroup per CU streaming 8 MB of its operand): two work items per tile, one per half of K, when the caller gave
-      // a workspace for the second half's sums
-      bool ksplit = false;
-      if (d->ksplit_ws) {
-        VFML_REQUIRE(vfml_aligned16(d->ksplit_ws), "vfml_conv2d_split: ksplit_ws must be 16-byte aligned");
-        const int64_t tiles = (int64_t)((a.M + 127) / 128) * ((d->cout + 127) / 128);
-        ksplit = a.direct && a.fastk && a.pointwise && out_fmt == VFML_FMT_F32 && !a.cswap && tiles <= 256 &&
-                 kp >= 4096;
-        if (ksplit) {     // (the workspace holds the primary output's shape, then - with out_t - the transposed one's)
-          a.ksplit = 2;
-          a.out_k1 = d->ksplit_ws;
-          a.out_t_k1 = d->ksplit_ws + (int64_t)a.M * d->ldo;
-        }
-      }
-      if (d->proj_out) {
-        // projection epilogue: what the kernel's slab routine is built for
-        VFML_REQUIRE(d->epilogue == VFML_EPI_RELU && !d->addend && !d->stats_part && !d->out_t && !a.direct,
-                     "vfml_conv2d_split: proj_out goes with VFML_EPI_RELU, no addend / stats_part / out_t");
-        VFML_REQUIRE(a.fastk && (a.nm == 3 || a.nm == 4) && d->cout % 128 == 0,
-                     "vfml_conv2d_split: proj_out needs the uniform-step loader (channel-block weight order, whole 32-channel "
-                     "blocks), the full split product or VFML_CONV_MFMA2A (which then holds for the projection too) and "
-                     "cout %% 128 == 0");
-        VFML_REQUIRE(d->proj_hi && d->proj_lo && d->proj_n > 0 && d->proj_n <= 48 && d->proj_n % 4 == 0 && d->proj_kp >= d->cout &&
-                         d->proj_kp % 8 == 0 && d->ld_proj >= d->proj_n && d->ld_proj % 4 == 0 && vfml_aligned16(d->proj_out) &&
-                         vfml_aligned16(d->proj_hi) && vfml_aligned16(d->proj_lo) && d->proj_scale > 0.f,
-                     "vfml_conv2d_split: proj_hi / proj_lo [proj_n <= 48, %% 4 == 0][proj_kp >= cout] f16 planes, ld_proj >= proj_n, "
-                     "16-byte alignment");
-        const char* ph2 = (const char*)d->proj_hi;
-        const char* pl2 = (const char*)d->proj_lo;
-        const int64_t plane = (int64_t)d->proj_n * d->proj_kp * 2;
-        VFML_REQUIRE(pl2 >= ph2 && (pl2 - ph2) + plane < (1ll << 30), "vfml_conv2d_split: proj_lo must follow proj_hi within 1 GiB");
-        a.proj_w = ph2; a.proj_lo_off = (int)(pl2 - ph2); a.proj_bytes = (int)((pl2 - ph2) + plane);
-        a.proj_n = d->proj_n; a.proj_kp = d->proj_kp; a.proj_inv = 1.0f / d->proj_scale;
-        a.proj_out = d->proj_out; a.ld_proj = d->ld_proj;
-      }
-      const char* tile_env = getenv("VFML_DMA_TILE");   // experiments / tests: "TM,TN,WM,WN" (read per call)
-      int cfg = d->cout > 32 ? 2122 : 1141;
-      if (d->cout > 64) {
-        // 192 x 128, 128 x 192, 128 x 128 or 128 x 64 tiles (two workgroups per CU each).  Cost model:
-        // (rounds over the 512 resident slots; a problem that does not fill them is one round, a longer one
-        // costs its fractional number of rounds because workgroups of the last round run less contended)
-        // x (MFMAs per tile / measured relative efficiency of the tile shape: fewer operand bytes per MFMA
-        // on the larger tiles).
-        auto cost = [&](int tbm, int tbn, double mf, double eff) {
-          const double tiles = (double)((a.M + tbm - 1) / tbm) * (double)((d->cout + tbn - 1) / tbn);
-          return (tiles > 512.0 ? tiles / 512.0 : 1.0) * mf / eff;
-        };
-        const double c3222 = cost(192, 128, 6.0, 1.0), c2322 = cost(128, 192, 6.0, 1.0), c2222 = cost(128, 128, 4.0, 0.93),
-                     c2122 = cost(128, 64, 2.0, 0.7);
-        cfg = 3222;
-        double best = c3222;
-        if (c2322 < best) { best = c2322; cfg = 2322; }
-        if (c2222 < best) { best = c2222; cfg = 2222; }
-        if (c2122 < best) { best = c2122; cfg = 2122; }
-        if (a.proj_out && cfg != 3222 && cfg != 2222) cfg = c3222 <= c2222 ? 3222 : 2222;    // (128-column tiles of four waves)
-      }
-      bool forced = false;
-      if (tile_env && d->cout > 32) {
-        int tm = 2, tn = 2, wm = 2, wn = 2;
-        sscanf(tile_env, "%d,%d,%d,%d", &tm, &tn, &wm, &wn);
-        const int want = tm * 1000 + tn * 100 + wm * 10 + wn;
-        // (2241 / 2341 exist in the shared-stage kernel only; narrower outputs keep their per-tap shapes otherwise)
-        if (d->cout > 64 || want == 2241 || want == 2341) { cfg = want; forced = true; }
-        VFML_REQUIRE(!a.proj_out || cfg == 3222 || cfg == 2222, "vfml_conv2d_split: proj_out runs on the 192 x 128 / 128 x 128 tiles (VFML_DMA_TILE)");
-      }
-      // stride-1 "same" convolutions with a filter row of 2..5 taps: one activation stage per (channel block, tap row),
-      // shared by the row's taps (conv_gemm_tapx.hip).  The three-MFMA calls on the 192 x 128 / 128 x 192 tiles keep the
-      // per-tap stages of conv_gemm_dma_kernel: there the two kernels run level.
-      if (!(d->flags & VFML_CONV_PER_TAP) && !a.proj_out) {
-        const int tcfg = vfml_detail::tapx_cfg(a, cfg, forced);
-        if (tcfg && (forced || a.nm == 5 || tcfg == 2241 || tcfg == 2341)) return vfml_detail::launch_tapx(a, tcfg, s);
-      }
-      if (a.ksplit == 2) {
-        // (the GEMM form is one tile shape; the partial sums of the second half of K are added once the launch is queued)
-        const int rc = launch_dma<2, 2, 2, 2>(a, s);
-        if (rc) return rc;
-        const int64_t quads = (int64_t)a.M * (d->cout / 4);
-        hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((quads + 255) / 256 < 65535 * 16 ? (quads + 255) / 256 : 65535 * 16)), dim3(256), 0, s,
-                           d->out, d->ksplit_ws, a.M, d->cout / 4, d->ldo);
-        if (d->out_t)      // [cout][ld_out_t] with M valid columns (M % 4 == 0: host check of out_t)
-          hipLaunchKernelGGL(add_rows_kernel, dim3((unsigned)((quads + 255) / 256 < 65535 * 16 ? (quads + 255) / 256 : 65535 * 16)), dim3(256), 0, s,
-                             d->out_t, a.out_t_k1, d->cout, a.M / 4, d->ld_out_t);
-        return vfml_check_launch("vfml_conv2d_split");
-      }
-      switch (cfg) {
-        case 3222: return launch_dma<3, 2, 2, 2>(a, s);   // 192 x 128, 2 workgroups per CU
-        case 2322: return launch_dma<2, 3, 2, 2>(a, s);   // 128 x 192
-        case 2122: return launch_dma<2, 1, 2, 2>(a, s);   // 128 x 64
-        case 1141: return launch_dma<1, 1, 4, 1>(a, s);   // 128 x 32
-        // (the 8-wave shapes of round 1 - 256 x 128, 192 x 256, 256 x 256, one workgroup per CU - measured slower and are
-        // no longer built)
-        case 2241: case 2341: return launch_dma<2, 1, 2, 2>(a, s);   // (forced shared-stage shapes on a call that kernel does not take)
-        default: return launch_dma<2, 2, 2, 2>(a, s);
-      }
+  // split-row sources: every slice is a multiple of 8 channels and >= one K step wide
+  // LDS-DMA kernel when both weight planes fit one descriptor window (< 1 GiB)
+  const char* ph = (const char*)w_hi;
+  const char* pl = bhi ? ph : (const char*)w_lo;
+  const char* wb = ph < pl ? ph : pl;
+  const int64_t ext = (ph < pl ? pl - ph : ph - pl) + (int64_t)d->cout * kp * 2;
+  // (a single plane may span up to 2 GiB: its lanes' out-of-range marker is 0x7ffffff0 instead of 1 GiB)
+  const bool dma_ok = bhi ? ext <= 0x7ffffff0ll : ext < (1ll << 30);
+  VFML_REQUIRE(dma_ok, "vfml_conv2d_split: split-row sources need w_hi and w_lo within 1 GiB of each other (one allocation)");
+  a.wbase = wb; a.whi_off = (int)(ph - wb); a.wlo_off = (int)(pl - wb); a.bytesb = (int)ext;
+  a.bhi = bhi ? 1 : 0;
+  a.tilebase = tilebase;
+  {
+    const int64_t abias = ((int64_t)d->pad_h * d->w + d->pad_w) * d->ld0 * 4;
+    // (for a 1x1 convolution over whole 32-channel blocks the two K orders are the same bytes)
+    const bool cblock = k_order == VFML_KORDER_CBLOCK || k_order == VFML_KORDER_CBLOCK64 ||
+                        (a.pointwise && (d->c0 + d->c1) % BK == 0);
+    a.fastk = cblock && d->c0 % BK == 0 && (d->c0 + d->c1) % BK == 0 &&
+              (!two || (d->ld1 == d->ld0 && a.d1off >= a.d0off)) && d->kh * d->kw <= 32 &&
+              (int64_t)a.bytes0 + abias < (1ll << 31);
+    VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.fastk,
+                 "vfml_conv2d_split: VFML_KORDER_CBLOCK64 needs the uniform-step loader (one row stride for both sources, kh*kw <= 32)");
+    if (a.fastk) a.korder = VFML_KORDER_CBLOCK;
+    // one MFMA per product over whole 64-channel blocks: 64-channel steps of hi halves (NM 5) - for 1x1 kernels in
+    // any weight order (the K axis is the channel axis), else with the weights in 64-channel-block order
+    // (cout > 32: the 128 x 32 tile of narrower outputs has no uniform-step instantiation)
+    if (a.nm == 1 && a.fastk && d->c0 % 64 == 0 && (d->c0 + d->c1) % 64 == 0 && d->cout > 32 &&
+        (k_order == VFML_KORDER_CBLOCK64 || a.pointwise))
+      a.nm = 5;
+    VFML_REQUIRE(k_order != VFML_KORDER_CBLOCK64 || a.nm == 5, "vfml_conv2d_split: VFML_KORDER_CBLOCK64 weights need the 64-channel-step kernel");
+    a.abias = a.fastk ? (int)abias : 0;
+    a.src1_delta = two ? (a.d1off - a.d0off) * 4 : 0;
+  }
+  // (VFML_FMT_F16 outputs exist in this form only: any width)
+  a.direct = (d->epilogue == VFML_EPI_NONE || d->epilogue == VFML_EPI_RELU) && !d->addend &&
+             (out_fmt == VFML_FMT_F32 || out_fmt == VFML_FMT_F16) && !d->stats_part &&
+             (d->cout >= DIRECT_MIN_COUT || out_fmt == VFML_FMT_F16) && d->cout % 4 == 0 && d->ldo % 4 == 0 && vfml_aligned16(d->out) &&
+             (!d->bias || vfml_aligned16(d->bias));
+  VFML_REQUIRE(out_fmt != VFML_FMT_F16 || (a.direct && a.fastk),
+               "vfml_conv2d_split: VFML_FMT_F16 outputs are written by the GEMM form only (1x1 over whole 32-channel blocks, no "
+               "addend / activation beyond ReLU, cout %% 4 == 0, ldo %% 4 == 0, 16-byte aligned out)");
+  if (d->flags & VFML_CONV_SWAP_CROSS) {
+    VFML_REQUIRE(a.direct && a.fastk, "vfml_conv2d_split: VFML_CONV_SWAP_CROSS is implemented by the GEMM form only "
+                                      "(1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024, cout %% 4 == 0)");
+    a.cswap = 1;
+  }
+  if (bhi)
+    VFML_REQUIRE(a.direct && a.fastk && !a.cswap, "vfml_conv2d_split: a weight operand without lo plane is implemented by the "
+                                                    "GEMM form only (1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024)");
+  if (d->out_t) {
+    VFML_REQUIRE(a.direct && a.fastk && a.pointwise && !d->bias && d->epilogue == VFML_EPI_NONE && a.M % 4 == 0 &&
+                 d->ld_out_t % 4 == 0 && d->ld_out_t >= a.M && vfml_aligned16(d->out_t),
+                 "vfml_conv2d_split: out_t needs the GEMM form (1x1 over whole 32-channel blocks, plain f32 out, cout >= 1024, cout %% 4 == 0), no bias / "
+                 "epilogue, pixels %% 4 == 0, ld_out_t %% 4 == 0 and >= pixels, 16-byte alignment");
+    a.out_t = d->out_t; a.ld_out_t = d->ld_out_t;
+  }
+  // A GEMM with few tiles and a long K axis (the MemFlow read-out: 254 tiles of 128 x 128 on 512 resident slots, one
+  // workgroup per CU streaming 8 MB of its operand): two work items per tile, one per half of K, when the caller gave
+  // a workspace for the second half's sums
+  if (d->ksplit_ws) {
+    VFML_REQUIRE(vfml_aligned16(d->ksplit_ws), "vfml_conv2d_split: ksplit_ws must be 16-byte aligned");
+    const int64_t tiles = (int64_t)((a.M + 127) / 128) * ((d->cout + 127) / 128);
+    const bool ksplit = a.direct && a.fastk && a.pointwise && out_fmt == VFML_FMT_F32 && !a.cswap && tiles <= 256 &&
+                        kp >= 4096;
+    if (ksplit) {     // (the workspace holds the primary output's shape, then - with out_t - the transposed one's)
+      a.ksplit = 2;
+      a.out_k1 = d->ksplit_ws;
+      a.out_t_k1 = d->ksplit_ws + (int64_t)a.M * d->ldo;
     }
-    vfml_set_error("vfml_conv2d_split: split-row sources need w_hi and w_lo within 1 GiB of each other (one allocation)");
+  }
+  if (d->proj_out) {
+    // projection epilogue: what the kernel's slab routine is built for
+    VFML_REQUIRE(d->epilogue == VFML_EPI_RELU && !d->addend && !d->stats_part && !d->out_t && !a.direct,
+                 "vfml_conv2d_split: proj_out goes with VFML_EPI_RELU, no addend / stats_part / out_t");
+    VFML_REQUIRE(a.fastk && (a.nm == 3 || a.nm == 4) && d->cout % 128 == 0,
+                 "vfml_conv2d_split: proj_out needs the uniform-step loader (channel-block weight order, whole 32-channel "
+                 "blocks), the full split product or VFML_CONV_MFMA2A (which then holds for the projection too) and "
+                 "cout %% 128 == 0");
+    VFML_REQUIRE(d->proj_hi && d->proj_lo && d->proj_n > 0 && d->proj_n <= 48 && d->proj_n % 4 == 0 && d->proj_kp >= d->cout &&
+                     d->proj_kp % 8 == 0 && d->ld_proj >= d->proj_n && d->ld_proj % 4 == 0 && vfml_aligned16(d->proj_out) &&
+                     vfml_aligned16(d->proj_hi) && vfml_aligned16(d->proj_lo) && d->proj_scale > 0.f,
+                 "vfml_conv2d_split: proj_hi / proj_lo [proj_n <= 48, %% 4 == 0][proj_kp >= cout] f16 planes, ld_proj >= proj_n, "
+                 "16-byte alignment");
+    const char* ph2 = (const char*)d->proj_hi;
+    const char* pl2 = (const char*)d->proj_lo;
+    const int64_t plane = (int64_t)d->proj_n * d->proj_kp * 2;
+    VFML_REQUIRE(pl2 >= ph2 && (pl2 - ph2) + plane < (1ll << 30), "vfml_conv2d_split: proj_lo must follow proj_hi within 1 GiB");
+    a.proj_w = ph2; a.proj_lo_off = (int)(pl2 - ph2); a.proj_bytes = (int)((pl2 - ph2) + plane);
+    a.proj_n = d->proj_n; a.proj_kp = d->proj_kp; a.proj_inv = 1.0f / d->proj_scale;
+    a.proj_out = d->proj_out; a.ld_proj = d->ld_proj;
+  }
+  return 0;
+}
+
+// VFML_DMA_TILE="TM,TN,WM,WN" (experiments / tests; read per call): the forced tile shape as digits, 0 when unset
+static int dma_tile_env() {
+  const char* tile_env = getenv("VFML_DMA_TILE");
+  if (!tile_env) return 0;
+  int tm = 2, tn = 2, wm = 2, wn = 2;
+  sscanf(tile_env, "%d,%d,%d,%d", &tm, &tn, &wm, &wn);
+  return tm * 1000 + tn * 100 + wm * 10 + wn;
+}
+
+// Steps 1 to 3 of a call short of the launch: arguments, plan, and the plan's row in its family's table
+static int split_prepare(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale, int in_fmt, int out_fmt,
+                         int aux_fmt, int k_order, int forced_tile, SplitArgs& a, SplitPlan& plan, const SplitVariant*& row) {
+  if (const int rc = split_fill(d, w_hi, w_lo, kp, w_scale, in_fmt, out_fmt, aux_fmt, k_order, a)) return rc;
+  if (const int rc = vfml_detail::plan_split(a, in_fmt == VFML_FMT_S16, d->flags, forced_tile, &plan)) return rc;
+  // (what the plan settled: a call that qualifies for uniform steps, or asks for fewer MFMAs, may run on a kernel without)
+  a.nm = plan.nm;
+  a.fastk = plan.fastk;
+  if (!plan.fastk) a.abias = 0;
+  row = plan.family == vfml_detail::SPLIT_TAPX ? vfml_detail::tapx_variant(plan)
+        : plan.family == vfml_detail::SPLIT_DMA ? vfml_detail::find_variant(DMA_VARIANTS, sizeof(DMA_VARIANTS) / sizeof(DMA_VARIANTS[0]), plan)
+                                                : vfml_detail::find_variant(REG_VARIANTS, sizeof(REG_VARIANTS) / sizeof(REG_VARIANTS[0]), plan);
+  if (!row) {
+    char name[160];
+    vfml_detail::variant_name(plan, name, sizeof(name));
+    vfml_set_error("vfml_conv2d_split: no such variant: %s", name);
     return 1;
   }
-  VFML_REQUIRE(!d->proj_out, "vfml_conv2d_split: proj_out is implemented for split-row (VFML_FMT_S16) sources only");
-  if (bn == 128) {
-    a.ntiles = (d->cout + 127) / 128;
-    return bigc ? launch<128, 2, 2, true, false>(a, s) : launch<128, 2, 2, false, false>(a, s);
-  } else if (bn == 64) {
-    a.ntiles = (d->cout + 63) / 64;
-    return bigc ? launch<64, 2, 2, true, false>(a, s) : launch<64, 2, 2, false, false>(a, s);
-  }
-  a.ntiles = 1;
-  return bigc ? launch<32, 4, 1, true, false>(a, s) : launch<32, 4, 1, false, false>(a, s);
+  return 0;
+}
+
+extern "C" int vfml_conv2d_split(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
+                                 int in_fmt, int out_fmt, int aux_fmt, int k_order, void* stream) {
+  SplitArgs a;
+  SplitPlan plan;
+  const SplitVariant* row;
+  if (const int rc = split_prepare(d, w_hi, w_lo, kp, w_scale, in_fmt, out_fmt, aux_fmt, k_order, dma_tile_env(), a, plan, row)) return rc;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int rc = row->launch(a, s);
+  if (rc || !plan.add_rows) return rc;
+  // (the partial sums of the second half of K are added once the launch is queued)
+  const int64_t quads = (int64_t)a.M * (d->cout / 4);
+  const dim3 grid((unsigned)((quads + 255) / 256 < 65535 * 16 ? (quads + 255) / 256 : 65535 * 16));
+  hipLaunchKernelGGL(add_rows_kernel, grid, dim3(256), 0, s, d->out, d->ksplit_ws, a.M, d->cout / 4, d->ldo);
+  if (d->out_t)      // [cout][ld_out_t] with M valid columns (M % 4 == 0: host check of out_t)
+    hipLaunchKernelGGL(add_rows_kernel, grid, dim3(256), 0, s, d->out_t, a.out_t_k1, d->cout, a.M / 4, d->ld_out_t);
+  return vfml_check_launch("vfml_conv2d_split");
+}
+
+extern "C" int vfml_conv2d_split_variant(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
+                                         int in_fmt, int out_fmt, int aux_fmt, int k_order, char* buf, int len) {
+  VFML_REQUIRE(buf && len > 0, "vfml_conv2d_split_variant: no buffer");
+  SplitArgs a;
+  SplitPlan plan;
+  const SplitVariant* row;
+  if (const int rc = split_prepare(d, w_hi, w_lo, kp, w_scale, in_fmt, out_fmt, aux_fmt, k_order, dma_tile_env(), a, plan, row)) return rc;
+  VFML_REQUIRE(vfml_detail::variant_name(row->key, buf, len) < len, "vfml_conv2d_split_variant: the name needs more than %d bytes", len);
+  return 0;
 }

@@ -310,34 +310,15 @@ int launch_tapx_k(SplitArgs& a, hipStream_t s) {
   return vfml_check_launch("vfml_conv2d_split");
 }
 
+// the instantiations that exist
+#define TAPX_ROWS(TM, TN, WM, WN) \
+  {vfml_detail::tapx_plan(TM, TN, WM, WN, 3), &launch_tapx_k<TM, TN, WM, WN, 3>}, \
+  {vfml_detail::tapx_plan(TM, TN, WM, WN, 5), &launch_tapx_k<TM, TN, WM, WN, 5>}
+const SplitVariant TAPX_VARIANTS[] = {TAPX_ROWS(3, 2, 2, 2), TAPX_ROWS(2, 3, 2, 2), TAPX_ROWS(2, 2, 4, 1), TAPX_ROWS(2, 3, 4, 1)};
+#undef TAPX_ROWS
+
 }  // namespace
 
-// The tile shape (TM TN WM WN as digits) this kernel would run the call on, or 0 when the call is not its: stride-1 "same"
-// convolutions over split-row sources on the uniform-step loader, 2..5 taps per filter row, three MFMAs per product or
-// one over 64-channel steps.  `cfg` = the shape the per-tap dispatcher chose among its own.
-int vfml_detail::tapx_cfg(const SplitArgs& a, int cfg, bool forced) {
-  if (!(a.fastk && !a.direct && !a.pointwise && !a.tilebase && a.stride == 1 && a.ho == a.H && a.wo == a.W && a.kw >= 2 &&
-        a.kw <= VFML_TAPX_KWMAX && a.kh <= 4 && (a.nm == 3 || a.nm == 5)))
-    return 0;
-  if (a.cout <= 32) return 0;
-  if (forced) return (cfg == 3222 || cfg == 2322 || (cfg == 2241 && a.cout <= 64) || (cfg == 2341 && a.cout <= 96)) ? cfg : 0;   // (VFML_DMA_TILE)
-  if (a.cout <= 96) {
-    // 256 x 64 / 256 x 96 tiles, when they fill the 512 resident slots of their last round to 85 % (the 1080p 1/8-scale
-    // maps are 380 such tiles: three quarters of one round - the per-tap kernel's 128-row tiles serve those better)
-    const int64_t tiles = (a.M + 255) / 256, rounds = (tiles + 511) / 512;
-    if (tiles * 100 < rounds * 512 * 85) return 0;
-    return a.cout <= 64 ? 2241 : 2341;
-  }
-  return cfg == 3222 || cfg == 2322 ? cfg : 0;
-}
-
-int vfml_detail::launch_tapx(SplitArgs& a, int cfg, hipStream_t s) {
-  switch (cfg) {
-    case 3222: return a.nm == 5 ? launch_tapx_k<3, 2, 2, 2, 5>(a, s) : launch_tapx_k<3, 2, 2, 2, 3>(a, s);
-    case 2322: return a.nm == 5 ? launch_tapx_k<2, 3, 2, 2, 5>(a, s) : launch_tapx_k<2, 3, 2, 2, 3>(a, s);
-    case 2241: return a.nm == 5 ? launch_tapx_k<2, 2, 4, 1, 5>(a, s) : launch_tapx_k<2, 2, 4, 1, 3>(a, s);
-    case 2341: return a.nm == 5 ? launch_tapx_k<2, 3, 4, 1, 5>(a, s) : launch_tapx_k<2, 3, 4, 1, 3>(a, s);
-  }
-  vfml_set_error("vfml_conv2d_split: no shared-stage variant for tile shape %d", cfg);
-  return 1;
+const SplitVariant* vfml_detail::tapx_variant(const SplitPlan& plan) {
+  return find_variant(TAPX_VARIANTS, sizeof(TAPX_VARIANTS) / sizeof(TAPX_VARIANTS[0]), plan);
 }

@@ -1,6 +1,6 @@
-// Shared by the split-f16 convolution translation units (conv_gemm_split.hip, conv_gemm_tapx.hip): argument block,
-// compile-time loops, the LDS-DMA primitive, the bank swizzle of the 16x16x32 LDS image and the epilogue that turns a
-// workgroup's fp32 tile in LDS into global rows.
+// Shared by the split-f16 convolution translation units (conv_gemm_split.hip, conv_gemm_tapx.hip, conv_split_plan.hip):
+// argument block, the plan of a call and the rows of the launch tables, compile-time loops, the LDS-DMA primitive, the
+// bank swizzle of the 16x16x32 LDS image and the epilogue that turns a workgroup's fp32 tile in LDS into global rows.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
@@ -49,10 +49,43 @@ struct SplitArgs {
 };
 // conv_gemm_tapx.hip: the kernel that shares one activation stage between the taps of a filter row
 #define VFML_TAPX_KWMAX 5      // widest filter row it is built for
-int tapx_cfg(const SplitArgs& a, int cfg, bool forced);       // cfg = tile shape as TM TN WM WN digits; 0: not its call
-int launch_tapx(SplitArgs& a, int cfg, hipStream_t s);
+
+// How a vfml_conv2d_split call becomes a kernel (conv_split_plan.hip): the template instantiation that runs it, spelled
+// with the kernels' own template parameter names.
+enum SplitFamily { SPLIT_REG, SPLIT_DMA, SPLIT_TAPX };   // conv_gemm_split_kernel / conv_gemm_dma_kernel / conv_gemm_tapx_kernel
+struct SplitPlan {
+  SplitFamily family;
+  int bn;                                   // SPLIT_REG: BN
+  int tm, tn;                               // SPLIT_DMA / SPLIT_TAPX: TM TN
+  int wm, wn;
+  bool bigc, in16;                          // SPLIT_REG
+  bool persist, fastk, cswap, mf16, h16;    // SPLIT_DMA
+  int nm;
+  bool add_rows;                            // the K split's add_rows launches follow (no part of the kernel's name)
+};
+// the forced tile shape is VFML_DMA_TILE's "TM,TN,WM,WN" as digits, 0 = none; 0, or 1 with the error set
+int plan_split(const SplitArgs& a, bool in16, int flags, int forced_tile, SplitPlan* plan);
+constexpr SplitPlan reg_plan(int bn, int wm, int wn, bool bigc, bool in16, int nm) {
+  return {SPLIT_REG, bn, 0, 0, wm, wn, bigc, in16, false, false, false, false, false, nm, false};
+}
+constexpr SplitPlan dma_plan(int tm, int tn, int wm, int wn, bool persist, bool fastk, bool cswap, int nm, bool mf16, bool h16) {
+  return {SPLIT_DMA, 0, tm, tn, wm, wn, false, false, persist, fastk, cswap, mf16, h16, nm, false};
+}
+constexpr SplitPlan tapx_plan(int tm, int tn, int wm, int wn, int nm) {
+  return {SPLIT_TAPX, 0, tm, tn, wm, wn, false, false, false, true, false, true, false, nm, false};   // (uniform steps, 16x16x32 MFMAs)
+}
+// One row of a family's table of the instantiations that exist: the launch sets a.mtiles / a.ntiles and nothing else.
+struct SplitVariant {
+  SplitPlan key;
+  int (*launch)(SplitArgs& a, hipStream_t s);
+};
+const SplitVariant* find_variant(const SplitVariant* rows, size_t n, const SplitPlan& plan);   // null: no such instantiation
+int variant_name(const SplitPlan& key, char* buf, int len);     // the kernel's name as rocprofv3 prints it
+const SplitVariant* tapx_variant(const SplitPlan& plan);        // conv_gemm_tapx.hip's table
 }  // namespace vfml_detail
 using vfml_detail::SplitArgs;
+using vfml_detail::SplitPlan;
+using vfml_detail::SplitVariant;
 
 namespace {
 

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -121,6 +121,8 @@ def lib():
     L.vfml_conv2d.argtypes = [POINTER(ConvDesc), c_void_p]
     L.vfml_conv2d_split.argtypes = [POINTER(ConvDesc), c_void_p, c_void_p, c_int, c_float, c_int, c_int, c_int, c_int,
                                     c_void_p]
+    L.vfml_conv2d_variant.argtypes = [POINTER(ConvDesc), c_char_p, c_int]
+    L.vfml_conv2d_split_variant.argtypes = L.vfml_conv2d_split.argtypes[:-1] + [c_char_p, c_int]
     L.vfml_to_s16.argtypes = [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_float, c_void_p]
     L.vfml_softmax_rows_s16.argtypes = [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_float, c_void_p]
     L.vfml_transpose_split_f16.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p]
@@ -199,14 +201,14 @@ def lib():
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
-    if L.vfml_abi_version() != 25:
+    if L.vfml_abi_version() != 26:
         raise RuntimeError("libvfml_hip.so ABI version mismatch")
     _lib = L
     return L
 
 
 EXPORTS = [
-    "vfml_conv2d", "vfml_conv2d_split", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
+    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
@@ -293,52 +295,6 @@ def profile_end():
     return out
 
 
-def conv_variant(cout, split=False, ctot=32, in16=False, m=0, order=KORDER_TAP, plain_f32_out=False, fastk=False,
-                 cswap=False, nm=3, same=None, per_tap=False, stats=False, h16=False):
-    """Template instantiation vfml_conv2d[_split] dispatches to, spelled as rocprofv3 prints it (mirrors
-    the dispatch at the end of csrc/conv_gemm_split.hip; the rare 64-wide choice of the register-staged
-    split kernel for cout > 64 is not modelled)."""
-    tile = "128, 2, 2" if cout > 64 else ("64, 2, 2" if cout > 32 else "32, 4, 1")
-    if not split:
-        return f"conv_gemm_kernel<{tile}>"
-    dma = in16
-    if dma:     # split-f16, LDS-DMA staged
-        fk = "true" if fastk else "false"       # uniform-step loader (SplitArgs::fastk)
-        if plain_f32_out and cout >= 1024 and cout % 4 == 0:
-            if not fastk:
-                nm = 3
-            return f"conv_gemm_dma_kernel<2, 2, 2, 2, true, {fk}, {'true' if cswap else 'false'}, {nm}, false, {'true' if h16 else 'false'}>"   # persistent GEMM form
-        if cout <= 32:
-            return f"conv_gemm_dma_kernel<1, 1, 4, 1, false, false, false, {nm}, true, false>"
-        # the shared-stage kernel (csrc/conv_gemm_tapx.hip: vfml_detail::tapx_cfg and the dispatcher's condition):
-        # `same` = (kh, kw) of a stride-1 "same" convolution, else None
-        tapx = (not per_tap and fastk and same is not None and 2 <= same[1] <= 5 and same[0] <= 4
-                and nm in (3, 5))
-        tiles256 = -(-m // 256)
-        fills = tiles256 * 100 >= -(-tiles256 // 512) * 512 * 85      # 256-row tiles fill their last round to 85 %
-        if tapx and cout <= 64 and fills:
-            return f"conv_gemm_tapx_kernel<2, 2, 4, 1, {nm}>"
-        if tapx and 64 < cout <= 96 and fills:
-            return f"conv_gemm_tapx_kernel<2, 3, 4, 1, {nm}>"
-        if cout <= 64:
-            return f"conv_gemm_dma_kernel<2, 1, 2, 2, false, {fk}, false, {nm}, true, false>"
-        def cost(tbm, tbn, mf, eff):
-            tiles = -(-m // tbm) * -(-cout // tbn)
-            return (tiles / 512.0 if tiles > 512 else 1.0) * mf / eff
-        cands = [(cost(192, 128, 6.0, 1.0), "3, 2, 2, 2"), (cost(128, 192, 6.0, 1.0), "2, 3, 2, 2"),
-                 (cost(128, 128, 4.0, 0.93), "2, 2, 2, 2"), (cost(128, 64, 2.0, 0.7), "2, 1, 2, 2")]
-        t = cands[0][1]
-        best = cands[0][0]
-        for c, name in cands[1:]:
-            if c < best:
-                best, t = c, name
-        if tapx and t in ("3, 2, 2, 2", "2, 3, 2, 2") and nm == 5:
-            return f"conv_gemm_tapx_kernel<{t}, {nm}>"
-        return f"conv_gemm_dma_kernel<{t}, false, {fk}, false, {nm}, true, false>"
-    bigc = "true" if (ctot >= 32 or in16) else "false"
-    return f"conv_gemm_split_kernel<{tile}, {bigc}, {'true' if in16 else 'false'}, {nm}>"
-
-
 class SplitWeight:
     """[rows][k] f32 matrix (times a power-of-two `scale`) as two f16 planes [rows][kp] (hi, lo) for
     vfml_conv2d_split."""
@@ -381,13 +337,15 @@ def conv2d(in0, c0, ld0, n, h, w, weight, bias, cout, kh, kw, out, ldo, *, strid
            aux0=None, ld_aux0=0, aux0_off=0, aux1=None, ld_aux1=0, aux1_off=0,
            in_fmt=FMT_F32, out_fmt=FMT_F32, aux_fmt=FMT_F32, addend=None, ld_addend=0, addend_off=0,
            out_t=None, ld_out_t=0, out_t_off=0, swap_cross=False, stats_part=None, mfma=3, per_tap=False, ksplit_ws=None,
-           proj=None, proj_out=None, ld_proj=0, addend_ind=None):
+           proj=None, proj_out=None, ld_proj=0, addend_ind=None, variant_only=False):
     """Launch vfml_conv2d. Tensors are flat float32 device buffers; *_off are float offsets into them
     (channel slices of wider NHWC buffers).  mfma: terms of the split-f16 product (3; 2 or "2w" = weights as plain
     f16; "2a" = activations as plain f16; 1 = both operands plain f16 - VFML_CONV_MFMA2 / _MFMA2A / _MFMA1).  per_tap:
     VFML_CONV_PER_TAP (the per-tap staging kernel where the shared-stage one would run; same bits).
     proj (a SplitWeight [proj_n <= 48][cout]) with proj_out / ld_proj: the projection epilogue (vfml_conv_desc.proj_out) -
-    relu(out) is not stored, proj_out receives cout / 128 partial maps [n*ho*wo][ld_proj] of relu(out) x proj^T."""
+    relu(out) is not stored, proj_out receives cout / 128 partial maps [n*ho*wo][ld_proj] of relu(out) x proj^T.
+    variant_only: launch nothing and return the name of the kernel the library would launch for this call, as
+    rocprofv3 prints it (vfml_conv2d_variant / vfml_conv2d_split_variant: the library's own plan, csrc/conv_split_plan.hip)."""
     d = ConvDesc()
     d.in0, d.c0, d.ld0 = _ptr(_dev(in0), in0_off), c0, ld0
     d.in1, d.c1, d.ld1 = (_ptr(_dev(in1), in1_off) if in1 is not None else None), c1, ld1
@@ -420,17 +378,30 @@ def conv2d(in0, c0, ld0, n, h, w, weight, bias, cout, kh, kw, out, ldo, *, strid
         d.proj_out, d.ld_proj = _ptr(_dev(proj_out)), ld_proj
     if is_split:
         # weight_off counts rows of the split planes (each row kp halves)
+        wargs = (c_void_p(weight.hi.data_ptr() + 2 * weight_off * weight.kp),
+                 c_void_p(weight.lo.data_ptr() + 2 * weight_off * weight.kp) if weight.lo is not None else None, weight.kp,
+                 weight.scale, in_fmt, out_fmt, aux_fmt, weight.order)
+
         def launch():
-            _check(lib().vfml_conv2d_split(ctypes.byref(d), c_void_p(weight.hi.data_ptr() + 2 * weight_off * weight.kp),
-                                           c_void_p(weight.lo.data_ptr() + 2 * weight_off * weight.kp) if weight.lo is not None else None, weight.kp,
-                                           weight.scale, in_fmt, out_fmt, aux_fmt, weight.order, _stream()),
-                   "vfml_conv2d_split")
+            _check(lib().vfml_conv2d_split(ctypes.byref(d), *wargs, _stream()), "vfml_conv2d_split")
+
+        def variant():
+            buf = ctypes.create_string_buffer(160)
+            _check(lib().vfml_conv2d_split_variant(ctypes.byref(d), *wargs, buf, len(buf)), "vfml_conv2d_split_variant")
+            return buf.value.decode()
     else:
         if in_fmt != FMT_F32 or out_fmt != FMT_F32 or aux_fmt != FMT_F32:
             raise ValueError("the exact-f32 kernel (vfml_conv2d) takes and writes plain f32 activations only")
 
         def launch():
             _check(lib().vfml_conv2d(ctypes.byref(d), _stream()), "vfml_conv2d")
+
+        def variant():
+            buf = ctypes.create_string_buffer(160)
+            _check(lib().vfml_conv2d_variant(ctypes.byref(d), buf, len(buf)), "vfml_conv2d_variant")
+            return buf.value.decode()
+    if variant_only:
+        return variant()
     if _PROFILE is None:
         launch()
         return
@@ -440,23 +411,7 @@ def conv2d(in0, c0, ld0, n, h, w, weight, bias, cout, kh, kw, out, ldo, *, strid
     e0.record()
     launch()
     e1.record()
-    plain = (epilogue in (EPI_NONE, EPI_RELU) and addend is None and out_fmt in (FMT_F32, FMT_F16) and ldo % 4 == 0)
-    ctot = c0 + c1
-    pointwise = kh == 1 and kw == 1 and stride == 1 and pad_h == 0 and pad_w == 0
-    fastk = (is_split and in_fmt == FMT_S16 and (weight.order in (KORDER_CBLOCK, KORDER_CBLOCK64) or (pointwise and ctot % 32 == 0))
-             and c0 % 32 == 0 and ctot % 32 == 0 and kh * kw <= 32
-             and (in1 is None or (ld1 == ld0 and in1.data_ptr() + 4 * in1_off >= in0.data_ptr() + 4 * in0_off)))
-    nm_eff = {"2a": 4}.get(mfma, mfma)
-    if (mfma == 1 and fastk and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32 and
-            (weight.order == KORDER_CBLOCK64 or pointwise)):
-        nm_eff = 5                                           # 64-channel steps of hi halves
-    elif is_split and weight.lo is None:
-        nm_eff = {3: 2, 2: 2, 4: 1, 1: 1}[nm_eff]            # a single weight plane has no lo half to use
-    same = (kh, kw) if (stride == 1 and ho == h and wo == w and not pointwise) else None
-    # (a VFML_FMT_F16 output is written by the GEMM form whatever its width)
-    _PROFILE.append((conv_variant(max(cout, 1024) if out_fmt == FMT_F16 else cout, is_split, ctot, in_fmt == FMT_S16, n * ho * wo,
-                                  weight.order if is_split else KORDER_TAP, plain, fastk, swap_cross, nm_eff, same, per_tap,
-                                  h16=out_fmt == FMT_F16),
+    _PROFILE.append((variant(),       # the kernel the library chose
                      2.0 * n * ho * wo * (kh * kw * (c0 + c1) * cout + (cout * proj.rows if proj is not None else 0)),
                      # operands read once + result written once, 4 bytes per element in either activation format
                      4.0 * (n * h * w * (c0 + c1) + n * ho * wo * cout * (2 if out_t is not None else 1)
