@@ -619,6 +619,49 @@ int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan_bytes, int
                               const unsigned char* qtables, const int32_t* tables, int y0, int y1, int subseq_bytes,
                               void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
 
+/* Deflate / inflate of the flow cache's .npz members (tests/deflate_oracle.py is the definition of
+ * the stream, vfml/csrc/deflate_code.h of its code lengths).  The raw bytes are cut into chunks of chunk_bytes (a power of
+ * two, 1024..32768); a chunk becomes one dynamic-Huffman block of literals and the end-of-block symbol - or one stored
+ * block when that is not larger - and every chunk but the last is followed by an empty stored block (00 00 FF FF after
+ * padding), so that every chunk starts on a byte boundary; the last block carries BFINAL.  Any inflater reads the result;
+ * with the chunks' offsets it is decoded in parallel.  All integer, all on `stream`, no host synchronisation, no
+ * allocation.
+ * raw: device, any alignment (a slice of a larger buffer is coded in place).  workspace: device, 256-byte aligned,
+ * vfml_deflate_workspace_bytes / vfml_inflate_workspace_bytes; not shared by calls that may run at once.
+ * out: receives the stream, any alignment; vfml_deflate_capacity(raw_bytes, chunk_bytes) bytes always suffice; with a
+ * smaller capacity nothing is written at or past out + capacity and *stream_bytes still holds the length the stream
+ * needs.  offsets: device uint32[ceil(raw_bytes / chunk_bytes)], the byte offset of every chunk in the stream;
+ * *stream_bytes, *crc: device, 4-byte aligned.  *crc = CRC-32 (the zip polynomial) of the raw bytes continued from
+ * crc_init (the CRC of whatever the caller puts in front, 0 for nothing): chunk 0 continues crc_init, the others start
+ * from 0, and the values are folded on the device with multiplications by x^(8 len).
+ * 1 <= raw_bytes < 2 GiB and at most 16000 chunks (what a zip extra field can index); the size functions return 0
+ * otherwise. */
+int64_t vfml_deflate_capacity(int64_t raw_bytes, int chunk_bytes);
+int64_t vfml_deflate_workspace_bytes(int64_t raw_bytes, int chunk_bytes);
+int vfml_deflate_huffman(const unsigned char* raw, int64_t raw_bytes, int chunk_bytes, uint32_t crc_init, void* workspace,
+                         unsigned char* out, int64_t capacity, uint32_t* offsets, uint32_t* stream_bytes, uint32_t* crc,
+                         void* stream);
+
+/* The inflater: a wave per chunk, chunk i = data[offsets[i] .. offsets[i+1]) (the last one ends at data_bytes) and
+ * decodes to raw[i * chunk_bytes ..), min(chunk_bytes, what is left of raw_bytes) bytes.  A chunk is any sequence of
+ * dynamic, fixed and stored blocks of literals that ends with BFINAL or with the chunk's bytes; n_chunks =
+ * ceil(raw_bytes / chunk_bytes).  *crc as above.  *status (device, 4-byte aligned) receives 0 or the OR of
+ * VFML_INFLATE_ERR_*: damaged data is a defined result - every index is checked on the device, nothing outside `data` is
+ * read and nothing outside `raw` written, whose content (and *crc) is then unspecified. */
+enum {
+  VFML_INFLATE_ERR_CODE = 1,     /* bits that are no code of the block's table, or a block header that describes none */
+  VFML_INFLATE_ERR_MATCH = 2,    /* a length / distance symbol: this codec has literals only                           */
+  VFML_INFLATE_ERR_LENGTH = 4,   /* a chunk that decodes to another length than its share of raw_bytes                  */
+  VFML_INFLATE_ERR_BITS = 8,     /* a chunk's bits ran out inside a block                                               */
+  VFML_INFLATE_ERR_STORED = 16,  /* a stored block whose LEN and NLEN do not agree                                      */
+  VFML_INFLATE_ERR_CHUNK = 32    /* offsets that are not ascending inside data_bytes, or a chunk whose compressed form is
+                                    longer than 9/8 chunk_bytes + 64 bytes (more than fixed codes need)                 */
+};
+int64_t vfml_inflate_workspace_bytes(int64_t raw_bytes, int chunk_bytes);
+int vfml_inflate_chunks(const unsigned char* data, int64_t data_bytes, const uint32_t* offsets, int n_chunks, int chunk_bytes,
+                        int64_t raw_bytes, uint32_t crc_init, void* workspace, unsigned char* raw, uint32_t* crc,
+                        int32_t* status, void* stream);
+
 const char* vfml_last_error(void);
 int vfml_abi_version(void);
 

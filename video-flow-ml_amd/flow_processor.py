@@ -305,28 +305,61 @@ class _ExternalFlowSource:
 
 
 class _FieldReader:
-    """Reads cache fields ahead of use on a small thread pool, in frame order."""
+    """Reads cache fields ahead of use on a small thread pool, in frame order.  With `device` (the device render path,
+    DEVICE_NPZ) an .npz whose `flow` member carries a chunk index (storage/device_npz.py) is only read by the pool: get()
+    uploads its bytes and inflates them on the device, and returns a device tensor whose CRC is looked at one field
+    later.  Files without an index - the reference's, zlib's, .flo - are decoded by the pool as before."""
 
-    def __init__(self, mgr, cache_dir, fmt, n, ahead=4):
+    def __init__(self, mgr, cache_dir, fmt, n, ahead=4, device=None):
         from concurrent.futures import ThreadPoolExecutor
         self.mgr, self.cache_dir, self.fmt, self.n, self.ahead = mgr, cache_dir, fmt, n, ahead
+        self.device = device if fmt == 'npz' else None
         self.pool = ThreadPoolExecutor(max_workers=2, thread_name_prefix="render-read")
         self.futs = {}
         self.next = 0
+        self.unchecked = None
+
+    def _load(self, i):
+        if self.device is not None:
+            from storage import device_npz
+            plan = device_npz.load_indexed(self.mgr._frame_file(self.cache_dir, i, 'npz'), 'flow')
+            if plan is not None:
+                return plan
+        return self.mgr.load_cached_flow(self.cache_dir, i, self.fmt)
+
+    def _check(self):
+        if self.unchecked is not None:
+            from vfml import hip
+            (cells, crc), self.unchecked = self.unchecked, None
+            hip.inflate_check(cells, crc)
 
     def get(self, i):
         while self.next < min(self.n, i + self.ahead + 1):
-            self.futs[self.next] = self.pool.submit(self.mgr.load_cached_flow, self.cache_dir, self.next, self.fmt)
+            self.futs[self.next] = self.pool.submit(self._load, self.next)
             self.next += 1
-        return np.asarray(self.futs.pop(i).result(), dtype=np.float32)
+        got = self.futs.pop(i).result()
+        if isinstance(got, dict):
+            from storage import device_npz
+            field, cells, crc = device_npz.inflate_indexed(got, self.device)
+            self._check()                      # the field before this one, now that this one's work is queued
+            self.unchecked = (cells, crc)
+            return field
+        return np.asarray(got, dtype=np.float32)
 
     def close(self):
         self.pool.shutdown(cancel_futures=True)
+        self._check()
 
 
 # The device render path's MJPG frames are encoded on the GPU (vfml_jpeg_encode_rgb, DESIGN.md section 12); False: its
 # composed frames go back uncompressed to the writer's Pillow pool, as --device cpu's do.
 DEVICE_MJPG = True
+# True: the flow cache's .npz members are deflated (the job) and inflated (the render stage) on the GPU
+# (vfml_deflate_huffman / vfml_inflate_chunks, DESIGN.md section 14); False: the writer's and the reader's host threads
+# run zlib, as they always do for tiled jobs, --save-flow flo / both, --device cpu and an explicitly set
+# VFML_NPZ_DEFLATE.  Off until fields/s and rendered frames/s have been measured against the host path (section 14's
+# rule for the default); a device-written cache is read by either setting.
+DEVICE_NPZ = False
 
 
 def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=None, log=print):
@@ -379,7 +412,7 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     encoder = render_encoder(args.flow_format, args.motion_vectors_clamp_range)
     taa_flow, taa_simple, taa_external = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
     variant = FLOW_INPUT_VARIANTS.get(args.flow_format)
-    reader = _FieldReader(FlowCacheManager(), cache_dir, fmt, n)
+    reader = _FieldReader(FlowCacheManager(), cache_dir, fmt, n, device=device if gpu and DEVICE_NPZ else None)
     log(ENCODER_LINES.get(args.flow_format, ENCODER_LINES['gamedev']).format(c=args.motion_vectors_clamp_range))
     t0 = time.time()
     try:
@@ -458,12 +491,15 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         frame = feeder.clip[i]
         k = i % len(fslots)
         host = reader.get(i)
-        if fevents[k] is not None:
-            fevents[k].synchronize()
-        np.copyto(fslots[k].numpy(), host)
-        field = fslots[k].to(device, non_blocking=True)
-        fevents[k] = torch.cuda.Event()
-        fevents[k].record(stream)
+        if torch.is_tensor(host):
+            field = host            # an indexed .npz member: inflated on the device, it never was on the host uncompressed
+        else:
+            if fevents[k] is not None:
+                fevents[k].synchronize()
+            np.copyto(fslots[k].numpy(), host)
+            field = fslots[k].to(device, non_blocking=True)
+            fevents[k] = torch.cuda.Event()
+            fevents[k].record(stream)
         viz = encoder.encode(field, width, height) if external is None else None
         taa_frame = taa_simple_frame = None
         if taa:
@@ -602,7 +638,19 @@ def main(argv=None):
     # LOD levels are reduced on the GPU that computed the field (bit-identical to the reference's loop) and travel
     # with it; tiled frames are assembled on rank 0 and reduced by the writer's threads
     sink = (lambda k, field, lods: writer.submit(field, k, lods)) if writer is not None else None
-    if per_rank:
+    # whole-frame .npz jobs on a GPU: fields and LOD levels are deflated on the device, the writer gets finished streams
+    device_npz = (DEVICE_NPZ and per_rank and save_format == 'npz' and str(device).startswith('cuda')
+                  and "VFML_NPZ_DEFLATE" not in os.environ)
+    if device_npz:
+        from storage.device_npz import CHUNK_BYTES, DeviceNpzWriter
+        from vfml import hip
+        device_npz = hip.deflate_capacity(height * width * 8, CHUNK_BYTES) > 0     # (a field of more chunks than an index holds)
+    if device_npz:
+        npz = DeviceNpzWriter(device, writer.submit_members)
+        run_sharded(proc, None, range(n), tile_mode=False, rank=rank, world=world, feeder=feeder, device_npz=npz,
+                    collect=False, num_lods=gpu_lods)
+        npz.finish()
+    elif per_rank:
         run_sharded(proc, None, range(n), tile_mode=False, rank=rank, world=world, feeder=feeder, local_sink=sink,
                     collect=False, num_lods=gpu_lods)
     else:

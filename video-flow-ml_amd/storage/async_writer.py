@@ -43,6 +43,46 @@ class AsyncFlowCacheWriter:
         finally:
             self._slots.release()
 
+    def _write_members(self, frame_idx, members):
+        """members: [(ZipMember 'flow', shape)] of the field and, with LODs, of levels 1..: streams that the GPU coded
+        (storage/device_npz.py).  The files and their small members are those of _write; the field's stream goes into
+        flow_frame_N.npz and flow_frame_N_lod0.npz alike."""
+        import os
+
+        from .cache_manager import write_npz
+        try:
+            os.makedirs(self.cache_dir, exist_ok=True)
+            flow, shape = members[0]
+            write_npz(self.manager._frame_file(self.cache_dir, frame_idx, 'npz'),
+                      {'flow': flow, 'frame_idx': frame_idx, 'shape': shape, 'dtype': 'float32'}, mode='huffman')
+            if self.num_lods:
+                for level, (flow, shape) in enumerate(members[:self.num_lods]):
+                    write_npz(self.manager._frame_file(self.cache_dir, frame_idx, 'npz', level),
+                              {'flow': flow, 'frame_idx': frame_idx, 'lod_level': level, 'shape': shape, 'dtype': 'float32'},
+                              mode='huffman')
+            with self._lock:
+                self._written.append(frame_idx)
+        except BaseException as e:     # surfaced by the next submit() / close()
+            with self._lock:
+                if self._error is None:
+                    self._error = e
+        finally:
+            self._slots.release()
+
+    def submit_members(self, frame_idx, members):
+        """The entry for finished member streams (save_format 'npz'): see _write_members.  Blocks like submit."""
+        if self.save_format != 'npz':
+            raise ValueError("submit_members writes .npz caches only")
+        if self.num_lods and len(members) < self.num_lods:
+            raise ValueError(f"{self.num_lods} LOD levels expected, {len(members)} given")
+        self._raise_pending_error()
+        self._slots.acquire()
+        try:
+            self._pool.submit(self._write_members, frame_idx, members)
+        except BaseException:
+            self._slots.release()
+            raise
+
     def _raise_pending_error(self):
         with self._lock:
             err, self._error = self._error, None

@@ -7,6 +7,7 @@ File formats and names are byte-compatible with reference storage/cache_manager.
 The LOD generator keeps the reference's semantics (:77-161: pad odd sides bottom/right with zero
 weight, 2x2 weighted mean, vectors x0.5) but is vectorised instead of a per-pixel Python loop.
 """
+import collections
 import os
 import struct
 from typing import Any, Dict, List, Optional, Tuple
@@ -51,45 +52,72 @@ def _npy_parts(value):
     return head.getvalue(), arr
 
 
-def write_npz(filename, members, mode=None):
-    """Write {name: array-like} as an .npz archive np.load reads back member for member like np.savez_compressed's."""
+class ZipMember(collections.namedtuple("ZipMember", "name method crc size chunks extra")):
+    """A ready-made member `<name>.npy` of an archive: zip method (8 deflate, 0 stored), CRC-32 and size of the
+    uncompressed .npy bytes, the pieces of the data as they go into the file, the extra field of both headers."""
+    __slots__ = ()
+
+
+def host_member(name, value, method):
+    """The ZipMember of `value`, coded on the host: method 8 = Z_HUFFMAN_ONLY deflate, 0 = stored."""
     import zlib
-    mode = mode or os.environ.get("VFML_NPZ_DEFLATE", "huffman")
-    if mode == "zlib":
-        np.savez_compressed(filename, **members)
-        return
-    if mode not in ("huffman", "stored"):
-        raise ValueError(f"VFML_NPZ_DEFLATE={mode!r}: huffman, zlib or stored")
-    if not str(filename).endswith('.npz'):       # (np.savez appends the suffix too)
-        filename = str(filename) + '.npz'
-    method = 8 if mode == "huffman" else 0
+    head, arr = _npy_parts(value)
+    raw = memoryview(arr.reshape(-1).view(np.uint8)) if arr.size else memoryview(b'')
+    crc = zlib.crc32(raw, zlib.crc32(head))
+    size = len(head) + raw.nbytes
+    if method == 8:
+        co = zlib.compressobj(1, zlib.DEFLATED, -15, 9, zlib.Z_HUFFMAN_ONLY)
+        chunks = [co.compress(head), co.compress(raw), co.flush()]
+    else:
+        chunks = [head, raw]
+    return ZipMember(name, method, crc, size, chunks, b'')
+
+
+def write_zip(filename, members):
+    """Lay out a zip archive from ZipMembers (host_member's, or storage.device_npz's with a stream that the GPU coded):
+    local headers, data, central directory."""
     central, offset = [], 0
     with open(filename, 'wb') as f:
-        for name, value in members.items():
-            head, arr = _npy_parts(value)
-            raw = memoryview(arr.reshape(-1).view(np.uint8)) if arr.size else memoryview(b'')
-            crc = zlib.crc32(raw, zlib.crc32(head))
-            size = len(head) + raw.nbytes
-            if size >= 0xFFFFFFFF:
-                raise ValueError("flow-cache member of 4 GiB or more")
-            if method == 8:
-                co = zlib.compressobj(1, zlib.DEFLATED, -15, 9, zlib.Z_HUFFMAN_ONLY)
-                chunks = [co.compress(head), co.compress(raw), co.flush()]
-            else:
-                chunks = [head, raw]
+        for name, method, crc, size, chunks, extra in members:
             csize = sum(len(c) for c in chunks)
+            if size >= 0xFFFFFFFF or csize >= 0xFFFFFFFF:
+                raise ValueError("flow-cache member of 4 GiB or more")
+            if len(extra) > 0xFFFF:
+                raise ValueError("zip extra field of more than 65535 bytes")
             fname = (name + '.npy').encode()
             # version 2.0, no flags, DOS time 1980-01-01 (as zipfile stamps members without a file behind them)
-            f.write(_ZIP_LOCAL.pack(b'PK\x03\x04', 20, 0, method, 0, 0x21, crc, csize, size, len(fname), 0))
+            f.write(_ZIP_LOCAL.pack(b'PK\x03\x04', 20, 0, method, 0, 0x21, crc, csize, size, len(fname), len(extra)))
             f.write(fname)
+            f.write(extra)
             for c in chunks:
                 f.write(c)
-            central.append(_ZIP_CENTRAL.pack(b'PK\x01\x02', 20, 20, 0, method, 0, 0x21, crc, csize, size, len(fname), 0, 0, 0,
-                                             0, 0x01800000, offset) + fname)
-            offset += _ZIP_LOCAL.size + len(fname) + csize
+            central.append(_ZIP_CENTRAL.pack(b'PK\x01\x02', 20, 20, 0, method, 0, 0x21, crc, csize, size, len(fname),
+                                             len(extra), 0, 0, 0, 0x01800000, offset) + fname + extra)
+            offset += _ZIP_LOCAL.size + len(fname) + len(extra) + csize
         cd = b''.join(central)
         f.write(cd)
         f.write(_ZIP_END.pack(b'PK\x05\x06', 0, 0, len(central), len(central), len(cd), offset, 0))
+
+
+def npz_mode(mode=None):
+    mode = mode or os.environ.get("VFML_NPZ_DEFLATE", "huffman")
+    if mode not in ("huffman", "stored", "zlib"):
+        raise ValueError(f"VFML_NPZ_DEFLATE={mode!r}: huffman, zlib or stored")
+    return mode
+
+
+def write_npz(filename, members, mode=None):
+    """Write {name: array-like} as an .npz archive np.load reads back member for member like np.savez_compressed's.
+    A value may also be a ZipMember: it is laid out as it is."""
+    mode = npz_mode(mode)
+    if mode == "zlib":
+        np.savez_compressed(filename, **members)
+        return
+    if not str(filename).endswith('.npz'):       # (np.savez appends the suffix too)
+        filename = str(filename) + '.npz'
+    method = 8 if mode == "huffman" else 0
+    write_zip(filename, [value if isinstance(value, ZipMember) else host_member(name, value, method)
+                         for name, value in members.items()])
 
 
 class FlowFileHandler:

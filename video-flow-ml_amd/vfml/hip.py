@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -74,7 +74,7 @@ def build(force=False, verbose=False):
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "vfml_common.h"), os.path.join(CSRC, "conv_split_common.h"),
             os.path.join(CSRC, "jet_table.inc"), os.path.join(CSRC, "jpeg_tables.inc"), os.path.join(CSRC, "jpeg_decode_common.h"),
-            os.path.join(CSRC, "jpeg_sync_steps.h"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
+            os.path.join(CSRC, "jpeg_sync_steps.h"), os.path.join(CSRC, "deflate_code.h"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
     deps = srcs + hdrs
     if not force and os.path.exists(LIB_PATH) and all(
             os.path.getmtime(LIB_PATH) >= os.path.getmtime(d) for d in deps):
@@ -198,6 +198,13 @@ def lib():
     L.vfml_jpeg_decode_sync_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int]
     L.vfml_jpeg_decode_rgb_sync.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    for fn in (L.vfml_deflate_capacity, L.vfml_deflate_workspace_bytes, L.vfml_inflate_workspace_bytes):
+        fn.restype = c_int64
+        fn.argtypes = [c_int64, c_int]
+    L.vfml_deflate_huffman.argtypes = [c_void_p, c_int64, c_int, ctypes.c_uint32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                       c_void_p, c_void_p]
+    L.vfml_inflate_chunks.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, ctypes.c_uint32, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
@@ -218,6 +225,8 @@ EXPORTS = [
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
     "vfml_jpeg_decode_workspace_bytes", "vfml_jpeg_decode_rgb",
     "vfml_jpeg_decode_sync_workspace_bytes", "vfml_jpeg_decode_rgb_sync",
+    "vfml_deflate_capacity", "vfml_deflate_workspace_bytes", "vfml_deflate_huffman",
+    "vfml_inflate_workspace_bytes", "vfml_inflate_chunks",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -1207,3 +1216,115 @@ def flow_correct(frame1, frame2, flow, lod, twiddles, good_threshold, fine_thres
                                c_void_p(counts.data_ptr()), None if records is None else c_void_p(records.data_ptr()),
                                cap, c_void_p(ws.data_ptr()), nbytes, _stream()), "vfml_flow_correct")
     return out, counts
+
+
+# -- deflate / inflate of flow-cache members ---------------------------------------------------
+_DEFLATE_WS = {}
+_INFLATE_WS = {}
+INFLATE_ERRORS = ((1, "bits that are no code of the block's table"), (2, "a length / distance symbol"),
+                  (4, "a chunk that decodes to the wrong length"), (8, "a chunk's bits ran out"),
+                  (16, "a bad stored-block length"), (32, "chunk offsets outside the data, or an oversized chunk"))
+
+
+def deflate_capacity(raw_bytes, chunk_bytes=32768):
+    """Bytes that hold the deflate stream of any raw_bytes bytes (vfml_deflate_capacity); 0: not coded on the device."""
+    return int(lib().vfml_deflate_capacity(int(raw_bytes), int(chunk_bytes)))
+
+
+def deflate_chunks(raw_bytes, chunk_bytes=32768):
+    return (int(raw_bytes) + int(chunk_bytes) - 1) // int(chunk_bytes)
+
+
+def _as_bytes(t, who):
+    if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.numel() >= 1):
+        raise ValueError(f"{who}: a non-empty contiguous device tensor expected")
+    return t.numel() * t.element_size()
+
+
+def deflate(tensor, chunk_bytes=32768, crc_init=0, out=None):
+    """The bytes of a contiguous device tensor (a slice of a larger buffer included, any alignment) -> (stream, cells):
+    their literals-only deflate stream in chunks of chunk_bytes (vfml_deflate_huffman:
+    stream-ordered, no synchronisation) in a uint8 device tensor, and an int32 device tensor of uint32 values
+    [stream length, CRC-32 continued from crc_init, offset of chunk 0, 1, ...].  deflate_stream reads them back.
+    out: a contiguous uint8 device tensor that receives the stream - its size is the capacity, nothing is written past
+    it; None: one of the worst-case size is allocated.  The workspace is kept per device, size and stream."""
+    nbytes = _as_bytes(tensor, "deflate")
+    L = lib()
+    cap = int(L.vfml_deflate_capacity(nbytes, int(chunk_bytes)))
+    if cap == 0:
+        raise ValueError(f"deflate: {nbytes} bytes in chunks of {chunk_bytes} are not coded on the device (chunk_bytes a power "
+                         f"of two 1024..32768, below 2 GiB, at most 16000 chunks)")
+    stream = torch.cuda.current_stream().cuda_stream
+    key = (tensor.device.index, nbytes, int(chunk_bytes), stream)
+    ws = _DEFLATE_WS.get(key)
+    if ws is None:
+        ws = _DEFLATE_WS[key] = torch.empty(int(L.vfml_deflate_workspace_bytes(nbytes, int(chunk_bytes))), dtype=torch.uint8,
+                                            device=tensor.device)
+    if out is None:
+        out = torch.empty(cap, dtype=torch.uint8, device=tensor.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == tensor.device and out.dim() == 1
+              and out.is_contiguous()):
+        raise ValueError("deflate: out must be a contiguous one-dimensional uint8 tensor on the input's device")
+    n = deflate_chunks(nbytes, chunk_bytes)
+    cells = torch.empty(2 + n, dtype=torch.int32, device=tensor.device)
+    base = cells.data_ptr()
+    _check(L.vfml_deflate_huffman(c_void_p(tensor.data_ptr()), nbytes, int(chunk_bytes), int(crc_init) & 0xFFFFFFFF,
+                                  c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), out.numel(), c_void_p(base + 8),
+                                  c_void_p(base), c_void_p(base + 4), _stream()), "vfml_deflate_huffman")
+    return out, cells
+
+
+def deflate_stream(stream, cells):
+    """(stream bytes, crc, [chunk offsets]) of a deflate result on the host (synchronises).  A stream that did not fit
+    its tensor raises and names the size it needs."""
+    host = [int(v) & 0xFFFFFFFF for v in cells.cpu().tolist()]
+    if host[0] > stream.numel():
+        raise RuntimeError(f"deflate: the stream needs {host[0]} bytes, its buffer holds {stream.numel()}")
+    return stream[:host[0]].cpu().numpy().tobytes(), host[1], host[2:]
+
+
+def inflate(data, offsets, chunk_bytes, raw_bytes, crc_init=0, out=None):
+    """A chunked deflate stream -> (raw, cells): data, a contiguous one-dimensional uint8 device tensor (a slice
+    included), whose chunk i starts at offsets[i] (a sequence, or an int32 device tensor) and decodes to chunk_bytes raw
+    bytes (the last one to the rest of raw_bytes); raw: uint8 device tensor [raw_bytes] (out, when given), cells: int32
+    device tensor [CRC-32 continued from crc_init, status] (vfml_inflate_chunks: stream-ordered, no synchronisation
+    once the offsets are on the device).  inflate_check reads the cells."""
+    if not (torch.is_tensor(data) and data.is_cuda and data.dtype == torch.uint8 and data.dim() == 1 and data.is_contiguous()):
+        raise ValueError("inflate: data must be a contiguous one-dimensional uint8 device tensor")
+    L = lib()
+    raw_bytes, chunk_bytes = int(raw_bytes), int(chunk_bytes)
+    need = int(L.vfml_inflate_workspace_bytes(raw_bytes, chunk_bytes))
+    if need == 0:
+        raise ValueError(f"inflate: {raw_bytes} bytes in chunks of {chunk_bytes} are not decoded on the device")
+    n = deflate_chunks(raw_bytes, chunk_bytes)
+    if not torch.is_tensor(offsets):
+        offsets = torch.tensor([int(o) - (1 << 32) if int(o) >= (1 << 31) else int(o) for o in offsets], dtype=torch.int32).to(data.device)
+    if not (offsets.is_cuda and offsets.dtype == torch.int32 and offsets.is_contiguous() and offsets.numel() == n):
+        raise ValueError(f"inflate: {n} chunk offsets expected (int32, on the device)")
+    stream = torch.cuda.current_stream().cuda_stream
+    key = (data.device.index, raw_bytes, chunk_bytes, stream)
+    ws = _INFLATE_WS.get(key)
+    if ws is None:
+        ws = _INFLATE_WS[key] = torch.empty(need, dtype=torch.uint8, device=data.device)
+    if out is None:
+        out = torch.empty(raw_bytes, dtype=torch.uint8, device=data.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == data.device and out.dim() == 1
+              and out.is_contiguous() and out.numel() == raw_bytes):
+        raise ValueError(f"inflate: out must be a contiguous uint8 tensor [{raw_bytes}] on the data's device")
+    cells = torch.empty(2, dtype=torch.int32, device=data.device)
+    # (an empty tensor's data_ptr is 0: the library wants a pointer, and reads nothing through it when data_bytes is 0)
+    dptr = data.data_ptr() if data.numel() else ws.data_ptr()
+    _check(L.vfml_inflate_chunks(c_void_p(dptr), data.numel(), c_void_p(offsets.data_ptr()), n, chunk_bytes, raw_bytes,
+                                 int(crc_init) & 0xFFFFFFFF, c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()),
+                                 c_void_p(cells.data_ptr()), c_void_p(cells.data_ptr() + 4), _stream()), "vfml_inflate_chunks")
+    return out, cells
+
+
+def inflate_check(cells, crc=None):
+    """Reads an inflate result's cells (synchronises): a damaged stream raises, so does a CRC other than `crc`; -> crc."""
+    got, status = (int(v) & 0xFFFFFFFF for v in cells.cpu().tolist())
+    if status:
+        raise RuntimeError("inflate: damaged stream: " + "; ".join(text for bit, text in INFLATE_ERRORS if status & bit))
+    if crc is not None and got != (int(crc) & 0xFFFFFFFF):
+        raise RuntimeError(f"inflate: CRC-32 {got:08x}, the archive says {int(crc) & 0xFFFFFFFF:08x}")
+    return got

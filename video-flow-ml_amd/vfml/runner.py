@@ -322,7 +322,8 @@ class _Unpacker(threading.Thread):
 
 
 def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, group=None, on_field=None,
-                collect=True, num_lods=0, chunk=None, feeder=None, prepare_only=False, local_sink=None, out=None):
+                collect=True, num_lods=0, chunk=None, feeder=None, prepare_only=False, local_sink=None, out=None,
+                device_npz=None):
     """Compute the flow field of every frame in `frame_indices` of the device-resident uint8 clip [F,H,W,3]
     (`clip` may be None when a ClipFeeder is given: its clip is used and fed as the job advances).
     Returns on rank 0 a float32 numpy array [len(frame_indices), H, W, 2] (None with collect=False, when the
@@ -334,6 +335,10 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     to the reference's loop).
     `local_sink(k, field, lods)` (whole-frame jobs only; excludes collect / on_field): called on EVERY rank for that
     rank's own fields - no collective, nothing funnels into rank 0 (the CLI's per-rank cache writers).
+    `device_npz` (a storage.device_npz.DeviceNpzWriter; GPU whole-frame jobs, in place of local_sink): every rank's fields
+    and LOD levels are deflated on the device behind the kernels that made them (`device_npz.submit(k, [field, lod1, ...])`)
+    and never come to the host uncompressed; the writer's own sink receives the finished member streams.  The caller calls
+    `device_npz.finish()` after the job.
     prepare_only: allocate the job's staging buffers (kept for later jobs of the same geometry) and return.
     out: optional result array (rank 0, with collect): float32 [len(frame_indices), H, W, 2], filled and returned instead of a
     fresh one - a caller that times the job hands in memory it has already touched (at 8 ranks x 41 fields/s the result
@@ -345,9 +350,11 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     tiles = _tiles(proc, W, H, tile_mode)
     whole = len(tiles) == 1
     on_gpu = clip.is_cuda
-    local = local_sink is not None
+    local = local_sink is not None or device_npz is not None
     if local and (not whole or collect or on_field is not None):
         raise ValueError("local_sink applies to whole-frame jobs and replaces collect / on_field")
+    if device_npz is not None and (local_sink is not None or not on_gpu):
+        raise ValueError("device_npz applies to GPU jobs and replaces local_sink")
     lods_on = num_lods > 1 and whole and on_gpu
     lshapes = lod_shapes(H, W, num_lods) if lods_on else []
     items = tile_items(frame_indices, len(tiles))
@@ -368,7 +375,7 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     dev = clip.device
     nb = min(NBUF, n_chunks)
     gather = world > 1 and not local
-    sink_here = local or rank == 0                          # this rank brings chunks to its host memory
+    sink_here = (local or rank == 0) and device_npz is None     # this rank brings chunks to its host memory
     hworld = world if gather else 1                         # ranks per host chunk buffer
     send = [_buffer(f"send{i}", (K, slot), dev) for i in range(nb)]
     recv = host = None
@@ -426,12 +433,17 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
                 row = sbuf[j]
                 n = H * W * 2
                 row[:n].copy_(flow.reshape(-1))
+                levels = [row[:n].view(H, W, 2)]
                 if lods_on:
                     from . import hip
                     off = n
                     for lvl in hip.flow_lods(row[:n].view(H, W, 2), num_lods)[1:]:
                         row[off:off + lvl.numel()].copy_(lvl.reshape(-1))
+                        levels.append(row[off:off + lvl.numel()].view(lvl.shape))
                         off += lvl.numel()
+                if device_npz is not None:
+                    # (the row is rewritten NBUF chunks later, on this stream: behind the kernels queued here)
+                    device_npz.submit(slot_of[part[j][0]], levels)
         else:
             for j, (f, t) in enumerate(part):
                 feed(f, f)
