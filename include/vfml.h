@@ -29,7 +29,8 @@ extern "C" {
 
 /* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3, vfml_resize_u8 and the vfml_jpeg_*
  * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
- * the number did not move. */
+ * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
+ * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420. */
 #define VFML_ABI_VERSION 26
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -618,6 +619,34 @@ int64_t vfml_jpeg_decode_sync_workspace_bytes(int h, int w, int64_t scan_bytes, 
 int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
                               const unsigned char* qtables, const int32_t* tables, int y0, int y1, int subseq_bytes,
                               void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
+
+/* Both decoders for the other samplings a baseline file may have ("Samplings";
+ * tests/jpeg_sampling_oracle.py is the definition).  Entropy decoding, IDCT and colour conversion are those above; the
+ * sampling sets the MCU and the chroma filter:
+ *   VFML_JPEG_420   2x2 / 1x1 / 1x1   MCU 16x16   Y00 Y01 Y10 Y11 Cb Cr   h2v2 triangle filter, as above
+ *   VFML_JPEG_422   2x1 / 1x1 / 1x1   MCU 16x8    Y0 Y1 Cb Cr             libjpeg's h2v1 "fancy" filter per row:
+ *                   out[2c] = (3 C[c] + C[c-1] + 1) >> 2, out[2c+1] = (3 C[c] + C[c+1] + 2) >> 2 (columns clamped); where
+ *                   the chroma plane is at most 2 samples wide (w <= 4) every sample is repeated instead, as libjpeg does
+ *   VFML_JPEG_444   1x1 / 1x1 / 1x1   MCU 8x8     Y Cb Cr                 no filter
+ *   VFML_JPEG_GREY  one component, whatever factors its header names: a scan that is not interleaved (T.81 A.2.2), an
+ *                   MCU is one block, ceil(h/8) x ceil(w/8) of them, Ri counts blocks; the picture is R = G = B = Y.
+ *                   tables[0], tables[1] select its Huffman tables and qtables[0..63] is its table; the other entries
+ *                   are not read
+ * Chroma planes are ceil(h V / Vmax) x ceil(w H / Hmax).  Only 4:2:0 has a vertical filter: for the other samplings a row
+ * window reads the intervals of its luma rows alone.  Every other argument, the status bits and the guarantees on a
+ * damaged scan are those of vfml_jpeg_decode_rgb and vfml_jpeg_decode_rgb_sync, which are these with VFML_JPEG_420 and
+ * give the bytes they always gave.  A sampling outside the enum returns non-zero (vfml_last_error) and launches nothing;
+ * the workspace functions return 0 for it.  A workspace sized for one sampling does not fit another. */
+enum { VFML_JPEG_420 = 0, VFML_JPEG_422 = 1, VFML_JPEG_444 = 2, VFML_JPEG_GREY = 3 };
+int64_t vfml_jpeg_decode_sampled_workspace_bytes(int h, int w, int sampling, int64_t scan_bytes);
+int vfml_jpeg_decode_rgb_sampled(const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                                 int restart_interval, const unsigned char* qtables, const int32_t* tables, int y0, int y1,
+                                 void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream);
+int64_t vfml_jpeg_decode_sync_sampled_workspace_bytes(int h, int w, int sampling, int64_t scan_bytes, int subseq_bytes);
+int vfml_jpeg_decode_rgb_sync_sampled(const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                                      int restart_interval, const unsigned char* qtables, const int32_t* tables, int y0,
+                                      int y1, int subseq_bytes, void* workspace, unsigned char* rgb, int64_t row_stride,
+                                      int32_t* status, void* stream);
 
 /* Deflate / inflate of the flow cache's .npz members (tests/deflate_oracle.py is the definition of
  * the stream, vfml/csrc/deflate_code.h of its code lengths).  The raw bytes are cut into chunks of chunk_bytes (a power of

@@ -16,7 +16,12 @@ separate run under the profiler, whose tracing slows the host:
 ffmpeg's MJPG writers leave it) at 1920x1080 and 1920x2160, and every window measures, one after the other on the same
 bytes, the self-synchronising kernel (`--plan sync`) at each `--subseq` size, the interval
 kernel (`--plan interval`: one wave walks the whole scan; `--interval-calls` decodes per window) and one Pillow decode.
-`--plan` picks one of the two kernels."""
+`--plan` picks one of the two kernels.
+
+`--sampling 4:2:0,4:2:2,4:4:4,grey` (any of them): Pillow's files of the scene in those samplings at quality 95 (1920x1080, or
+`--size`), each written twice - one MCU row per restart interval for the interval kernel, no markers for the
+self-synchronising kernel at its default subsequence size - and every window measures every sampling and both kernels
+one after the other, so the figures of a run stand beside each other; `--plan` picks one kernel."""
 import argparse
 import io
 import json
@@ -87,6 +92,59 @@ def norestart(args, hip, jpeg_parse, Image):
     return 0
 
 
+def pillow_sampled(Image, img, sampling, **kw):
+    buf = io.BytesIO()
+    if sampling == "grey":
+        Image.fromarray(img, "RGB").convert("L").save(buf, format="JPEG", quality=95, **kw)
+    else:
+        Image.fromarray(img, "RGB").save(buf, format="JPEG", quality=95, subsampling=sampling, **kw)
+    return buf.getvalue()
+
+
+def sampled(args, hip, jpeg_parse, Image):
+    if Image is None:
+        raise SystemExit("jpeg_decode_bench --sampling: the files are Pillow's; Pillow is not installed")
+    names = args.sampling.split(",")
+    for name in names:
+        if name not in jpeg_parse.DEVICE_SAMPLINGS:
+            raise SystemExit(f"jpeg_decode_bench --sampling {name}: one of {', '.join(jpeg_parse.DEVICE_SAMPLINGS)}")
+    w, h = (int(v) for v in args.size.lower().split("x")) if args.size else (1920, 1080)
+    img = picture(w, h)
+    rgb = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    configs, out = [], {"calls_per_window": args.calls, "size": f"{w}x{h}"}
+    for name in names:
+        for plan, kw in (("interval", dict(restart_marker_rows=1)), ("sync", {})):
+            if args.plan not in (None, plan):
+                continue
+            data = pillow_sampled(Image, img, name, **kw)
+            info = jpeg_parse.parse(data, jpeg_parse.DEVICE_SAMPLINGS)
+            assert info.sampling == name and jpeg_parse.decode_plan(info) == plan
+            dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+            for _ in range(3):
+                _, status = hip.jpeg_decode(dev, out=rgb, info=info, plan=plan)
+            hip.jpeg_decode_check(status)
+            same = bool(np.array_equal(rgb.cpu().numpy(), np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))))
+            configs.append((f"{name} {plan}", dev, info, plan))
+            out[f"{name} {plan}"] = {"us_windows": [], "same_bytes": same, "file_bytes": len(data), "intervals": info.intervals}
+    for _ in range(args.windows):
+        for key, dev, info, plan in configs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.calls):
+                hip.jpeg_decode(dev, out=rgb, info=info, plan=plan)
+            e1.record()
+            torch.cuda.synchronize()
+            out[key]["us_windows"].append(e0.elapsed_time(e1) / args.calls * 1e3)
+    print(f"{w}x{h}, Pillow's files at quality 95")
+    for key, *_ in configs:
+        us = out[key]["us_windows"]
+        out[key]["us_median"] = statistics.median(us)
+        print(f"  {key:16s} {statistics.median(us):10.1f} us per picture (windows {min(us):.1f} .. {max(us):.1f}); file "
+              f"{out[key]['file_bytes'] / 1e6:.3f} MB; same bytes: {out[key]['same_bytes']}")
+    print(json.dumps(out))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20)
@@ -97,6 +155,8 @@ def main(argv=None):
     ap.add_argument("--plan", default=None, choices=["interval", "sync"], help="with --restart 0: that kernel only")
     ap.add_argument("--subseq", default="64,128,256", help="with --restart 0: the sync kernel's subsequence sizes")
     ap.add_argument("--interval-calls", type=int, default=2)
+    ap.add_argument("--sampling", default=None, help="comma-separated, of 4:2:0 4:2:2 4:4:4 grey: Pillow's files in those "
+                    "samplings, both kernels")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_decode_bench: needs a GPU; nothing is measured without one")
@@ -106,6 +166,8 @@ def main(argv=None):
         from PIL import Image
     except ImportError:
         Image = None
+    if args.sampling:
+        return sampled(args, hip, jpeg_parse, Image)
     if args.restart == 0:
         return norestart(args, hip, jpeg_parse, Image)
     cases = [(*(int(v) for v in args.size.lower().split("x")), None)] if args.size else CASES

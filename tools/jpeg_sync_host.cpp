@@ -5,7 +5,8 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -I video-flow-ml_amd/vfml/csrc tools/jpeg_sync_host.cpp -o jpeg_sync_host
 //   jpeg_sync_host case.bin [case.bin ...]
 //
-// A case file is little-endian int32 h, w, restart interval, subsequence bytes, scan bytes, then the 392 int32 of
+// A case file is little-endian int32 h, w, restart interval, subsequence bytes | sampling << 16 (0: 4:2:0, 1: 4:2:2,
+// 2: 4:4:4, 3: grey, as VFML_JPEG_* of include/vfml.h), scan bytes, then the 392 int32 of
 // storage.jpeg_parse.decode_tables, then the scan.  Per case it prints "status <bits>", "subsequences <n>" and one line
 // of 64 coefficients (natural order, DC values summed) per block.
 #include <cstdio>
@@ -34,9 +35,9 @@ static int run(const char* path) {
     std::fclose(f);
     return 2;
   }
-  const int h = head[0], w = head[1], dri = head[2], S = head[3];
+  const int h = head[0], w = head[1], dri = head[2], S = head[3] & 0xFFFF, samp = (int)((uint32_t)head[3] >> 16);
   const int64_t n = head[4];
-  if (h < 1 || w < 1 || h > 65535 || w > 65535 || dri < 0 || n < 0 || S < 16 || S > 1024 || (S & (S - 1))) {
+  if (samp > 3 || h < 1 || w < 1 || h > 65535 || w > 65535 || dri < 0 || n < 0 || S < 16 || S > 1024 || (S & (S - 1))) {
     std::fprintf(stderr, "jpeg_sync_host: %s: bad header\n", path);
     std::fclose(f);
     return 2;
@@ -49,7 +50,10 @@ static int run(const char* path) {
   }
   std::fclose(f);
 
-  const int nmcu = ((h + 15) / 16) * ((w + 15) / 16);
+  // the MCU: 16x16 / 16x8 / 8x8 / 8x8 pixels, nb blocks of which the first ny are luma
+  const int mw = samp <= 1 ? 16 : 8, mh = samp == 0 ? 16 : 8;
+  const int nb = samp == 0 ? 6 : samp == 1 ? 4 : samp == 2 ? 3 : 1, ny = nb == 1 ? 1 : nb - 2;
+  const int nmcu = ((h + mh - 1) / mh) * ((w + mw - 1) / mw);
   const int ri = dri > 0 ? dri : nmcu;
   const int nint = (nmcu + ri - 1) / ri;
   int status = 0;
@@ -64,14 +68,14 @@ static int run(const char* path) {
     }
   if (rank + 1 != (uint32_t)nint) status |= js::kErrCount;
 
-  std::vector<int16_t> coef((size_t)nmcu * 6 * 64, 0);
+  std::vector<int16_t> coef((size_t)nmcu * nb * 64, 0);
   const int64_t N = n > 0 ? (n + S - 1) / S : 1;
   if (status == 0) {
     js::Tabs* tabs = new js::Tabs;
     js::tabs_fill(*tabs, tables.data(), kZigzag, 0, 1);
     js::Ctx c;
     c.scan = scan.data(), c.n = (uint32_t)n, c.mpos = mpos.data(), c.nmark = (uint32_t)mpos.size();
-    c.ri = ri, c.nmcu = nmcu, c.S = S;
+    c.ri = ri, c.nmcu = nmcu, c.S = S, c.nb = nb, c.ny = ny;
     std::vector<js::Rec> rec((size_t)N);
     // speculate
     for (int64_t i = 0; i < N; ++i) {
@@ -101,9 +105,9 @@ static int run(const char* path) {
     for (int m0 = 0; m0 < nmcu; m0 += ri) {
       int32_t pred[3] = {0, 0, 0};
       for (int m = m0; m < m0 + ri && m < nmcu; ++m)
-        for (int b = 0; b < 6; ++b) {
-          int16_t& dc = coef[((size_t)m * 6 + b) * 64];
-          int32_t& p = pred[b < 4 ? 0 : b - 3];
+        for (int b = 0; b < nb; ++b) {
+          int16_t& dc = coef[((size_t)m * nb + b) * 64];
+          int32_t& p = pred[b < ny ? 0 : b - ny + 1];
           p = (int32_t)((uint32_t)p + (uint32_t)(int32_t)dc);
           dc = (int16_t)(uint16_t)((uint32_t)p & 0xFFFFu);
         }
@@ -111,7 +115,7 @@ static int run(const char* path) {
     delete tabs;
   }
   std::printf("case %s\nstatus %d\nsubsequences %lld\n", path, status, (long long)N);
-  for (size_t blk = 0; blk < (size_t)nmcu * 6; ++blk) {
+  for (size_t blk = 0; blk < (size_t)nmcu * nb; ++blk) {
     for (int k = 0; k < 64; ++k) std::printf(k ? " %d" : "%d", (int)coef[blk * 64 + k]);
     std::printf("\n");
   }

@@ -276,13 +276,13 @@ class _ExternalFlowSource:
     def _read(self):
         """-> the picture [h,w,3] uint8; or (file bytes, JpegInfo): a JPEG the device decodes; or None: no new picture."""
         if self.files:
-            from storage.jpeg_parse import JpegUnsupported, parse
+            from storage.jpeg_parse import DEVICE_SAMPLINGS, JpegUnsupported, parse
             data = self.video.read_chunk()
             if data is None or (not data and self._seen):
                 return None
             self._seen = True
             try:
-                info = parse(data)
+                info = parse(data, DEVICE_SAMPLINGS)
                 if (info.h, info.w) == (self.video.height, self.video.width):
                     return data, info
             except JpegUnsupported:

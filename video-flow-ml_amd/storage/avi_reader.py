@@ -237,15 +237,16 @@ def _read_frames_device(path, start, count, device):
     """read_frames with an MJPG stream's frames decoded on `device` (storage/device_mjpg.py DeviceMjpgDecoder); None:
     the file is not for it - no MJPG stream, or a first frame the device decoder does not take.  Later frames of that
     kind, and frames whose scan turns out damaged, go to Pillow one by one.  A frame without restart intervals (Pillow's,
-    OpenCV's, ffmpeg's) is decoded on the device like any other, by the kernel jpeg_parse.decode_plan names."""
+    OpenCV's, ffmpeg's) is decoded on the device like any other, by the kernel jpeg_parse.decode_plan names; so are
+    4:2:2, 4:4:4 and grey frames (jpeg_parse.DEVICE_SAMPLINGS), which a stream may mix."""
     import torch
 
     from .device_mjpg import DeviceMjpgDecoder
-    from .jpeg_parse import JpegUnsupported, parse
+    from .jpeg_parse import DEVICE_SAMPLINGS, JpegUnsupported, parse
 
     def parsed(chunk):
         try:
-            return parse(chunk)
+            return parse(chunk, DEVICE_SAMPLINGS)
         except JpegUnsupported:
             return None
 

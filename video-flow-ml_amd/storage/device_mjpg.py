@@ -8,7 +8,8 @@ cell is copied to pinned memory; one frame later the host reads it and copies ex
 that already holds the file header; one frame after that the slot - header, scan, EOI - is appended to the AVI.  The
 host therefore never waits for the frame the GPU is working on, and never copies the worst-case capacity.
 
-DeviceMjpgDecoder is its mirror for the MJPG frames that are read (vfml_jpeg_decode_rgb): the
+DeviceMjpgDecoder is its mirror for the MJPG frames that are read (vfml_jpeg_decode_rgb_sampled, DESIGN.md section 13;
+4:2:0, 4:2:2, 4:4:4 and grey frames, in any mix): the
 file's bytes go up through a small ring of pinned slots, the picture is decoded where it is used, and the status cell of
 a frame comes back and is looked at while the next frame is on its way.
 """
@@ -114,7 +115,7 @@ class DeviceMjpgDecoder:
         file that the rule gives to 'interval')."""
         from storage import jpeg_parse
         if info is None:
-            info = jpeg_parse.parse(data)
+            info = jpeg_parse.parse(data, jpeg_parse.DEVICE_SAMPLINGS)
         s = self._frames % len(self._host)
         self._frames += 1
         if self._event[s] is not None:

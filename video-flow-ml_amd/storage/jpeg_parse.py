@@ -3,9 +3,10 @@ section 13).  Pure Python, no Pillow; only the segments in front of the scan are
 located, never read.
 
 Accepted: baseline sequential DCT (SOF0), 8-bit samples, three components sampled 2x2 / 1x1 / 1x1 in one interleaved
-scan, 8-bit quantisation tables, Huffman tables from the file (a file without DHT gets the T.81 Annex K tables of
-storage/jpeg_tables.py, the MJPG "AVI1" convention), any restart interval.  APPn and COM are skipped.  Anything else
-raises JpegUnsupported with a message that names it.
+scan - with parse(data, DEVICE_SAMPLINGS) also 2x1 / 1x1 / 1x1 (4:2:2), 1x1 / 1x1 / 1x1 (4:4:4) and one component
+(grey, any factors) - 8-bit quantisation tables, Huffman tables from the file (a file without DHT gets the T.81 Annex
+K tables of storage/jpeg_tables.py, the MJPG "AVI1" convention), any restart interval.  APPn and COM are skipped.
+Anything else raises JpegUnsupported with a message that names it.
 """
 from dataclasses import dataclass
 
@@ -22,16 +23,17 @@ class JpegUnsupported(ValueError):
 class JpegInfo:
     h: int
     w: int
-    qtables: np.ndarray          # uint8 [3, 64]: the quantisation table of Y, Cb, Cr, natural (row-major) order
+    qtables: np.ndarray          # uint8 [3, 64]: the quantisation table of Y, Cb, Cr, natural (row-major) order (grey: Y's x 3)
     huffman: tuple               # (BITS, HUFFVAL) of DC0, AC0, DC1, AC1 (None: not in the file and not used)
-    selectors: tuple             # ((dc, ac) table id of Y, of Cb, of Cr)
+    selectors: tuple             # ((dc, ac) table id of Y, of Cb, of Cr); grey: of Y alone
     restart_interval: int        # Ri in MCUs, 0: the scan is one interval
     scan: tuple                  # (start, end) of the entropy-coded data in the file's bytes
     annex_k: bool                # the file holds no DHT segment: the Annex K tables were supplied
+    sampling: str = "4:2:0"      # one of DEVICE_SAMPLINGS
 
     @property
     def mcu_grid(self):
-        return jt.mcu_grid(self.h, self.w)
+        return jt.mcu_grid(self.h, self.w, self.sampling)
 
     @property
     def intervals(self):
@@ -45,6 +47,9 @@ _SOF_NAMES = {0xC1: "extended sequential DCT (SOF1)", 0xC2: "progressive DCT (SO
               0xCB: "arithmetic coding (SOF11)", 0xCD: "arithmetic coding (SOF13)", 0xCE: "arithmetic coding (SOF14)",
               0xCF: "arithmetic coding (SOF15)", 0xCC: "arithmetic coding (DAC)"}
 _NATURAL = np.array(jt.ZIGZAG)
+DEVICE_SAMPLINGS = ("4:2:0", "4:2:2", "4:4:4", "grey")      # what the device kernels take
+_FACTORS = {(0x22, 0x11, 0x11): "4:2:0", (0x21, 0x11, 0x11): "4:2:2", (0x11, 0x11, 0x11): "4:4:4"}
+_FACTOR_TEXT = {"4:2:0": "2x2 / 1x1 / 1x1 (4:2:0)", "4:2:2": "2x1 / 1x1 / 1x1 (4:2:2)", "4:4:4": "1x1 / 1x1 / 1x1 (4:4:4)"}
 
 
 def _check_huffman(bits, vals, what):
@@ -58,8 +63,11 @@ def _check_huffman(bits, vals, what):
         raise JpegUnsupported(f"JPEG: {what} holds {len(vals)} symbols for {sum(bits)} codes")
 
 
-def parse(data):
-    """bytes of a JPEG file -> JpegInfo; JpegUnsupported for anything the device decoder does not take."""
+def parse(data, samplings=("4:2:0",)):
+    """bytes of a JPEG file -> JpegInfo; JpegUnsupported for anything the device decoder does not take.  samplings: the
+    kinds of frame the caller takes, of DEVICE_SAMPLINGS; a file of another kind is refused."""
+    samplings = tuple(samplings)
+    colour = [s for s in DEVICE_SAMPLINGS[:3] if s in samplings]
     if not isinstance(data, (bytes, bytearray)):
         data = bytes(data)
     n = len(data)
@@ -98,20 +106,27 @@ def parse(data):
             p, h, w, nf = seg[0], (seg[1] << 8) | seg[2], (seg[3] << 8) | seg[4], seg[5]
             if p != 8:
                 raise JpegUnsupported(f"JPEG: {p}-bit sample precision is not built; 8-bit only")
-            if nf != 3:
-                raise JpegUnsupported(f"JPEG: {nf} component(s); three (Y Cb Cr) only")
+            if nf != 3 and not (nf == 1 and "grey" in samplings):
+                raise JpegUnsupported(f"JPEG: {nf} component(s); three (Y Cb Cr) "
+                                      + ("or one (grey) only" if "grey" in samplings else "only"))
             if len(seg) != 6 + 3 * nf:
                 raise JpegUnsupported("JPEG: SOF0 segment length does not fit its components")
             if h == 0:
                 raise JpegUnsupported("JPEG: zero lines in the frame header (DNL) is not built")
             if w == 0:
                 raise JpegUnsupported("JPEG: zero samples per line")
-            comps = [(seg[6 + 3 * c], seg[7 + 3 * c], seg[8 + 3 * c]) for c in range(3)]
-            sampling = [c[1] for c in comps]
-            if sampling != [0x22, 0x11, 0x11]:
-                raise JpegUnsupported("JPEG: sampling factors " + " / ".join(f"{s >> 4}x{s & 15}" for s in sampling)
-                                      + "; 2x2 / 1x1 / 1x1 (4:2:0) only")
-            frame = (h, w, comps)
+            comps = [(seg[6 + 3 * c], seg[7 + 3 * c], seg[8 + 3 * c]) for c in range(nf)]
+            factors = tuple(c[1] for c in comps)
+            kind = "grey" if nf == 1 else _FACTORS.get(factors)
+            if nf == 1:
+                if not (1 <= factors[0] >> 4 <= 4 and 1 <= factors[0] & 15 <= 4):
+                    raise JpegUnsupported(f"JPEG: sampling factors {factors[0] >> 4}x{factors[0] & 15} outside 1..4")
+            elif kind not in samplings:
+                said = "JPEG: sampling factors " + " / ".join(f"{s >> 4}x{s & 15}" for s in factors)
+                if factors[1] != factors[2] and len(colour) > 1:     # the one-sampling call keeps its wording
+                    said += ": chroma components whose factors differ from each other are not built"
+                raise JpegUnsupported(said + "; " + ", ".join(_FACTOR_TEXT[s] for s in colour) + " only")
+            frame = (h, w, comps, kind)
         elif m == 0xDB:
             at = 0
             while at < len(seg):
@@ -149,22 +164,22 @@ def parse(data):
             if frame is None:
                 raise JpegUnsupported("JPEG: a scan before the frame header")
             ns = seg[0] if seg else 0
-            if ns != 3:
+            if ns != len(frame[2]):
                 raise JpegUnsupported(f"JPEG: a scan of {ns} component(s): several scans are not built; one "
                                       f"interleaved scan of Y Cb Cr only")
             if len(seg) != 1 + 2 * ns + 3:
                 raise JpegUnsupported("JPEG: SOS segment length does not fit its components")
             sel = []
-            for c in range(3):
+            for c in range(ns):
                 cid, tables = seg[1 + 2 * c], seg[2 + 2 * c]
                 if cid != frame[2][c][0]:
                     raise JpegUnsupported("JPEG: the scan's components are not in the frame's order Y Cb Cr")
                 sel.append((tables >> 4, tables & 15))
-            if (seg[7], seg[8], seg[9]) != (0, 63, 0):
+            if tuple(seg[1 + 2 * ns:]) != (0, 63, 0):
                 raise JpegUnsupported("JPEG: spectral selection / successive approximation in a sequential scan")
             break
         # APPn, COM and anything else with a length: skipped
-    h, w, comps = frame
+    h, w, comps, kind = frame
     if not dht_seen:
         huff = {k: t for k, t in enumerate(jt.HUFFMAN)}
     for c, (td, ta) in enumerate(sel):
@@ -176,9 +191,9 @@ def parse(data):
     end = data.find(jt.EOI, i)
     if end < 0:
         end = n
-    return JpegInfo(h=h, w=w, qtables=np.stack([quant[c[2]] for c in comps]),
+    return JpegInfo(h=h, w=w, qtables=np.stack([quant[c[2]] for c in (comps * 3)[:3]]),
                     huffman=tuple(huff.get(k) for k in range(4)), selectors=tuple(sel), restart_interval=ri,
-                    scan=(i, end), annex_k=not dht_seen)
+                    scan=(i, end), annex_k=not dht_seen, sampling=kind)
 
 
 def huffman_lookup(table):
@@ -208,14 +223,15 @@ def decode_plan(info):
 
 
 TABLE_INTS = 8 + 4 * 96
+SAMPLING_CODE = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2, "grey": 3}      # VFML_JPEG_* of include/vfml.h
 
 
 def decode_tables(info):
-    """-> (qtables uint8 [3,64], tables int32 [392]): what vfml_jpeg_decode_rgb reads (layout in include/vfml.h):
+    """-> (qtables uint8 [3,64], tables int32 [392]): what vfml_jpeg_decode_rgb_sampled reads (layout in include/vfml.h):
     tables[2c], tables[2c+1] = index (0..3, in the order DC0 AC0 DC1 AC1) of component c's DC and AC table; from
     tables[8] on, per table 96 ints: limit[16], offset[16] (huffman_lookup) and HUFFVAL as 256 bytes."""
     t = np.zeros(TABLE_INTS, np.int32)
-    for c, (td, ta) in enumerate(info.selectors):
+    for c, (td, ta) in enumerate((info.selectors * 3)[:3]):      # grey: the unused entries hold Y's
         t[2 * c], t[2 * c + 1] = 2 * td, 2 * ta + 1
     for k, table in enumerate(info.huffman):
         limit, offset = huffman_lookup(table)

@@ -101,9 +101,15 @@ def dct_matrix():
     return np.rint(8192.0 * c * np.cos((2 * n + 1) * k * np.pi / 16)).astype(np.int64)
 
 
-def mcu_grid(h, w):
-    """(MCU rows, MCUs per row) of an h x w picture: 16 x 16 pixels each (4:2:0)."""
-    return (int(h) + 15) // 16, (int(w) + 15) // 16
+# sampling -> (MCU height, MCU width) in pixels
+MCU_SIZE = {"4:2:0": (16, 16), "4:2:2": (8, 16), "4:4:4": (8, 8), "grey": (8, 8)}
+
+
+def mcu_grid(h, w, sampling="4:2:0"):
+    """(MCU rows, MCUs per row) of an h x w picture: 16 x 16 pixels each in 4:2:0, 16 wide and 8 high in 4:2:2, 8 x 8
+    in 4:4:4 and in a one-component (grey) scan."""
+    mh, mw = MCU_SIZE[sampling]
+    return -(-int(h) // mh), -(-int(w) // mw)
 
 
 def _segment(marker, payload):

@@ -1,7 +1,10 @@
-// vfml_jpeg_decode_rgb: the decoder of the MJPG frames the drop-in reads - baseline sequential
-// DCT, 8-bit, YCbCr 4:2:0 in one interleaved scan, any Huffman tables, any restart interval.  Integer arithmetic only:
-// T.81 F.2.2 entropy decoding, libjpeg's jidctint "islow" inverse DCT, its h2v2 "fancy" chroma upsampling and its colour
-// conversion, so the picture equals libjpeg's byte for byte; tests/jpeg_decode_oracle.py is the same definition in numpy.
+// vfml_jpeg_decode_rgb, vfml_jpeg_decode_rgb_sampled: the decoder of the MJPG frames the drop-in reads (DESIGN.md
+// sections 13 and 13.2) - baseline sequential DCT, 8-bit, YCbCr 4:2:0, 4:2:2 or 4:4:4 in one interleaved scan or one grey
+// component, any Huffman tables, any restart interval.  Integer arithmetic only: T.81 F.2.2 entropy decoding, libjpeg's
+// jidctint "islow" inverse DCT, its h2v2 / h2v1 "fancy" chroma upsampling and its colour conversion, so the picture equals
+// libjpeg's byte for byte; tests/jpeg_decode_oracle.py (4:2:0) and tests/jpeg_sampling_oracle.py are the same definition
+// in numpy.  The sampling sets the blocks of an MCU (DecArgs nb, ny: uniform values of the entropy stages) and
+// instantiates the transform and the colour kernel.
 // The marker segments are read on the host (storage/jpeg_parse.py); nothing on the host looks at the entropy data.
 //
 // Five launches on one stream, no synchronisation:
@@ -13,10 +16,11 @@
 //              interval's bytes in an LDS ring, 256 at a time, the stuffed 00s removed by ballot and prefix count; the
 //              symbol chain is serial, its values wave-uniform: a code's length is the first lane whose left-aligned
 //              code limit exceeds the next 16 bits (one ballot), its symbol one LDS read.  A block is built in LDS and
-//              stored by all lanes, int16 in natural order, six per MCU.
-//   transform  one wave per MCU: dequantisation, then a lane per column and a lane per row of the six blocks for the two
+//              stored by all lanes, int16 in natural order, nb (six in 4:2:0) per MCU.
+//   transform  one wave per MCU: dequantisation, then a lane per column and a lane per row of its blocks for the two
 //              IDCT passes through LDS; 8-bit Y, Cb, Cr planes of the padded size in the workspace.
-//   colour     a lane per chroma sample of an output row: the triangle filter and the conversion of its two pixels.
+//   colour     a lane per chroma sample of an output row: the triangle filter and the conversion of its two pixels
+//              (4:4:4 and grey: a lane per pixel, no filter).
 // Bounds on a damaged stream: interval ranges are clamped to the scan, the ring is indexed modulo its size, a block reads
 // at most 64 symbols of at most 31 bits (less than the 320 bytes staged ahead), a coefficient index is checked against
 // 63 before it is used, table indices are masked to the table.  What is wrong ends in the status cell, and nothing is
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(64) void jpeg_dec_entropy_kernel(const DecArgs a) {
   unsigned char* ringbytes = reinterpret_cast<unsigned char*>(ring);
   __syncthreads();
   for (int mcu = m0; mcu < m1 && !err; ++mcu) {
-    for (int b = 0; b < 6 && !err; ++b) {
+    for (int b = 0; b < a.nb && !err; ++b) {
       // stage ahead: 256 raw bytes per step, four loads in flight
       while (wr - br.rd < (unsigned)kStageAhead && src < end) {
         unsigned raw[4];
@@ -190,7 +194,7 @@ __global__ __launch_bounds__(64) void jpeg_dec_entropy_kernel(const DecArgs a) {
       }
       blk[lane] = 0;
       __syncthreads();
-      const int comp = b < 4 ? 0 : b - 3;
+      const int comp = b < a.ny ? 0 : b - a.ny + 1;
       // DC
       {
         const int t = dc_t[comp];
@@ -250,7 +254,7 @@ __global__ __launch_bounds__(64) void jpeg_dec_entropy_kernel(const DecArgs a) {
       }
       if (!err && src >= end && 8ull * br.rd - (unsigned)br.nb > 8ull * wr) err = kErrData;
       __syncthreads();
-      if (!err) a.coef[((int64_t)mcu * 6 + b) * 64 + lane] = blk[lane];
+      if (!err) a.coef[((int64_t)mcu * a.nb + b) * 64 + lane] = blk[lane];
       __syncthreads();
     }
   }
@@ -276,8 +280,11 @@ __device__ __forceinline__ void idct_butterfly(const int* i, int* o) {
   o[2] = t12 + q, o[5] = t12 - q, o[3] = t13 + p, o[4] = t13 - p;
 }
 
+// S: the sampling.  A wave per MCU: lanes 0 .. 8 nb - 1 take a column, then a row, of its nb blocks.
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_dec_transform_kernel(const DecArgs a) {
-  __shared__ int ws[4][6][64 + 8];        // a row of 9: the column pass and the row pass both spread over the banks
+  constexpr int NB = samp_nb(S), NY = samp_ny(S), HS = samp_hs(S), VS = samp_vs(S);
+  __shared__ int ws[4][NB][64 + 8];       // a row of 9: the column pass and the row pass both spread over the banks
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int count = a.mrows * a.cols;
   int g = blockIdx.x * 4 + wave;
@@ -287,14 +294,14 @@ __global__ __launch_bounds__(256) void jpeg_dec_transform_kernel(const DecArgs a
   const int my = mcu / a.cols, mx = mcu - my * a.cols;
   const int at = (lane >> 3) * 9 + (lane & 7);
 #pragma unroll
-  for (int b = 0; b < 6; ++b) {
-    const int comp = b < 4 ? 0 : b - 3;
-    ws[wave][b][at] = (int)a.coef[((int64_t)mcu * 6 + b) * 64 + lane] * (int)a.qt[comp * 64 + lane];
+  for (int b = 0; b < NB; ++b) {
+    const int comp = b < NY ? 0 : b - NY + 1;
+    ws[wave][b][at] = (int)a.coef[((int64_t)mcu * NB + b) * 64 + lane] * (int)a.qt[comp * 64 + lane];
   }
   __syncthreads();
-  const int b = lane >> 3, j = lane & 7;  // lanes 0..47: block b, column / row j
+  const int b = lane >> 3, j = lane & 7;  // lanes 0 .. 8 NB - 1: block b, column / row j
   int in[8], out[8];
-  if (lane < 48) {
+  if (lane < 8 * NB) {
 #pragma unroll
     for (int r = 0; r < 8; ++r) in[r] = ws[wave][b][r * 9 + j];
     idct_butterfly(in, out);
@@ -302,7 +309,7 @@ __global__ __launch_bounds__(256) void jpeg_dec_transform_kernel(const DecArgs a
     for (int r = 0; r < 8; ++r) ws[wave][b][r * 9 + j] = (out[r] + 1024) >> 11;
   }
   __syncthreads();
-  if (lane < 48) {
+  if (lane < 8 * NB) {
 #pragma unroll
     for (int c = 0; c < 8; ++c) in[c] = ws[wave][b][j * 9 + c];
     idct_butterfly(in, out);
@@ -315,10 +322,10 @@ __global__ __launch_bounds__(256) void jpeg_dec_transform_kernel(const DecArgs a
     }
     if (valid) {
       unsigned char* dst;
-      if (b < 4)
-        dst = a.py + ((int64_t)my * 16 + (b >> 1) * 8 + j) * (a.cols * 16) + mx * 16 + (b & 1) * 8;
+      if (b < NY)
+        dst = a.py + ((int64_t)my * (8 * VS) + (b / HS) * 8 + j) * (a.cols * (8 * HS)) + mx * (8 * HS) + (b % HS) * 8;
       else
-        dst = (b == 4 ? a.pcb : a.pcr) + ((int64_t)my * 8 + j) * (a.cols * 8) + mx * 8;
+        dst = (b == NY ? a.pcb : a.pcr) + ((int64_t)my * 8 + j) * (a.cols * 8) + mx * 8;
       *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);     // planes are 256-byte aligned, their rows multiples of 8
     }
   }
@@ -326,6 +333,50 @@ __global__ __launch_bounds__(256) void jpeg_dec_transform_kernel(const DecArgs a
 
 // ---- colour ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned char clamp255(int v) { return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
+
+__device__ __forceinline__ void store_rgb(unsigned char* dst, int Y, int cb, int cr) {
+  dst[0] = clamp255(Y + ((91881 * cr + 32768) >> 16));
+  dst[1] = clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+  dst[2] = clamp255(Y + ((116130 * cb + 32768) >> 16));
+}
+
+// 4:2:2: a lane per chroma sample of an output row and its two pixels: libjpeg's h2v1 triangle filter, which it uses
+// where the chroma plane is more than 2 samples wide; a narrower one has every sample repeated
+__global__ __launch_bounds__(256) void jpeg_dec_colour422_kernel(const DecArgs a) {
+  const int cw = (a.w + 1) >> 1;
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= cw) return;
+  const int y = a.y0 + blockIdx.y;
+  const int cl = c > 0 ? c - 1 : 0, cr_ = c < cw - 1 ? c + 1 : cw - 1;
+  int even[2], odd[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const unsigned char* p0 = (k == 0 ? a.pcb : a.pcr) + (int64_t)y * (a.cols * 8);
+    const int s = p0[c];
+    even[k] = (cw > 2 ? (3 * s + p0[cl] + 1) >> 2 : s) - 128;
+    odd[k] = (cw > 2 ? (3 * s + p0[cr_] + 2) >> 2 : s) - 128;
+  }
+  const unsigned char* yrow = a.py + (int64_t)y * (a.cols * 16);
+  unsigned char* dst = a.rgb + (int64_t)blockIdx.y * a.stride + 6 * (int64_t)c;
+  store_rgb(dst, yrow[2 * c], even[0], even[1]);
+  if (2 * c + 1 < a.w) store_rgb(dst + 3, yrow[2 * c + 1], odd[0], odd[1]);
+}
+
+// 4:4:4 and grey: a lane per pixel; no filter, and for grey no chroma: R = G = B = Y
+template <bool Grey>
+__global__ __launch_bounds__(256) void jpeg_dec_colour11_kernel(const DecArgs a) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  if (x >= a.w) return;
+  const int y = a.y0 + blockIdx.y;
+  const int64_t at = (int64_t)y * (a.cols * 8) + x;
+  unsigned char* dst = a.rgb + (int64_t)blockIdx.y * a.stride + 3 * (int64_t)x;
+  const int Y = a.py[at];
+  if (Grey) {
+    dst[0] = dst[1] = dst[2] = (unsigned char)Y;
+  } else {
+    store_rgb(dst, Y, (int)a.pcb[at] - 128, (int)a.pcr[at] - 128);
+  }
+}
 
 __global__ __launch_bounds__(256) void jpeg_dec_colour_kernel(const DecArgs a) {
   const int ch = (a.h + 1) >> 1, cw = (a.w + 1) >> 1;
@@ -369,44 +420,56 @@ void vfml_jpeg::dec_launch_markers(const DecArgs& a, unsigned chunks, hipStream_
 }
 
 void vfml_jpeg::dec_launch_picture(const DecArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(jpeg_dec_transform_kernel, dim3((unsigned)((a.mrows * a.cols + 3) / 4)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(jpeg_dec_colour_kernel, dim3((unsigned)(((a.w + 1) / 2 + 255) / 256), (unsigned)(a.y1 - a.y0)),
-                     dim3(256), 0, s, a);
+  const dim3 tg((unsigned)((a.mrows * a.cols + 3) / 4)), rows1(1, (unsigned)(a.y1 - a.y0));
+  const dim3 half((unsigned)(((a.w + 1) / 2 + 255) / 256), rows1.y), full((unsigned)((a.w + 255) / 256), rows1.y);
+  switch (a.samp) {
+    case kS420:
+      hipLaunchKernelGGL(jpeg_dec_transform_kernel<kS420>, tg, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(jpeg_dec_colour_kernel, half, dim3(256), 0, s, a);
+      break;
+    case kS422:
+      hipLaunchKernelGGL(jpeg_dec_transform_kernel<kS422>, tg, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(jpeg_dec_colour422_kernel, half, dim3(256), 0, s, a);
+      break;
+    case kS444:
+      hipLaunchKernelGGL(jpeg_dec_transform_kernel<kS444>, tg, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(jpeg_dec_colour11_kernel<false>, full, dim3(256), 0, s, a);
+      break;
+    default:
+      hipLaunchKernelGGL(jpeg_dec_transform_kernel<kSGrey>, tg, dim3(256), 0, s, a);
+      hipLaunchKernelGGL(jpeg_dec_colour11_kernel<true>, full, dim3(256), 0, s, a);
+      break;
+  }
+}
+
+extern "C" int64_t vfml_jpeg_decode_sampled_workspace_bytes(int h, int w, int sampling, int64_t scan_bytes) {
+  DecLayout L;
+  return dec_layout(h, w, sampling, scan_bytes, L) ? L.bytes : 0;
 }
 
 extern "C" int64_t vfml_jpeg_decode_workspace_bytes(int h, int w, int64_t scan_bytes) {
-  DecLayout L;
-  return dec_layout(h, w, scan_bytes, L) ? L.bytes : 0;
+  return vfml_jpeg_decode_sampled_workspace_bytes(h, w, kS420, scan_bytes);
 }
 
-extern "C" int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
-                                    const unsigned char* qtables, const int32_t* tables, int y0, int y1, void* workspace,
-                                    unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream) {
+// fn: the entry point's name, for its messages
+static int decode_rgb(const char* fn, const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                      int restart_interval, const unsigned char* qtables, const int32_t* tables, int y0, int y1,
+                      void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream) {
+  VFML_REQUIRE(samp_ok(sampling), "%s: sampling %d (VFML_JPEG_420, _422, _444 or _GREY)", fn, sampling);
   DecLayout L;
-  VFML_REQUIRE(dec_layout(h, w, scan_bytes, L), "vfml_jpeg_decode_rgb: picture %dx%d, scan of %lld bytes (sides of 1..65535, "
-               "a scan below 2 GiB)", w, h, (long long)scan_bytes);
-  VFML_REQUIRE(scan && qtables && tables && workspace && rgb && status, "vfml_jpeg_decode_rgb: null argument");
-  VFML_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, "vfml_jpeg_decode_rgb: restart interval %d",
-               restart_interval);
-  VFML_REQUIRE(0 <= y0 && y0 < y1 && y1 <= h, "vfml_jpeg_decode_rgb: rows %d..%d of a picture of %d", y0, y1, h);
-  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "vfml_jpeg_decode_rgb: row stride %lld below the row's %d bytes",
-               (long long)row_stride, 3 * w);
-  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "vfml_jpeg_decode_rgb: workspace must be 256-byte aligned");
+  VFML_REQUIRE(dec_layout(h, w, sampling, scan_bytes, L), "%s: picture %dx%d, scan of %lld bytes (sides of 1..65535, "
+               "a scan below 2 GiB)", fn, w, h, (long long)scan_bytes);
+  VFML_REQUIRE(scan && qtables && tables && workspace && rgb && status, "%s: null argument", fn);
+  VFML_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, "%s: restart interval %d", fn, restart_interval);
+  VFML_REQUIRE(0 <= y0 && y0 < y1 && y1 <= h, "%s: rows %d..%d of a picture of %d", fn, y0, y1, h);
+  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "%s: row stride %lld below the row's %d bytes", fn, (long long)row_stride,
+               3 * w);
+  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "%s: workspace must be 256-byte aligned", fn);
   VFML_REQUIRE((reinterpret_cast<uintptr_t>(tables) & 3u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0,
-               "vfml_jpeg_decode_rgb: tables and status must be 4-byte aligned");
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const int nmcu = L.rows * L.cols;
+               "%s: tables and status must be 4-byte aligned", fn);
   DecArgs a;
-  a.scan = scan, a.n = (unsigned)scan_bytes, a.h = h, a.w = w, a.rows = L.rows, a.cols = L.cols;
-  a.ri = restart_interval > 0 ? restart_interval : nmcu;
-  a.nint = (nmcu + a.ri - 1) / a.ri;
-  a.qt = qtables, a.tables = tables, a.y0 = y0, a.y1 = y1;
-  a.bcount = reinterpret_cast<unsigned*>(ws + L.bcount);
-  a.mpos = reinterpret_cast<unsigned*>(ws + L.mpos);
-  a.coef = reinterpret_cast<short*>(ws + L.coef);
-  a.py = ws + L.py, a.pcb = ws + L.pcb, a.pcr = ws + L.pcr;
-  a.rgb = rgb, a.stride = row_stride, a.status = status;
-  dec_window(a, h, y0, y1);
+  dec_args(a, L, static_cast<unsigned char*>(workspace), scan, scan_bytes, h, w, sampling, restart_interval, qtables,
+           tables, y0, y1, rgb, row_stride, status);
   const int mlo = a.mrow0, mhi = a.mrow0 + a.mrows - 1;
   int ilo = 0, ihi = a.nint - 1;          // intervals are skipped when each is a whole number of MCU rows
   if (restart_interval > 0 && restart_interval % L.cols == 0) {
@@ -418,5 +481,20 @@ extern "C" int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_byte
   dec_launch_markers(a, (unsigned)L.chunks, s);
   hipLaunchKernelGGL(jpeg_dec_entropy_kernel, dim3((unsigned)(ihi - ilo + 1)), dim3(64), 0, s, a);
   dec_launch_picture(a, s);
-  return vfml_check_launch("vfml_jpeg_decode_rgb");
+  return vfml_check_launch(fn);
+}
+
+extern "C" int vfml_jpeg_decode_rgb_sampled(const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                                            int restart_interval, const unsigned char* qtables, const int32_t* tables,
+                                            int y0, int y1, void* workspace, unsigned char* rgb, int64_t row_stride,
+                                            int32_t* status, void* stream) {
+  return decode_rgb("vfml_jpeg_decode_rgb_sampled", scan, scan_bytes, h, w, sampling, restart_interval, qtables, tables, y0,
+                    y1, workspace, rgb, row_stride, status, stream);
+}
+
+extern "C" int vfml_jpeg_decode_rgb(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
+                                    const unsigned char* qtables, const int32_t* tables, int y0, int y1, void* workspace,
+                                    unsigned char* rgb, int64_t row_stride, int32_t* status, void* stream) {
+  return decode_rgb("vfml_jpeg_decode_rgb", scan, scan_bytes, h, w, kS420, restart_interval, qtables, tables, y0, y1,
+                    workspace, rgb, row_stride, status, stream);
 }

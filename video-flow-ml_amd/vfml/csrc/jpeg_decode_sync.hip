@@ -1,5 +1,5 @@
-// vfml_jpeg_decode_rgb_sync: the JPEG decoder of jpeg_decode.hip with an entropy stage that does not need restart
-// markers - the self-synchronising parallel Huffman decode: the scan is cut into subsequences
+// vfml_jpeg_decode_rgb_sync, vfml_jpeg_decode_rgb_sync_sampled (the sampling as an argument): the
+// JPEG decoder of jpeg_decode.hip with an entropy stage that does not need restart markers - the self-synchronising parallel Huffman decode: the scan is cut into subsequences
 // of S raw bytes, one lane each, whatever the file's restart interval.  Same contract, same picture, same status bits as
 // vfml_jpeg_decode_rgb; tests/jpeg_selfsync_oracle.py is the definition, jpeg_sync_steps.h the per-subsequence code
 // (shared with tools/jpeg_sync_host.cpp, which runs it on the CPU under sanitizers).
@@ -17,6 +17,7 @@
 //   write          every lane decodes once more from its true entry state: non-zero AC coefficients to their natural
 //                  place, the DC difference to place 0; the true chain's errors into the status cell
 //   dc             a workgroup per interval: inclusive sums of the DC differences per component, low 16 bits kept
+//                  (a template on the blocks per MCU: its sums index registers)
 //   transform, colour   the picture kernels of jpeg_decode.hip, on the window's MCU rows
 // The result is the fixed point of "entry state = the left neighbour's exit state", unique by induction from the known
 // states (the scan's first bit, the byte behind a marker): exact whether or not speculation ever agrees; when it does
@@ -49,7 +50,7 @@ struct SyncArgs {
 __device__ __forceinline__ js::Ctx make_ctx(const SyncArgs& a) {
   js::Ctx c;
   c.scan = a.d.scan, c.n = a.d.n, c.mpos = a.d.mpos, c.nmark = (uint32_t)(a.d.nint - 1);
-  c.ri = a.d.ri, c.nmcu = a.d.rows * a.d.cols, c.S = a.S;
+  c.ri = a.d.ri, c.nmcu = a.d.rows * a.d.cols, c.S = a.S, c.nb = a.d.nb, c.ny = a.d.ny;
   return c;
 }
 
@@ -192,25 +193,34 @@ __device__ __forceinline__ int group_scan(int v, int (*buf)[kGroup], int& total)
   return mine;
 }
 
+// NB: blocks per MCU, the first NY of them luma
+template <int NB>
 __global__ __launch_bounds__(kGroup) void jpeg_sync_dc_kernel(const SyncArgs a) {
+  constexpr int NY = NB == 1 ? 1 : NB - 2, NC = NB - NY + 1;
   __shared__ int buf[2][kGroup];
   if ((*a.d.status & (kErrCount | kErrSequence)) != 0) return;
   const int nmcu = a.d.rows * a.d.cols;
   const long long m0 = (long long)blockIdx.x * a.d.ri;
   const long long m1 = m0 + a.d.ri < nmcu ? m0 + a.d.ri : nmcu;
   const int chunks = (int)((m1 - m0 + kGroup - 1) / kGroup);
-  unsigned carry[3] = {0u, 0u, 0u};
+  unsigned carry[NC];
+#pragma unroll
+  for (int k = 0; k < NC; ++k) carry[k] = 0u;
   for (int ch = 0; ch < chunks; ++ch) {
     const long long m = m0 + (long long)ch * kGroup + threadIdx.x;
     const bool valid = m < m1;
-    short* blk = a.d.coef + (valid ? m : m0) * 6 * 64;
-    int d[6];
+    short* blk = a.d.coef + (valid ? m : m0) * NB * 64;
+    int d[NB];
 #pragma unroll
-    for (int b = 0; b < 6; ++b) d[b] = valid ? (int)blk[b * 64] : 0;
-    unsigned sum[3] = {(unsigned)d[0] + (unsigned)d[1] + (unsigned)d[2] + (unsigned)d[3], (unsigned)d[4], (unsigned)d[5]};
-    unsigned base[3];
+    for (int b = 0; b < NB; ++b) d[b] = valid ? (int)blk[b * 64] : 0;
+    unsigned sum[NC];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NC; ++k) sum[k] = k ? (unsigned)d[NY + k - 1] : 0u;
+#pragma unroll
+    for (int b = 0; b < NY; ++b) sum[0] += (unsigned)d[b];
+    unsigned base[NC];
+#pragma unroll
+    for (int k = 0; k < NC; ++k) {
       int total;
       const int incl = group_scan((int)sum[k], buf, total);
       base[k] = carry[k] + (unsigned)incl - sum[k];
@@ -219,12 +229,13 @@ __global__ __launch_bounds__(kGroup) void jpeg_sync_dc_kernel(const SyncArgs a) 
     if (valid) {
       unsigned y = base[0];
 #pragma unroll
-      for (int b = 0; b < 4; ++b) {
+      for (int b = 0; b < NY; ++b) {
         y += (unsigned)d[b];
         blk[b * 64] = (short)(unsigned short)(y & 0xFFFFu);
       }
-      blk[4 * 64] = (short)(unsigned short)((base[1] + (unsigned)d[4]) & 0xFFFFu);
-      blk[5 * 64] = (short)(unsigned short)((base[2] + (unsigned)d[5]) & 0xFFFFu);
+#pragma unroll
+      for (int k = 1; k < NC; ++k)
+        blk[(NY + k - 1) * 64] = (short)(unsigned short)((base[k] + (unsigned)d[NY + k - 1]) & 0xFFFFu);
     }
   }
 }
@@ -234,9 +245,9 @@ struct SyncLayout {
   int64_t nsub, rec, blk0, bytes;
 };
 
-bool sync_layout(int h, int w, int64_t scan_bytes, int S, SyncLayout& Y) {
+bool sync_layout(int h, int w, int samp, int64_t scan_bytes, int S, SyncLayout& Y) {
   if (S < 16 || S > 1024 || (S & (S - 1))) return false;
-  if (!dec_layout(h, w, scan_bytes, Y.L)) return false;
+  if (!dec_layout(h, w, samp, scan_bytes, Y.L)) return false;
   Y.nsub = scan_bytes > 0 ? (scan_bytes + S - 1) / S : 1;
   int64_t at = Y.L.bytes;
   Y.rec = at, at += align256(Y.nsub * (int64_t)sizeof(js::Rec));
@@ -245,48 +256,33 @@ bool sync_layout(int h, int w, int64_t scan_bytes, int S, SyncLayout& Y) {
   return true;
 }
 
-}  // namespace
 
-extern "C" int64_t vfml_jpeg_decode_sync_workspace_bytes(int h, int w, int64_t scan_bytes, int subseq_bytes) {
-  SyncLayout Y;
-  return sync_layout(h, w, scan_bytes, subseq_bytes, Y) ? Y.bytes : 0;
-}
-
-extern "C" int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
-                                         const unsigned char* qtables, const int32_t* tables, int y0, int y1,
-                                         int subseq_bytes, void* workspace, unsigned char* rgb, int64_t row_stride,
-                                         int32_t* status, void* stream) {
+// fn: the entry point's name, for its messages
+int decode_rgb_sync(const char* fn, const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                    int restart_interval, const unsigned char* qtables, const int32_t* tables, int y0, int y1,
+                    int subseq_bytes, void* workspace, unsigned char* rgb, int64_t row_stride, int32_t* status,
+                    void* stream) {
+  VFML_REQUIRE(samp_ok(sampling), "%s: sampling %d (VFML_JPEG_420, _422, _444 or _GREY)", fn, sampling);
   VFML_REQUIRE(subseq_bytes >= 16 && subseq_bytes <= 1024 && (subseq_bytes & (subseq_bytes - 1)) == 0,
-               "vfml_jpeg_decode_rgb_sync: subsequences of %d bytes (a power of two, 16..1024)", subseq_bytes);
+               "%s: subsequences of %d bytes (a power of two, 16..1024)", fn, subseq_bytes);
   SyncLayout Y;
-  VFML_REQUIRE(sync_layout(h, w, scan_bytes, subseq_bytes, Y), "vfml_jpeg_decode_rgb_sync: picture %dx%d, scan of %lld "
-               "bytes (sides of 1..65535, a scan below 2 GiB)", w, h, (long long)scan_bytes);
-  VFML_REQUIRE(scan && qtables && tables && workspace && rgb && status, "vfml_jpeg_decode_rgb_sync: null argument");
-  VFML_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, "vfml_jpeg_decode_rgb_sync: restart interval %d",
-               restart_interval);
-  VFML_REQUIRE(0 <= y0 && y0 < y1 && y1 <= h, "vfml_jpeg_decode_rgb_sync: rows %d..%d of a picture of %d", y0, y1, h);
-  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "vfml_jpeg_decode_rgb_sync: row stride %lld below the row's %d bytes",
-               (long long)row_stride, 3 * w);
-  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
-               "vfml_jpeg_decode_rgb_sync: workspace must be 256-byte aligned");
+  VFML_REQUIRE(sync_layout(h, w, sampling, scan_bytes, subseq_bytes, Y), "%s: picture %dx%d, scan of %lld "
+               "bytes (sides of 1..65535, a scan below 2 GiB)", fn, w, h, (long long)scan_bytes);
+  VFML_REQUIRE(scan && qtables && tables && workspace && rgb && status, "%s: null argument", fn);
+  VFML_REQUIRE(restart_interval >= 0 && restart_interval <= 65535, "%s: restart interval %d", fn, restart_interval);
+  VFML_REQUIRE(0 <= y0 && y0 < y1 && y1 <= h, "%s: rows %d..%d of a picture of %d", fn, y0, y1, h);
+  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "%s: row stride %lld below the row's %d bytes", fn, (long long)row_stride,
+               3 * w);
+  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "%s: workspace must be 256-byte aligned", fn);
   VFML_REQUIRE((reinterpret_cast<uintptr_t>(tables) & 3u) == 0 && (reinterpret_cast<uintptr_t>(status) & 3u) == 0,
-               "vfml_jpeg_decode_rgb_sync: tables and status must be 4-byte aligned");
+               "%s: tables and status must be 4-byte aligned", fn);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const DecLayout& L = Y.L;
   const int nmcu = L.rows * L.cols;
   SyncArgs sa;
   DecArgs& a = sa.d;
-  a.scan = scan, a.n = (unsigned)scan_bytes, a.h = h, a.w = w, a.rows = L.rows, a.cols = L.cols;
-  a.ri = restart_interval > 0 ? restart_interval : nmcu;
-  a.nint = (nmcu + a.ri - 1) / a.ri;
-  a.qt = qtables, a.tables = tables, a.y0 = y0, a.y1 = y1;
-  a.bcount = reinterpret_cast<unsigned*>(ws + L.bcount);
-  a.mpos = reinterpret_cast<unsigned*>(ws + L.mpos);
-  a.coef = reinterpret_cast<short*>(ws + L.coef);
-  a.py = ws + L.py, a.pcb = ws + L.pcb, a.pcr = ws + L.pcr;
-  a.rgb = rgb, a.stride = row_stride, a.status = status;
-  a.int0 = 0;
-  dec_window(a, h, y0, y1);               // nothing of the scan can be skipped without markers: only the transform is windowed
+  // nothing of the scan can be skipped without markers: only the transform is windowed
+  dec_args(a, L, ws, scan, scan_bytes, h, w, sampling, restart_interval, qtables, tables, y0, y1, rgb, row_stride, status);
   sa.rec = reinterpret_cast<js::Rec*>(ws + Y.rec);
   sa.blk0 = reinterpret_cast<int*>(ws + Y.blk0);
   sa.nsub = Y.nsub, sa.S = subseq_bytes;
@@ -295,10 +291,44 @@ extern "C" int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan
   dec_launch_markers(a, (unsigned)L.chunks, s);
   hipLaunchKernelGGL(jpeg_sync_group_kernel, dim3((unsigned)sa.groups), dim3(kGroup), 0, s, sa);
   hipLaunchKernelGGL(jpeg_sync_chain_kernel, dim3(1), dim3(kGroup), 0, s, sa);
-  const hipError_t e = hipMemsetAsync(a.coef, 0, (size_t)nmcu * 6 * 64 * sizeof(short), s);
-  VFML_REQUIRE(e == hipSuccess, "vfml_jpeg_decode_rgb_sync: hipMemsetAsync: %s", hipGetErrorString(e));
+  const hipError_t e = hipMemsetAsync(a.coef, 0, (size_t)nmcu * a.nb * 64 * sizeof(short), s);
+  VFML_REQUIRE(e == hipSuccess, "%s: hipMemsetAsync: %s", fn, hipGetErrorString(e));
   hipLaunchKernelGGL(jpeg_sync_write_kernel, dim3((unsigned)sa.groups), dim3(kGroup), 0, s, sa);
-  hipLaunchKernelGGL(jpeg_sync_dc_kernel, dim3((unsigned)a.nint), dim3(kGroup), 0, s, sa);
+  const dim3 ints((unsigned)a.nint);
+  switch (a.nb) {
+    case 6: hipLaunchKernelGGL(jpeg_sync_dc_kernel<6>, ints, dim3(kGroup), 0, s, sa); break;
+    case 4: hipLaunchKernelGGL(jpeg_sync_dc_kernel<4>, ints, dim3(kGroup), 0, s, sa); break;
+    case 3: hipLaunchKernelGGL(jpeg_sync_dc_kernel<3>, ints, dim3(kGroup), 0, s, sa); break;
+    default: hipLaunchKernelGGL(jpeg_sync_dc_kernel<1>, ints, dim3(kGroup), 0, s, sa); break;
+  }
   dec_launch_picture(a, s);
-  return vfml_check_launch("vfml_jpeg_decode_rgb_sync");
+  return vfml_check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" int64_t vfml_jpeg_decode_sync_sampled_workspace_bytes(int h, int w, int sampling, int64_t scan_bytes,
+                                                                 int subseq_bytes) {
+  SyncLayout Y;
+  return sync_layout(h, w, sampling, scan_bytes, subseq_bytes, Y) ? Y.bytes : 0;
+}
+
+extern "C" int64_t vfml_jpeg_decode_sync_workspace_bytes(int h, int w, int64_t scan_bytes, int subseq_bytes) {
+  return vfml_jpeg_decode_sync_sampled_workspace_bytes(h, w, kS420, scan_bytes, subseq_bytes);
+}
+
+extern "C" int vfml_jpeg_decode_rgb_sync_sampled(const unsigned char* scan, int64_t scan_bytes, int h, int w, int sampling,
+                                                 int restart_interval, const unsigned char* qtables, const int32_t* tables,
+                                                 int y0, int y1, int subseq_bytes, void* workspace, unsigned char* rgb,
+                                                 int64_t row_stride, int32_t* status, void* stream) {
+  return decode_rgb_sync("vfml_jpeg_decode_rgb_sync_sampled", scan, scan_bytes, h, w, sampling, restart_interval, qtables,
+                         tables, y0, y1, subseq_bytes, workspace, rgb, row_stride, status, stream);
+}
+
+extern "C" int vfml_jpeg_decode_rgb_sync(const unsigned char* scan, int64_t scan_bytes, int h, int w, int restart_interval,
+                                         const unsigned char* qtables, const int32_t* tables, int y0, int y1,
+                                         int subseq_bytes, void* workspace, unsigned char* rgb, int64_t row_stride,
+                                         int32_t* status, void* stream) {
+  return decode_rgb_sync("vfml_jpeg_decode_rgb_sync", scan, scan_bytes, h, w, kS420, restart_interval, qtables, tables, y0,
+                         y1, subseq_bytes, workspace, rgb, row_stride, status, stream);
 }

@@ -3,7 +3,7 @@
 // tools/jpeg_sync_host.cpp runs the same phases in series on the CPU (under sanitizers in tests/test_jpeg_selfsync_cpu.py).
 // tests/jpeg_selfsync_oracle.py is the definition in Python.
 //
-// A state at a symbol boundary is (raw bit position, block in MCU b, coefficient index k; k = 0: DC next).  Positions are
+// A state at a symbol boundary is (raw bit position, block in MCU b < nb, coefficient index k; k = 0: DC next).  Positions are
 // 64-bit and absolute while a subsequence is decoded; a record keeps them relative to the subsequence's edge (8 bits).
 // Every loop is bounded by a count: the interval search by 32 halvings, a refill by 8 bytes, the Huffman search by 8
 // lengths, a subsequence decode by 9 S + 31 steps (a symbol is at least one bit, a marker at least two bytes).
@@ -41,6 +41,7 @@ struct Ctx {
   uint32_t nmark;                                // intervals - 1
   int ri, nmcu;                                  // MCUs per interval (the picture's when Ri = 0), MCUs
   int S;                                         // bytes per subsequence, a power of two 16..1024
+  int nb, ny;                                    // blocks per MCU (6 / 4 / 3 / 1 by the sampling), luma blocks among them
 };
 
 struct Rec {                                     // one subsequence's record
@@ -102,7 +103,7 @@ VFML_JSYNC_HD uint32_t interval_end(const Ctx& c, uint32_t iv, uint32_t floor_) 
 
 VFML_JSYNC_HD int64_t interval_block0(const Ctx& c, uint32_t iv) {
   const int64_t m = (int64_t)iv * c.ri;
-  return (m < c.nmcu ? m : c.nmcu) * 6;
+  return (m < c.nmcu ? m : c.nmcu) * c.nb;
 }
 
 // ---- bits: most significant first, FF 00 taken as FF where it is met, zeros behind the interval's end --------------
@@ -183,7 +184,7 @@ VFML_JSYNC_HD Out decode_sub(const Ctx& c, const Tabs& t, int64_t sub, uint32_t 
   const int64_t lim_bits = lim * 8;
   bool poison = entry == kPoison;
   int b = poison ? 0 : (int)((entry >> 8) & 7u), k = poison ? 0 : (int)((entry >> 11) & 63u);
-  if (b > 5) b = 0;
+  if (b >= c.nb) b = 0;
   const int64_t pos0 = start * 8 + (poison ? 0 : (int64_t)(entry & 255u));
   uint32_t iv = interval_of(c, (uint32_t)(pos0 >> 3));
   uint32_t end = interval_end(c, iv, 0u);
@@ -223,7 +224,7 @@ VFML_JSYNC_HD Out decode_sub(const Ctx& c, const Tabs& t, int64_t sub, uint32_t 
       rd_start(r, c, (int64_t)from * 8, end);
       continue;
     }
-    const int comp = b < 4 ? 0 : b - 3;
+    const int comp = b < c.ny ? 0 : b - c.ny + 1;
     bool done = false;
     if (k == 0) {
       const int sym = rd_symbol(r, t, t.dc_t[comp]);
@@ -267,7 +268,7 @@ VFML_JSYNC_HD Out decode_sub(const Ctx& c, const Tabs& t, int64_t sub, uint32_t 
       }
     }
     if (done || k >= 64) {
-      k = 0, b = b == 5 ? 0 : b + 1;
+      k = 0, b = b + 1 >= c.nb ? 0 : b + 1;
       ++o.nblk, ++blk;
       if (Write && r.pos > (int64_t)end * 8) o.err |= kErrData, poison = true;
     }

@@ -198,6 +198,14 @@ def lib():
     L.vfml_jpeg_decode_sync_workspace_bytes.argtypes = [c_int, c_int, c_int64, c_int]
     L.vfml_jpeg_decode_rgb_sync.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                             c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    L.vfml_jpeg_decode_sampled_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_decode_sampled_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int64]
+    L.vfml_jpeg_decode_rgb_sampled.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                                               c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
+    L.vfml_jpeg_decode_sync_sampled_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_decode_sync_sampled_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int64, c_int]
+    L.vfml_jpeg_decode_rgb_sync_sampled.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                    c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]
     for fn in (L.vfml_deflate_capacity, L.vfml_deflate_workspace_bytes, L.vfml_inflate_workspace_bytes):
         fn.restype = c_int64
         fn.argtypes = [c_int64, c_int]
@@ -225,6 +233,8 @@ EXPORTS = [
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
     "vfml_jpeg_decode_workspace_bytes", "vfml_jpeg_decode_rgb",
     "vfml_jpeg_decode_sync_workspace_bytes", "vfml_jpeg_decode_rgb_sync",
+    "vfml_jpeg_decode_sampled_workspace_bytes", "vfml_jpeg_decode_rgb_sampled",
+    "vfml_jpeg_decode_sync_sampled_workspace_bytes", "vfml_jpeg_decode_rgb_sync_sampled",
     "vfml_deflate_capacity", "vfml_deflate_workspace_bytes", "vfml_deflate_huffman",
     "vfml_inflate_workspace_bytes", "vfml_inflate_chunks",
     "vfml_last_error", "vfml_abi_version",
@@ -1080,7 +1090,8 @@ def jpeg_decode_plan(info):
 
 def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, subseq_bytes=None):
     """A baseline JPEG file -> (rgb, status): the picture, uint8 device tensor [H,W,3], decoded on the device byte for
-    byte as libjpeg (Pillow) decodes it (vfml_jpeg_decode_rgb, DESIGN.md section 13: stream-ordered, no
+    byte as libjpeg (Pillow) decodes it (vfml_jpeg_decode_rgb_sampled; 4:2:0, 4:2:2, 4:4:4 or grey
+    by info.sampling, a grey picture as R = G = B: stream-ordered, no
     synchronisation once the file's tables are on the device, see _jpeg_decode_tables), and the int32 device cell [1] that holds 0 or the error bits of a damaged scan
     (jpeg_decode_check reads it).
     data: the file's bytes - uploaded here - or a uint8 tensor that holds them, pinned (uploaded asynchronously; the
@@ -1089,7 +1100,7 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, su
     rows=(y0, y1): rows y0 <= y < y1 of the picture alone ([y1-y0,W,3]); with one or more whole MCU rows per restart
     interval the other intervals are not read.  out: a uint8 device tensor [rows,W,3] with contiguous pixels and a row
     stride of at least 3 W (a row slice of a larger buffer) that receives the picture.  The workspace is kept per
-    device, picture size, plan and stream.
+    device, picture size, plan and stream, and holds the largest sampling it has met.
     plan: 'interval' (vfml_jpeg_decode_rgb: a wave per restart interval), 'sync' (vfml_jpeg_decode_rgb_sync, section
     13.1: a lane per subseq_bytes of the scan, whatever the restart interval) or None: jpeg_decode_plan(info).  Both
     give the same bytes.  subseq_bytes: a power of two 16..1024, None: jpeg_subseq_bytes of the scan's size rounded up
@@ -1110,7 +1121,7 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, su
             raise ValueError("jpeg_decode: a host tensor of file bytes must be pinned")
     else:
         if info is None:
-            info = jpeg_parse.parse(data)
+            info = jpeg_parse.parse(data, jpeg_parse.DEVICE_SAMPLINGS)
         data = torch.frombuffer(bytearray(data), dtype=torch.uint8)
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     if device.type != "cuda":
@@ -1141,8 +1152,9 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, su
     sub = jpeg_subseq_bytes(cap) if subseq_bytes is None else int(subseq_bytes)
     if sync and (sub < 16 or sub > 1024 or sub & (sub - 1)):
         raise ValueError(f"jpeg_decode: subseq_bytes {sub}; a power of two 16..1024")
-    need = int(L.vfml_jpeg_decode_sync_workspace_bytes(h, w, cap, sub) if sync else
-               L.vfml_jpeg_decode_workspace_bytes(h, w, cap))
+    samp = jpeg_parse.SAMPLING_CODE[info.sampling]
+    need = int(L.vfml_jpeg_decode_sync_sampled_workspace_bytes(h, w, samp, cap, sub) if sync else
+               L.vfml_jpeg_decode_sampled_workspace_bytes(h, w, samp, cap))
     if need == 0:
         raise ValueError(f"jpeg_decode: picture {w}x{h} with a scan of {s1 - s0} bytes is too large")
     key = (device.index, h, w, torch.cuda.current_stream(device).cuda_stream) + ((sub,) if sync else ())
@@ -1153,17 +1165,18 @@ def jpeg_decode(data, rows=None, out=None, device=None, info=None, plan=None, su
     status = torch.empty(1, dtype=torch.int32, device=device)
     if sync:
         with torch.cuda.device(device):
-            _check(L.vfml_jpeg_decode_rgb_sync(c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0,
-                                               h, w, int(info.restart_interval), c_void_p(qt.data_ptr()),
-                                               c_void_p(tables.data_ptr()), y0, y1, sub, c_void_p(ws.data_ptr()),
-                                               c_void_p(out.data_ptr()), stride, c_void_p(status.data_ptr()), _stream()),
-                   "vfml_jpeg_decode_rgb_sync")
+            _check(L.vfml_jpeg_decode_rgb_sync_sampled(
+                c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0, h, w, samp,
+                int(info.restart_interval), c_void_p(qt.data_ptr()), c_void_p(tables.data_ptr()), y0, y1, sub,
+                c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), stride, c_void_p(status.data_ptr()), _stream()),
+                "vfml_jpeg_decode_rgb_sync_sampled")
         return out, status
     with torch.cuda.device(device):
-        _check(L.vfml_jpeg_decode_rgb(c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0, h, w,
-                                      int(info.restart_interval), c_void_p(qt.data_ptr()), c_void_p(tables.data_ptr()),
-                                      y0, y1, c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), stride,
-                                      c_void_p(status.data_ptr()), _stream()), "vfml_jpeg_decode_rgb")
+        _check(L.vfml_jpeg_decode_rgb_sampled(
+            c_void_p(scan.data_ptr()) if s1 > s0 else c_void_p(ws.data_ptr()), s1 - s0, h, w, samp,
+            int(info.restart_interval), c_void_p(qt.data_ptr()), c_void_p(tables.data_ptr()), y0, y1,
+            c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), stride, c_void_p(status.data_ptr()), _stream()),
+            "vfml_jpeg_decode_rgb_sampled")
     return out, status
 
 
