@@ -30,7 +30,8 @@ extern "C" {
 /* 25 also covers vfml_flow_decode, vfml_flow_diff_overlay, VFML_COMPOSE_GRID_2X3, vfml_resize_u8 and the vfml_jpeg_*
  * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
  * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
- * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420. */
+ * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
+ * the three vfml_jpeg_*_sampled entry points of the encoder. */
 #define VFML_ABI_VERSION 26
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -647,6 +648,27 @@ int vfml_jpeg_decode_rgb_sync_sampled(const unsigned char* scan, int64_t scan_by
                                       int restart_interval, const unsigned char* qtables, const int32_t* tables, int y0,
                                       int y1, int subseq_bytes, void* workspace, unsigned char* rgb, int64_t row_stride,
                                       int32_t* status, void* stream);
+
+/* The encoder for the samplings a flow video wants ("Samplings";
+ * tests/jpeg_encode_sampling_oracle.py is the definition and the scan equals its scan byte for byte).  Colour conversion,
+ * DCT, quantisation, clamps, Huffman tables, stuffing, padding and restart markers are those of vfml_jpeg_encode_rgb; the
+ * sampling sets the MCU, the chroma sample and the SOF0 / DRI bytes of the header (storage/jpeg_tables.py jpeg_header):
+ *   VFML_JPEG_420   2x2 / 1x1 / 1x1   MCU 16x16   Y00 Y01 Y10 Y11 Cb Cr   chroma = (a + b + c + d + 2) >> 2 over 2x2 cells
+ *   VFML_JPEG_422   2x1 / 1x1 / 1x1   MCU 16x8    Y0 Y1 Cb Cr             chroma = (a + b + 1) >> 1 over the horizontal pair
+ *   VFML_JPEG_444   1x1 / 1x1 / 1x1   MCU 8x8     Y Cb Cr                 chroma = the sample itself
+ * The picture is padded to multiples of the MCU by edge replication (4:2:2, 4:4:4: a height multiple of 8), one MCU row
+ * is one restart interval, and the DC predictors are per component and zero at the start of each interval.  Every other
+ * argument and every guarantee is that of vfml_jpeg_encode_rgb, which is this with VFML_JPEG_420 and writes the bytes it
+ * always wrote: nothing is written at or past scan + scan_capacity, *scan_bytes holds the length the picture needs, every
+ * workspace region is sized for the worst case of this sampling (416 bytes per block, MCUs per row x blocks per MCU x
+ * 416 + 2 per interval), and the worst-case scan stays below 4 GiB (0 from the size functions otherwise).
+ * VFML_JPEG_GREY and a sampling outside the enum return non-zero (vfml_last_error) and launch nothing; the size functions
+ * return 0 for them.  A workspace sized for one sampling does not fit another. */
+int64_t vfml_jpeg_sampled_workspace_bytes(int h, int w, int sampling);
+int64_t vfml_jpeg_sampled_scan_capacity(int h, int w, int sampling);
+int vfml_jpeg_encode_rgb_sampled(const unsigned char* rgb, int h, int w, int64_t row_stride, int sampling,
+                                 const unsigned char* qtables, void* workspace, unsigned char* scan,
+                                 int64_t scan_capacity, uint32_t* scan_bytes, void* stream);
 
 /* Deflate / inflate of the flow cache's .npz members (tests/deflate_oracle.py is the definition of
  * the stream, vfml/csrc/deflate_code.h of its code lengths).  The raw bytes are cut into chunks of chunk_bytes (a power of

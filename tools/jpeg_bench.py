@@ -1,4 +1,4 @@
-"""vfml_jpeg_encode_rgb on device-resident frames: time per frame at 3840x2160 (the 1080p job's TAA grid), 1920x1080 and
+"""vfml_jpeg_encode_rgb_sampled on device-resident frames (`--sampling 4:2:0|4:2:2|4:4:4`, default 4:2:0): time per frame at 3840x2160 (the 1080p job's TAA grid), 1920x1080 and
 3840x3240 (the --flow-input grid), the scan's size, and what crosses PCIe per frame against the uncompressed picture
 (dev tool, GPU only; not bench.py).
 
@@ -38,17 +38,19 @@ def main(argv=None):
     ap.add_argument("--calls", type=int, default=50)
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--size", default=None, help="WxH: this size only")
+    ap.add_argument("--sampling", default="4:2:0", choices=["4:2:0", "4:2:2", "4:4:4"], help="chroma sampling of the frames")
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("jpeg_bench: needs a GPU; nothing is measured without one")
     from vfml import hip
     sizes = [tuple(int(v) for v in args.size.lower().split("x"))] if args.size else SIZES
-    out = {"calls_per_window": args.calls}
+    out = {"calls_per_window": args.calls, "sampling": args.sampling}
+    code = hip.JPEG_ENCODE_SAMPLINGS[args.sampling]
     for w, h in sizes:
         img = torch.from_numpy(picture(w, h)).cuda()
-        scan = torch.empty(hip.jpeg_scan_capacity(h, w), dtype=torch.uint8, device="cuda")
+        scan = torch.empty(hip.jpeg_scan_capacity(h, w, args.sampling), dtype=torch.uint8, device="cuda")
         for _ in range(3):
-            _, length = hip.jpeg_encode(img, out=scan)
+            _, length = hip.jpeg_encode(img, out=scan, sampling=args.sampling)
         torch.cuda.synchronize()
         n = int(length.item())
         us = []
@@ -56,15 +58,15 @@ def main(argv=None):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(args.calls):
-                hip.jpeg_encode(img, out=scan)
+                hip.jpeg_encode(img, out=scan, sampling=args.sampling)
             e1.record()
             torch.cuda.synchronize()
             us.append(e0.elapsed_time(e1) / args.calls * 1e3)
         med = statistics.median(us)
         raw = 3 * w * h
-        print(f"{w}x{h}: {med:8.1f} us per frame (windows {min(us):.1f} .. {max(us):.1f}); scan {n / 1e6:.3f} MB of "
+        print(f"{w}x{h} {args.sampling}: {med:8.1f} us per frame (windows {min(us):.1f} .. {max(us):.1f}); scan {n / 1e6:.3f} MB of "
               f"{raw / 1e6:.1f} MB RGB = 1/{raw / n:.1f} back over PCIe; workspace "
-              f"{hip.lib().vfml_jpeg_workspace_bytes(h, w) / 1e6:.0f} MB, scan capacity {scan.numel() / 1e6:.0f} MB")
+              f"{hip.lib().vfml_jpeg_sampled_workspace_bytes(h, w, code) / 1e6:.0f} MB, scan capacity {scan.numel() / 1e6:.0f} MB")
         out[f"{w}x{h}"] = {"us_median": med, "us_windows": us, "scan_bytes": n, "rgb_bytes": raw}
     print(json.dumps(out))
     return 0

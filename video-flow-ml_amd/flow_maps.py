@@ -78,8 +78,9 @@ def qa_tiles_resident(frame1, frame2, flow, kernel_size=25, threshold=0.8):
 
 
 def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', kernel_size=25, threshold=0.8,
-                    uncompressed=False, fps=30.0, log=print):
-    """Write the QA grid of every cache frame in `frame_indices` to `output`; -> the number of frames written."""
+                    uncompressed=False, fps=30.0, log=print, sampling="4:2:0"):
+    """Write the QA grid of every cache frame in `frame_indices` to `output`; -> the number of frames written.
+    sampling: '4:2:0', '4:2:2' or '4:4:4', the chroma sampling of the MJPG frames."""
     from storage.avi_writer import AviWriter, dib_stride
     from storage.cache_manager import FlowCacheManager
     from vfml import hip
@@ -88,12 +89,13 @@ def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', ker
     mgr = FlowCacheManager()
     cache_dir = os.path.normpath(str(cache_dir))
     h, w = frames[0].shape[:2]
-    writer = AviWriter(output, 0 if uncompressed else 'MJPG', fps, (2 * w, 2 * h), log=log, encoder='external')
+    writer = AviWriter(output, 0 if uncompressed else 'MJPG', fps, (2 * w, 2 * h), log=log, encoder='external',
+                       sampling=sampling)
     stride = dib_stride(2 * w) if uncompressed else None
     jpeg = None
     if not uncompressed:           # MJPG frames are encoded on the device (vfml_jpeg_encode_rgb); only the scan comes back
         from storage.device_mjpg import DeviceMjpgEncoder
-        jpeg = DeviceMjpgEncoder(writer, 2 * h, 2 * w, device)
+        jpeg = DeviceMjpgEncoder(writer, 2 * h, 2 * w, device, sampling=sampling)
     written = 0
     try:
         for i in frame_indices:

@@ -360,6 +360,21 @@ DEVICE_MJPG = True
 # VFML_NPZ_DEFLATE.  Off until fields/s and rendered frames/s have been measured against the host path (section 14's
 # rule for the default); a device-written cache is read by either setting.
 DEVICE_NPZ = False
+# The chroma sampling of the output video's MJPG frames, on either path (vfml_jpeg_encode_rgb_sampled, or Pillow's
+# subsampling= under --device cpu): "4:2:0", "4:2:2" or "4:4:4" ("Samplings").  The environment
+# variable VFML_MJPG_SAMPLING overrides it.  A flow video for --flow-input should be 4:4:4: its vectors live in R and G,
+# and sampled chroma smears them at every motion edge.
+MJPG_SAMPLING = "4:2:0"
+MJPG_SAMPLINGS = ("4:2:0", "4:2:2", "4:4:4")
+
+
+def mjpg_sampling():
+    """MJPG_SAMPLING, or VFML_MJPG_SAMPLING when it is set; a value outside MJPG_SAMPLINGS is refused."""
+    value = os.environ.get("VFML_MJPG_SAMPLING") or MJPG_SAMPLING
+    if value not in MJPG_SAMPLINGS:
+        source = "VFML_MJPG_SAMPLING" if os.environ.get("VFML_MJPG_SAMPLING") else "flow_processor.MJPG_SAMPLING"
+        raise ValueError(f"{source} = {value!r}: the MJPG frames are written as {', '.join(MJPG_SAMPLINGS)}")
+    return value
 
 
 def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=None, log=print):
@@ -399,16 +414,21 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
         else:
             external = _ExternalFlowSource(args.flow_input, n, width, height, log, device=device)
             size = (width * 2, height * 3)
+    sampling = mjpg_sampling()
     if args.uncompressed:
         log("Using uncompressed video codec. Output will be .avi and file size will be very large.")
     else:
         log("Using MJPG codec. Output will be .avi for compatibility.")
+        if args.flow_only and args.flow_format in FLOW_INPUT_VARIANTS and sampling == "4:2:0":
+            log(f"note: MJPG_SAMPLING is 4:2:0: a {args.flow_format} video with sampled chroma loses its vectors at motion "
+                f"edges (R and G are smeared there); set VFML_MJPG_SAMPLING=4:4:4 for a video that --flow-input reads back")
     gpu = str(device).startswith('cuda')
     from vfml.dist import host_cpu_share
     jpeg_workers = max(1, min(8, host_cpu_share()))
     # MJPG on the device path: the frames are encoded on the GPU (vfml_jpeg_encode_rgb) and the writer takes finished JPEGs
     writer = AviWriter(output_path, 0 if args.uncompressed else 'MJPG', fps, size, workers=jpeg_workers,
-                       depth=jpeg_workers + 1, log=log, encoder='external' if gpu and DEVICE_MJPG else 'pillow')
+                       depth=jpeg_workers + 1, log=log, encoder='external' if gpu and DEVICE_MJPG else 'pillow',
+                       sampling=sampling)
     encoder = render_encoder(args.flow_format, args.motion_vectors_clamp_range)
     taa_flow, taa_simple, taa_external = TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1), TAAProcessor(alpha=0.1)
     variant = FLOW_INPUT_VARIANTS.get(args.flow_format)
@@ -480,7 +500,7 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
     jpeg = None
     if writer.external:
         from storage.device_mjpg import DeviceMjpgEncoder
-        jpeg = DeviceMjpgEncoder(writer, size[1], size[0], device)
+        jpeg = DeviceMjpgEncoder(writer, size[1], size[0], device, sampling=writer.sampling)
     nslots = 0 if jpeg is not None else writer.in_flight_limit() + 3
     oslots = [torch.empty((size[1], stride), dtype=torch.uint8).pin_memory() for _ in range(nslots)]
     oevents = [None] * nslots
@@ -571,6 +591,7 @@ def main(argv=None):
         log("note: --show-tiles concerns video composition / visualisation, which this build does not do; ignored")
     if args.flow_input is not None:
         check_flow_input(args)
+    mjpg_sampling()             # a setting that is not built is refused before anything is computed or rendered
     if not (args.input.startswith('synthetic:') or os.path.exists(args.input)):
         log(f"Error: Input video not found: {args.input}")
         return 1

@@ -1,7 +1,8 @@
 """AVI writer in pure Python: the container of flow_processor's output video (reference: cv2.VideoWriter, MJPG or
 uncompressed, flow_processor.py:876-897).  No OpenCV.
 
-* MJPG: each frame a baseline JPEG at quality 95, encoded with Pillow on a thread pool (frames stay in order).  Without
+* MJPG: each frame a baseline JPEG at quality 95 (4:2:0 unless `sampling` names 4:2:2 or 4:4:4), encoded with Pillow on a
+  thread pool (frames stay in order).  Without
   Pillow the writer says so and writes uncompressed frames instead.  `encoder='external'`: the caller hands in finished
   JPEG files (`write_encoded`: the device encoder's frames, vfml_jpeg_encode_rgb) - no Pillow, no pool.
 * uncompressed: 24-bit BI_RGB DIB frames - BGR, bottom-up rows, each row padded to 4 bytes.
@@ -47,20 +48,26 @@ def _pillow():
         return None
 
 
-def _jpeg(rgb):
+# sampling -> Pillow's subsampling= of the same kind of file (None: its default at this quality, 4:2:0, as always written)
+PILLOW_SUBSAMPLING = {"4:2:0": None, "4:2:2": 1, "4:4:4": 0}
+
+
+def _jpeg(rgb, subsampling=None):
     import io
     buf = io.BytesIO()
-    _pillow().fromarray(np.ascontiguousarray(rgb), "RGB").save(buf, format="JPEG", quality=JPEG_QUALITY)
+    kw = {} if subsampling is None else {"subsampling": subsampling}
+    _pillow().fromarray(np.ascontiguousarray(rgb), "RGB").save(buf, format="JPEG", quality=JPEG_QUALITY, **kw)
     return buf.getvalue()
 
 
 class AviWriter:
     """cv2.VideoWriter-like AVI writer (one video stream).  `fourcc`: 'MJPG' or 0 / None (uncompressed).
     `encoder`: who makes the JPEGs of an MJPG file - 'pillow' (write / write_payload, on the writer's pool) or
-    'external' (the caller, through write_encoded)."""
+    'external' (the caller, through write_encoded).  `sampling`: '4:2:0', '4:2:2' or '4:4:4', what the 'pillow' encoder
+    writes (an 'external' caller's files are its own, the name is only kept)."""
 
     def __init__(self, path, fourcc, fps, size, segment_bytes=1 << 30, workers=None, depth=None, log=print,
-                 encoder='pillow'):
+                 encoder='pillow', sampling='4:2:0'):
         self.path, self.fps = path, float(fps)
         self.width, self.height = (int(v) for v in size)
         self.mjpg = fourcc not in (0, None)
@@ -68,6 +75,9 @@ class AviWriter:
             raise ValueError(f"AviWriter: fourcc {fourcc!r}; 'MJPG' or 0 (uncompressed) are built")
         if encoder not in ('pillow', 'external'):
             raise ValueError(f"AviWriter: encoder {encoder!r}; 'pillow' or 'external'")
+        if sampling not in PILLOW_SUBSAMPLING:
+            raise ValueError(f"AviWriter: sampling {sampling!r}; {', '.join(PILLOW_SUBSAMPLING)} are built")
+        self.sampling = sampling
         self.external = self.mjpg and encoder == 'external'
         if self.mjpg and not self.external and _pillow() is None:
             log("Warning: Pillow is not installed; writing uncompressed frames instead of MJPG")
@@ -213,7 +223,7 @@ class AviWriter:
                 raise ValueError(f"AviWriter: payload of {data.size} bytes, want {self.frame_bytes}")
             self._chunk(data.tobytes())
             return
-        self._pending.append(self._pool.submit(_jpeg, buf))
+        self._pending.append(self._pool.submit(_jpeg, buf, PILLOW_SUBSAMPLING[self.sampling]))
         while len(self._pending) > self._depth:
             self._chunk(self._pending.popleft().result())
 

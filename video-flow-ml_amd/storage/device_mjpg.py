@@ -1,7 +1,8 @@
 """MJPG frames encoded and decoded on the device.
 
-DeviceMjpgEncoder: MJPG frames encoded on the device (vfml_jpeg_encode_rgb) on their way into an
-AviWriter(encoder='external'): the composed frame never leaves the device uncompressed, only its scan comes back.
+DeviceMjpgEncoder: MJPG frames encoded on the device (vfml_jpeg_encode_rgb_sampled; 4:2:0 unless
+the caller names 4:2:2 or 4:4:4) on their way into an AviWriter(encoder='external'): the composed frame never leaves the
+device uncompressed, only its scan comes back.
 
 Per frame, all on the caller's current stream: the encoder runs behind the kernel that wrote the picture; the length
 cell is copied to pinned memory; one frame later the host reads it and copies exactly that many bytes into a pinned slot
@@ -22,18 +23,22 @@ SLOTS = 3      # a slot is encoded into at frame i, fetched at i + 1, written at
 
 
 class DeviceMjpgEncoder:
-    def __init__(self, writer, height, width, device, quality=JPEG_QUALITY):
+    def __init__(self, writer, height, width, device, quality=JPEG_QUALITY, sampling="4:2:0"):
         from vfml import hip
+        from . import jpeg_tables
         if not getattr(writer, "external", False):
             raise ValueError("DeviceMjpgEncoder: the writer must be an MJPG AviWriter with encoder='external'")
         if (writer.height, writer.width) != (height, width):
             raise ValueError(f"DeviceMjpgEncoder: frames of {width}x{height} for a {writer.width}x{writer.height} writer")
-        self._hip, self._writer, self._quality = hip, writer, int(quality)
-        self._header = hip.jpeg_header(height, width, self._quality)
-        capacity = hip.jpeg_scan_capacity(height, width)
+        self._hip, self._writer, self._quality, self._sampling = hip, writer, int(quality), sampling
+        self._header = hip.jpeg_header(height, width, self._quality, sampling)
+        capacity = hip.jpeg_scan_capacity(height, width, sampling)
         self._scan = [torch.empty(capacity, dtype=torch.uint8, device=device) for _ in range(SLOTS)]
         self._length = [torch.empty(1, dtype=torch.int32).pin_memory() for _ in range(SLOTS)]
-        self._host = [self._slot(max(4096, 3 * height * width // 6)) for _ in range(SLOTS)]
+        # a first guess of a third of a byte per sample, i.e. per coefficient of the sampling's blocks; _fetch grows it
+        rows, cols = jpeg_tables.mcu_grid(height, width, sampling)
+        blocks = rows * cols * jpeg_tables.BLOCKS_PER_MCU[sampling]
+        self._host = [self._slot(max(4096, blocks * 64 // 3)) for _ in range(SLOTS)]
         self._bytes = [0] * SLOTS
         self._length_event = [None] * SLOTS
         self._copy_event = [None] * SLOTS
@@ -51,7 +56,7 @@ class DeviceMjpgEncoder:
         """rgb: the frame, uint8 device tensor [H,W,3] with contiguous rows, written on the current stream."""
         s = self._frames % SLOTS
         self._frames += 1
-        _, length = self._hip.jpeg_encode(rgb, self._quality, out=self._scan[s])
+        _, length = self._hip.jpeg_encode(rgb, self._quality, out=self._scan[s], sampling=self._sampling)
         self._length[s].copy_(length, non_blocking=True)
         self._length_event[s] = torch.cuda.Event()
         self._length_event[s].record()

@@ -126,8 +126,20 @@ def dqt_segments(quality):
     return [_segment(0xDB, bytes([t]) + q[t][zz].tobytes()) for t in (0, 1)]
 
 
-def sof0_segment(h, w):
-    return _segment(0xC0, bytes([8]) + struct.pack('>HH', h, w) + bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+# sampling -> the luma component's factor byte in SOF0 (chroma is 1x1): what the encoder writes
+LUMA_FACTORS = {"4:2:0": 0x22, "4:2:2": 0x21, "4:4:4": 0x11}
+BLOCKS_PER_MCU = {"4:2:0": 6, "4:2:2": 4, "4:4:4": 3}      # the luma blocks, Cb, Cr
+
+
+def _encoded_sampling(sampling):
+    if sampling not in LUMA_FACTORS:
+        raise ValueError(f"JPEG sampling {sampling!r}: the encoder builds {', '.join(LUMA_FACTORS)}")
+    return sampling
+
+
+def sof0_segment(h, w, sampling="4:2:0"):
+    luma = LUMA_FACTORS[_encoded_sampling(sampling)]
+    return _segment(0xC0, bytes([8]) + struct.pack('>HH', h, w) + bytes([3, 1, luma, 0, 2, 0x11, 1, 3, 0x11, 1]))
 
 
 def dht_segments():
@@ -143,14 +155,15 @@ def sos_segment():
     return _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
 
 
-def jpeg_header(h, w, quality):
-    """Everything in front of the entropy-coded scan of an h x w picture: SOI, APP0 (JFIF 1.01), DQT x 2, SOF0 (4:2:0),
-    DHT x 4, DRI (one MCU row per restart interval), SOS."""
+def jpeg_header(h, w, quality, sampling="4:2:0"):
+    """Everything in front of the entropy-coded scan of an h x w picture: SOI, APP0 (JFIF 1.01), DQT x 2, SOF0 (4:2:0,
+    4:2:2 or 4:4:4), DHT x 4, DRI (one MCU row of that sampling per restart interval), SOS."""
     h, w = int(h), int(w)
+    _encoded_sampling(sampling)
     if not (1 <= h <= 65535 and 1 <= w <= 65535):
         raise ValueError(f"JPEG picture {w}x{h}: sides of 1..65535")
-    return b''.join([SOI, app0_segment(), *dqt_segments(quality), sof0_segment(h, w), *dht_segments(),
-                     dri_segment(mcu_grid(h, w)[1]), sos_segment()])
+    return b''.join([SOI, app0_segment(), *dqt_segments(quality), sof0_segment(h, w, sampling), *dht_segments(),
+                     dri_segment(mcu_grid(h, w, sampling)[1]), sos_segment()])
 
 
 def jpeg_file(header, scan_bytes):

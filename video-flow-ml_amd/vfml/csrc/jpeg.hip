@@ -2,10 +2,15 @@
 // the Annex K tables unoptimised, one MCU row per restart interval.  Integer arithmetic only; tests/jpeg_oracle.py is the
 // same definition in numpy and the stream equals its stream byte for byte.  The constant tables (zigzag, DCT matrix,
 // Huffman codes) are jpeg_tables.inc, printed from storage/jpeg_tables.py, the module that writes the file header.
+// vfml_jpeg_encode_rgb_sampled is the same encoder for 4:2:0, 4:2:2 and 4:4:4 (tests/jpeg_encode_sampling_oracle.py): the
+// sampling is a template parameter of the two kernels that know the MCU, and their 4:2:0 instantiation is the code of
+// vfml_jpeg_encode_rgb, which forwards to it.
 //
 // Five launches on one stream, no host pass over the entropy data and no synchronisation:
-//   transform   one wave per MCU (16 x 16 pixels, 4 per lane): colour conversion, 2x2 chroma mean across lanes, both DCT
-//               passes through LDS, quantisation; int16 coefficients in zigzag order, six blocks per MCU in scan order.
+//   transform   one wave per region of 16 x 16 pixels, 4 per lane - one 4:2:0 MCU, two 4:2:2 MCUs one above the other or
+//               four 4:4:4 MCUs: colour conversion, the chroma sample (4:2:0: 2x2 mean across lanes; 4:2:2: the pair's mean
+//               in the lane; 4:4:4: the sample), both DCT passes through LDS, quantisation; int16 coefficients in zigzag
+//               order, the blocks of an MCU in scan order, MCUs in raster order.
 //   entropy     one wave per 8 x 8 block, one lane per coefficient: the ballot of "non-zero" gives a lane its zero run and
 //               the end of block, a wave prefix sum its bit offset; the lanes OR their codes into the block's bit string
 //               in LDS (at most 1660 bits) and the used words and the bit length go to the workspace.
@@ -33,6 +38,8 @@ struct JpegArgs {
   int64_t stride;
   const unsigned char* qt;                // [2][64] natural order
   int rows, cols;                         // MCU rows, MCUs per row
+  int bpm;                                // blocks per MCU
+  int rrows, rcols;                       // the transform's 16 x 16 regions
   short* coef;                            // [blocks][64] zigzag
   unsigned* bits;                         // [blocks][kBlockWords]
   unsigned* blen;                         // [blocks] bit length
@@ -49,16 +56,29 @@ struct JpegArgs {
 __host__ __device__ inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 // ---- transform ---------------------------------------------------------------------------------------------------
+// The MCU of a sampling (VFML_JPEG_420 / 422 / 444) and the 16 x 16 pixel region one wave transforms.
+template <int S>
+struct Mcu {
+  static constexpr int kLumaV = S == 0 ? 2 : 1, kLumaH = S == 2 ? 1 : 2;  // luma blocks down and across an MCU
+  static constexpr int kLuma = kLumaV * kLumaH;
+  static constexpr int kBlocks = kLuma + 2;                                 // Y .. Cb Cr
+  static constexpr int kRegionV = 2 / kLumaV, kRegionH = 2 / kLumaH;        // MCUs down and across a region
+  static constexpr int kRegionBlocks = kRegionV * kRegionH * kBlocks;       // 6, 8, 12
+};
+
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_transform_kernel(const JpegArgs a) {
-  __shared__ int xs[4][6][64];
-  __shared__ int ts[4][6][64];
+  using M = Mcu<S>;
+  constexpr int NB = M::kRegionBlocks;
+  __shared__ int xs[4][NB][64];
+  __shared__ int ts[4][NB][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int nmcu = a.rows * a.cols;
+  const int nmcu = a.rrows * a.rcols;
   int mcu = blockIdx.x * 4 + wave;
   const bool valid = mcu < nmcu;
   if (!valid) mcu = nmcu - 1;
-  const int my = mcu / a.cols, mx = mcu - my * a.cols;
-  // lane -> row r of the MCU, columns 4q .. 4q+3
+  const int my = mcu / a.rcols, mx = mcu - my * a.rcols;
+  // lane -> row r of the region, columns 4q .. 4q+3
   const int r = lane >> 2, q = lane & 3;
   int py = my * 16 + r;
   py = py < a.h ? py : a.h - 1;
@@ -73,22 +93,42 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const JpegArgs a) {
     const int Cb = (-11059 * R - 21709 * G + 32768 * B + (128 << 16) + 32767) >> 16;
     const int Cr = (32768 * R - 27439 * G - 5329 * B + (128 << 16) + 32767) >> 16;
     const int c = 4 * q + j;
-    xs[wave][(r >> 3) * 2 + (c >> 3)][(r & 7) * 8 + (c & 7)] = Y - 128;
-    if (j & 1) {
-      cbs[j >> 1] += Cb;
-      crs[j >> 1] += Cr;
-    } else {
-      cbs[j >> 1] = Cb;
-      crs[j >> 1] = Cr;
+    if constexpr (S == 0) {
+      xs[wave][(r >> 3) * 2 + (c >> 3)][(r & 7) * 8 + (c & 7)] = Y - 128;
+    } else if constexpr (S == 1) {        // MCU r >> 3 of the region: Y0 Y1 Cb Cr
+      xs[wave][(r >> 3) * 4 + (c >> 3)][(r & 7) * 8 + (c & 7)] = Y - 128;
+    } else {                              // MCU (r >> 3, c >> 3) of the region: Y Cb Cr
+      const int at = (r & 7) * 8 + (c & 7), b0 = ((r >> 3) * 2 + (c >> 3)) * 3;
+      xs[wave][b0][at] = Y - 128;
+      xs[wave][b0 + 1][at] = Cb - 128;
+      xs[wave][b0 + 2][at] = Cr - 128;
+    }
+    if constexpr (S != 2) {
+      if (j & 1) {
+        cbs[j >> 1] += Cb;
+        crs[j >> 1] += Cr;
+      } else {
+        cbs[j >> 1] = Cb;
+        crs[j >> 1] = Cr;
+      }
     }
   }
+  if constexpr (S == 0) {
 #pragma unroll
-  for (int p = 0; p < 2; ++p) {           // the other row of the 2x2 cell is four lanes away
-    const int cb = cbs[p] + __shfl_xor(cbs[p], 4), cr = crs[p] + __shfl_xor(crs[p], 4);
-    if (!(r & 1)) {
-      const int at = (r >> 1) * 8 + 2 * q + p;
-      xs[wave][4][at] = ((cb + 2) >> 2) - 128;
-      xs[wave][5][at] = ((cr + 2) >> 2) - 128;
+    for (int p = 0; p < 2; ++p) {         // the other row of the 2x2 cell is four lanes away
+      const int cb = cbs[p] + __shfl_xor(cbs[p], 4), cr = crs[p] + __shfl_xor(crs[p], 4);
+      if (!(r & 1)) {
+        const int at = (r >> 1) * 8 + 2 * q + p;
+        xs[wave][4][at] = ((cb + 2) >> 2) - 128;
+        xs[wave][5][at] = ((cr + 2) >> 2) - 128;
+      }
+    }
+  } else if constexpr (S == 1) {
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {         // the horizontal pair is the lane's own
+      const int at = (r & 7) * 8 + 2 * q + p;
+      xs[wave][(r >> 3) * 4 + 2][at] = ((cbs[p] + 1) >> 1) - 128;
+      xs[wave][(r >> 3) * 4 + 3][at] = ((crs[p] + 1) >> 1) - 128;
     }
   }
   __syncthreads();
@@ -99,7 +139,7 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const JpegArgs a) {
 #pragma unroll
     for (int m = 0; m < 8; ++m) ck[m] = kJpegDct[k * 8 + m];
 #pragma unroll
-    for (int b = 0; b < 6; ++b) {
+    for (int b = 0; b < NB; ++b) {
       int acc = 1024;
 #pragma unroll
       for (int m = 0; m < 8; ++m) acc += ck[m] * xs[wave][b][m * 8 + n];
@@ -116,16 +156,24 @@ __global__ __launch_bounds__(256) void jpeg_transform_kernel(const JpegArgs a) {
     for (int n = 0; n < 8; ++n) cl[n] = kJpegDct[l * 8 + n];
     const int q0 = a.qt[nat], q1 = a.qt[64 + nat];
 #pragma unroll
-    for (int b = 0; b < 6; ++b) {
+    for (int b = 0; b < NB; ++b) {
       int acc = 16384;
 #pragma unroll
       for (int n = 0; n < 8; ++n) acc += ts[wave][b][k * 8 + n] * cl[n];
       const int y = acc >> 15;
-      const int qq = b < 4 ? q0 : q1;
+      const int qq = b % M::kBlocks < M::kLuma ? q0 : q1;
       int v = ((y < 0 ? -y : y) + (qq >> 1)) / qq;
       if (lane > 0 && v > 1023) v = 1023;
       if (y < 0) v = -v;
-      if (valid) a.coef[((int64_t)mcu * 6 + b) * 64 + lane] = (short)v;
+      if constexpr (S == 0) {
+        if (valid) a.coef[((int64_t)mcu * 6 + b) * 64 + lane] = (short)v;
+      } else {                            // block b of the region -> its MCU, which may lie outside the grid
+        constexpr int kPerRow = M::kRegionH;
+        const int m = b / M::kBlocks;
+        const int gy = my * M::kRegionV + m / kPerRow, gx = mx * kPerRow + m % kPerRow;
+        if (valid && gy < a.rows && gx < a.cols)
+          a.coef[(((int64_t)gy * a.cols + gx) * M::kBlocks + b % M::kBlocks) * 64 + lane] = (short)v;
+      }
     }
   }
 }
@@ -141,17 +189,19 @@ __device__ __forceinline__ void put_bits(unsigned* words, unsigned at, unsigned 
   if (sh + len > 32) atomicOr(&words[wd + 1], (unsigned)x);
 }
 
+template <int S>
 __global__ __launch_bounds__(256) void jpeg_entropy_kernel(const JpegArgs a) {
+  constexpr int BPM = Mcu<S>::kBlocks, LUMA = Mcu<S>::kLuma;
   __shared__ unsigned words[4][kBlockWords];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t nblk = (int64_t)a.rows * a.cols * 6;
+  const int64_t nblk = (int64_t)a.rows * a.cols * BPM;
   int64_t g = (int64_t)blockIdx.x * 4 + wave;
   const bool valid = g < nblk;
   if (!valid) g = nblk - 1;
-  const int64_t mcu = g / 6;
-  const int b = (int)(g - mcu * 6);
+  const int64_t mcu = g / BPM;
+  const int b = (int)(g - mcu * BPM);
   const int col = (int)(mcu % a.cols);
-  const int tc = b < 4 ? 0 : 1;
+  const int tc = b < LUMA ? 0 : 1;
   if (lane < kBlockWords) words[wave][lane] = 0;
   int c = a.coef[g * 64 + lane];
   if (lane > 0) c = c < -1023 ? -1023 : (c > 1023 ? 1023 : c);     // (as written by the transform: bounds the bit string)
@@ -163,10 +213,10 @@ __global__ __launch_bounds__(256) void jpeg_entropy_kernel(const JpegArgs a) {
   int plen = 0, nzrl = 0;
   if (lane == 0) {
     int pred = 0;                         // the previous block of the component in this interval
-    if (b > 0 && b < 4)
+    if (b > 0 && b < LUMA)
       pred = a.coef[(g - 1) * 64];
-    else if (col > 0)
-      pred = a.coef[(b == 0 ? g - 3 : g - 6) * 64];
+    else if (col > 0)                     // the last luma block, or the same chroma block, of the MCU in front
+      pred = a.coef[(b == 0 ? g - BPM + LUMA - 1 : g - BPM) * 64];
     int d = c - pred;
     d = d < -2047 ? -2047 : (d > 2047 ? 2047 : d);
     const int s = bit_size(d);
@@ -236,7 +286,7 @@ __device__ __forceinline__ unsigned block_scan(unsigned v, unsigned* part, unsig
 __global__ __launch_bounds__(kIntervalThreads) void jpeg_interval_kernel(const JpegArgs a) {
   __shared__ unsigned part[kIntervalThreads / 64];
   const int r = blockIdx.x, tid = threadIdx.x;
-  const int nb = a.cols * 6;
+  const int nb = a.cols * a.bpm;
   const unsigned* blen = a.blen + (int64_t)r * nb;
   unsigned* boff = a.boff + (int64_t)r * nb;
   const unsigned* bits = a.bits + (int64_t)r * nb * kBlockWords;
@@ -335,15 +385,21 @@ __global__ __launch_bounds__(256) void jpeg_compact_kernel(const JpegArgs a) {
 }
 
 struct JpegLayout {
-  int rows, cols;
+  int rows, cols, bpm, rrows, rcols;
   int64_t blocks, row_cap, coef, bits, blen, boff, stage, ilen, ioff, bytes;
+  int64_t scan_max() const { return (int64_t)rows * ((int64_t)cols * bpm * kBlockBytesMax + 2); }   // RSTm after every row
 };
 
-bool jpeg_layout(int h, int w, JpegLayout& L) {
-  if (h < 1 || w < 1 || h > 65535 || w > 65535) return false;
-  L.rows = (h + 15) / 16, L.cols = (w + 15) / 16;
-  L.blocks = (int64_t)L.rows * L.cols * 6;
-  L.row_cap = align256((int64_t)L.cols * 6 * kBlockBytesMax + 2);
+bool jpeg_sampling_ok(int sampling) { return sampling == VFML_JPEG_420 || sampling == VFML_JPEG_422 || sampling == VFML_JPEG_444; }
+
+bool jpeg_layout(int h, int w, int sampling, JpegLayout& L) {
+  if (h < 1 || w < 1 || h > 65535 || w > 65535 || !jpeg_sampling_ok(sampling)) return false;
+  const int mh = sampling == VFML_JPEG_420 ? 16 : 8, mw = sampling == VFML_JPEG_444 ? 8 : 16;
+  L.rows = (h + mh - 1) / mh, L.cols = (w + mw - 1) / mw;
+  L.bpm = sampling == VFML_JPEG_420 ? 6 : (sampling == VFML_JPEG_422 ? 4 : 3);
+  L.rrows = (h + 15) / 16, L.rcols = (w + 15) / 16;
+  L.blocks = (int64_t)L.rows * L.cols * L.bpm;
+  L.row_cap = align256((int64_t)L.cols * L.bpm * kBlockBytesMax + 2);
   int64_t at = 0;
   L.coef = at, at += align256(L.blocks * 64 * 2);
   L.bits = at, at += align256(L.blocks * kBlockWords * 4);
@@ -354,36 +410,35 @@ bool jpeg_layout(int h, int w, JpegLayout& L) {
   L.ioff = at, at += align256(L.rows * 4);
   L.bytes = at;
   // the scan's worst case must fit the 32-bit length cell and the 32-bit offsets
-  return (int64_t)L.rows * ((int64_t)L.cols * 6 * kBlockBytesMax + 2) <= 0xFFFFFFFFll;
+  return L.scan_max() <= 0xFFFFFFFFll;
 }
 
-}  // namespace
-
-extern "C" int64_t vfml_jpeg_workspace_bytes(int h, int w) {
-  JpegLayout L;
-  return jpeg_layout(h, w, L) ? L.bytes : 0;
+template <int S>
+void jpeg_launch(const JpegArgs& a, const JpegLayout& L, hipStream_t s) {
+  const int64_t nregion = (int64_t)L.rrows * L.rcols;
+  hipLaunchKernelGGL(jpeg_transform_kernel<S>, dim3((unsigned)((nregion + 3) / 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_entropy_kernel<S>, dim3((unsigned)((L.blocks + 3) / 4)), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_interval_kernel, dim3(L.rows), dim3(kIntervalThreads), 0, s, a);
+  hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(jpeg_compact_kernel, dim3(32, L.rows), dim3(256), 0, s, a);
 }
 
-extern "C" int64_t vfml_jpeg_scan_capacity(int h, int w) {
+int jpeg_encode(const char* name, const unsigned char* rgb, int h, int w, int64_t row_stride, int sampling,
+                const unsigned char* qtables, void* workspace, unsigned char* scan, int64_t scan_capacity,
+                uint32_t* scan_bytes, void* stream) {
   JpegLayout L;
-  return jpeg_layout(h, w, L) ? (int64_t)L.rows * ((int64_t)L.cols * 6 * kBlockBytesMax + 2) - 2 : 0;
-}
-
-extern "C" int vfml_jpeg_encode_rgb(const unsigned char* rgb, int h, int w, int64_t row_stride,
-                                    const unsigned char* qtables, void* workspace, unsigned char* scan,
-                                    int64_t scan_capacity, uint32_t* scan_bytes, void* stream) {
-  JpegLayout L;
-  VFML_REQUIRE(jpeg_layout(h, w, L), "vfml_jpeg_encode_rgb: picture %dx%d (sides of 1..65535, worst-case scan below 4 GiB)",
-               w, h);
-  VFML_REQUIRE(rgb && qtables && workspace && scan && scan_bytes, "vfml_jpeg_encode_rgb: null argument");
-  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "vfml_jpeg_encode_rgb: row stride %lld below the row's %d bytes",
-               (long long)row_stride, 3 * w);
-  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "vfml_jpeg_encode_rgb: workspace must be 256-byte aligned");
-  VFML_REQUIRE((reinterpret_cast<uintptr_t>(scan_bytes) & 3u) == 0, "vfml_jpeg_encode_rgb: scan_bytes must be 4-byte aligned");
-  VFML_REQUIRE(scan_capacity >= 0, "vfml_jpeg_encode_rgb: negative scan capacity");
+  VFML_REQUIRE(jpeg_sampling_ok(sampling), "%s: sampling %d (VFML_JPEG_420, VFML_JPEG_422 and VFML_JPEG_444 are encoded)", name,
+               sampling);
+  VFML_REQUIRE(jpeg_layout(h, w, sampling, L), "%s: picture %dx%d (sides of 1..65535, worst-case scan below 4 GiB)", name, w, h);
+  VFML_REQUIRE(rgb && qtables && workspace && scan && scan_bytes, "%s: null argument", name);
+  VFML_REQUIRE(row_stride >= (int64_t)3 * w, "%s: row stride %lld below the row's %d bytes", name, (long long)row_stride, 3 * w);
+  VFML_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255u) == 0, "%s: workspace must be 256-byte aligned", name);
+  VFML_REQUIRE((reinterpret_cast<uintptr_t>(scan_bytes) & 3u) == 0, "%s: scan_bytes must be 4-byte aligned", name);
+  VFML_REQUIRE(scan_capacity >= 0, "%s: negative scan capacity", name);
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   JpegArgs a;
   a.rgb = rgb, a.h = h, a.w = w, a.stride = row_stride, a.qt = qtables, a.rows = L.rows, a.cols = L.cols;
+  a.bpm = L.bpm, a.rrows = L.rrows, a.rcols = L.rcols;
   a.coef = reinterpret_cast<short*>(ws + L.coef);
   a.bits = reinterpret_cast<unsigned*>(ws + L.bits);
   a.blen = reinterpret_cast<unsigned*>(ws + L.blen);
@@ -393,11 +448,41 @@ extern "C" int vfml_jpeg_encode_rgb(const unsigned char* rgb, int h, int w, int6
   a.ioff = reinterpret_cast<unsigned*>(ws + L.ioff);
   a.scan = scan, a.cap = scan_capacity, a.total = scan_bytes;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int64_t nmcu = (int64_t)L.rows * L.cols;
-  hipLaunchKernelGGL(jpeg_transform_kernel, dim3((unsigned)((nmcu + 3) / 4)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)((L.blocks + 3) / 4)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(jpeg_interval_kernel, dim3(L.rows), dim3(kIntervalThreads), 0, s, a);
-  hipLaunchKernelGGL(jpeg_offsets_kernel, dim3(1), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(jpeg_compact_kernel, dim3(32, L.rows), dim3(256), 0, s, a);
-  return vfml_check_launch("vfml_jpeg_encode_rgb");
+  if (sampling == VFML_JPEG_420)
+    jpeg_launch<0>(a, L, s);
+  else if (sampling == VFML_JPEG_422)
+    jpeg_launch<1>(a, L, s);
+  else
+    jpeg_launch<2>(a, L, s);
+  return vfml_check_launch(name);
+}
+
+}  // namespace
+
+extern "C" int64_t vfml_jpeg_sampled_workspace_bytes(int h, int w, int sampling) {
+  JpegLayout L;
+  return jpeg_layout(h, w, sampling, L) ? L.bytes : 0;
+}
+
+extern "C" int64_t vfml_jpeg_sampled_scan_capacity(int h, int w, int sampling) {
+  JpegLayout L;
+  return jpeg_layout(h, w, sampling, L) ? L.scan_max() - 2 : 0;
+}
+
+extern "C" int vfml_jpeg_encode_rgb_sampled(const unsigned char* rgb, int h, int w, int64_t row_stride, int sampling,
+                                            const unsigned char* qtables, void* workspace, unsigned char* scan,
+                                            int64_t scan_capacity, uint32_t* scan_bytes, void* stream) {
+  return jpeg_encode("vfml_jpeg_encode_rgb_sampled", rgb, h, w, row_stride, sampling, qtables, workspace, scan, scan_capacity,
+                     scan_bytes, stream);
+}
+
+extern "C" int64_t vfml_jpeg_workspace_bytes(int h, int w) { return vfml_jpeg_sampled_workspace_bytes(h, w, VFML_JPEG_420); }
+
+extern "C" int64_t vfml_jpeg_scan_capacity(int h, int w) { return vfml_jpeg_sampled_scan_capacity(h, w, VFML_JPEG_420); }
+
+extern "C" int vfml_jpeg_encode_rgb(const unsigned char* rgb, int h, int w, int64_t row_stride,
+                                    const unsigned char* qtables, void* workspace, unsigned char* scan,
+                                    int64_t scan_capacity, uint32_t* scan_bytes, void* stream) {
+  return jpeg_encode("vfml_jpeg_encode_rgb", rgb, h, w, row_stride, VFML_JPEG_420, qtables, workspace, scan, scan_capacity,
+                     scan_bytes, stream);
 }

@@ -190,6 +190,12 @@ def lib():
     L.vfml_jpeg_scan_capacity.argtypes = [c_int, c_int]
     L.vfml_jpeg_encode_rgb.argtypes = [c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                        c_void_p]
+    L.vfml_jpeg_sampled_workspace_bytes.restype = c_int64
+    L.vfml_jpeg_sampled_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.vfml_jpeg_sampled_scan_capacity.restype = c_int64
+    L.vfml_jpeg_sampled_scan_capacity.argtypes = [c_int, c_int, c_int]
+    L.vfml_jpeg_encode_rgb_sampled.argtypes = [c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                               c_void_p, c_void_p]
     L.vfml_jpeg_decode_workspace_bytes.restype = c_int64
     L.vfml_jpeg_decode_workspace_bytes.argtypes = [c_int, c_int, c_int64]
     L.vfml_jpeg_decode_rgb.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -231,6 +237,7 @@ EXPORTS = [
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
+    "vfml_jpeg_sampled_workspace_bytes", "vfml_jpeg_sampled_scan_capacity", "vfml_jpeg_encode_rgb_sampled",
     "vfml_jpeg_decode_workspace_bytes", "vfml_jpeg_decode_rgb",
     "vfml_jpeg_decode_sync_workspace_bytes", "vfml_jpeg_decode_rgb_sync",
     "vfml_jpeg_decode_sampled_workspace_bytes", "vfml_jpeg_decode_rgb_sampled",
@@ -976,10 +983,20 @@ _JPEG_WS = {}
 _JPEG_QT = {}
 
 
-def jpeg_header(h, w, quality=95):
+JPEG_ENCODE_SAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2}      # VFML_JPEG_* of include/vfml.h that the encoder builds
+
+
+def _jpeg_encode_sampling(sampling):
+    code = JPEG_ENCODE_SAMPLINGS.get(sampling)
+    if code is None:
+        raise ValueError(f"jpeg_encode: sampling {sampling!r}; {', '.join(JPEG_ENCODE_SAMPLINGS)} are built")
+    return code
+
+
+def jpeg_header(h, w, quality=95, sampling="4:2:0"):
     """The bytes in front of the scan that jpeg_encode writes (storage/jpeg_tables.py jpeg_header)."""
     from storage import jpeg_tables
-    return jpeg_tables.jpeg_header(h, w, quality)
+    return jpeg_tables.jpeg_header(h, w, quality, sampling)
 
 
 def jpeg_file(header, scan_bytes):
@@ -988,21 +1005,23 @@ def jpeg_file(header, scan_bytes):
     return jpeg_tables.jpeg_file(header, scan_bytes)
 
 
-def jpeg_scan_capacity(h, w):
-    """Bytes that hold the scan of any h x w picture (vfml_jpeg_scan_capacity)."""
-    return int(lib().vfml_jpeg_scan_capacity(int(h), int(w)))
+def jpeg_scan_capacity(h, w, sampling="4:2:0"):
+    """Bytes that hold the scan of any h x w picture (vfml_jpeg_sampled_scan_capacity)."""
+    return int(lib().vfml_jpeg_sampled_scan_capacity(int(h), int(w), _jpeg_encode_sampling(sampling)))
 
 
-def jpeg_encode(rgb, quality=95, out=None):
+def jpeg_encode(rgb, quality=95, out=None, sampling="4:2:0"):
     """RGB picture, uint8 device tensor [H,W,3] whose rows are contiguous (a row slice of a larger or wider buffer
     included: the row stride is the tensor's) -> (scan, length): the entropy-coded data of its baseline JPEG (DESIGN.md
     section 12) in a uint8 device tensor and its byte count in a uint32-valued int32 device cell [1]
-    (vfml_jpeg_encode_rgb: stream-ordered, no synchronisation).  jpeg_header(H, W, quality) + the first `length` bytes of
-    the scan + EOI is the file (jpeg_file); jpeg_scan reads them back and checks the length.
+    (vfml_jpeg_encode_rgb_sampled: stream-ordered, no synchronisation).  sampling: '4:2:0', '4:2:2' or '4:4:4'.
+    jpeg_header(H, W, quality, sampling) + the first `length` bytes of the scan + EOI is the file (jpeg_file); jpeg_scan
+    reads them back and checks the length.
     out: a contiguous uint8 device tensor that receives the scan - its size is the capacity, nothing is written past
     it; None: one of the worst-case size is allocated.  The workspace and the quantisation tables are kept per device,
-    picture size / quality and stream."""
+    picture size and sampling / quality and stream."""
     from storage import jpeg_tables
+    samp = _jpeg_encode_sampling(sampling)
     if not (torch.is_tensor(rgb) and rgb.is_cuda and rgb.dtype == torch.uint8 and rgb.dim() == 3 and rgb.shape[2] == 3
             and rgb.shape[0] >= 1 and rgb.shape[1] >= 1 and rgb.stride(2) == 1 and rgb.stride(1) == 3
             and (rgb.shape[0] == 1 or rgb.stride(0) >= 3 * rgb.shape[1])):
@@ -1011,11 +1030,11 @@ def jpeg_encode(rgb, quality=95, out=None):
     h, w = int(rgb.shape[0]), int(rgb.shape[1])
     stride = int(rgb.stride(0)) if h > 1 else 3 * w
     L = lib()
-    need = int(L.vfml_jpeg_workspace_bytes(h, w))
+    need = int(L.vfml_jpeg_sampled_workspace_bytes(h, w, samp))
     if need == 0:
         raise ValueError(f"jpeg_encode: picture {w}x{h} is too large for a JPEG")
     stream = torch.cuda.current_stream().cuda_stream
-    key = (rgb.device.index, h, w, stream)
+    key = (rgb.device.index, h, w, stream, samp)
     ws = _JPEG_WS.get(key)
     if ws is None:
         ws = _JPEG_WS[key] = torch.empty(need, dtype=torch.uint8, device=rgb.device)
@@ -1024,14 +1043,15 @@ def jpeg_encode(rgb, quality=95, out=None):
     if qt is None:
         qt = _JPEG_QT[qkey] = torch.from_numpy(jpeg_tables.quant_tables(quality).copy()).to(rgb.device)
     if out is None:
-        out = torch.empty(jpeg_scan_capacity(h, w), dtype=torch.uint8, device=rgb.device)
+        out = torch.empty(jpeg_scan_capacity(h, w, sampling), dtype=torch.uint8, device=rgb.device)
     elif not (torch.is_tensor(out) and out.dtype == torch.uint8 and out.device == rgb.device and out.dim() == 1
               and out.is_contiguous()):
         raise ValueError("jpeg_encode: out must be a contiguous one-dimensional uint8 tensor on the picture's device")
     length = torch.empty(1, dtype=torch.int32, device=rgb.device)
-    _check(L.vfml_jpeg_encode_rgb(c_void_p(rgb.data_ptr()), h, w, stride, c_void_p(qt.data_ptr()), c_void_p(ws.data_ptr()),
-                                  c_void_p(out.data_ptr()), out.numel(), c_void_p(length.data_ptr()), _stream()),
-           "vfml_jpeg_encode_rgb")
+    _check(L.vfml_jpeg_encode_rgb_sampled(c_void_p(rgb.data_ptr()), h, w, stride, samp, c_void_p(qt.data_ptr()),
+                                          c_void_p(ws.data_ptr()), c_void_p(out.data_ptr()), out.numel(),
+                                          c_void_p(length.data_ptr()), _stream()),
+           "vfml_jpeg_encode_rgb_sampled")
     return out, length
 
 
