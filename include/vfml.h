@@ -31,7 +31,7 @@ extern "C" {
  * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
  * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
  * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
- * the three vfml_jpeg_*_sampled entry points of the encoder. */
+ * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well. */
 #define VFML_ABI_VERSION 26
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -502,6 +502,34 @@ enum { VFML_COMPOSE_SIDE_BY_SIDE = 0, VFML_COMPOSE_STACKED = 1, VFML_COMPOSE_GRI
 enum { VFML_COMPOSE_BGR = 1, VFML_COMPOSE_BOTTOM_UP = 2 };
 int vfml_compose_frame(const void* const* tiles, const int* tile_types, int h, int w, int layout, int flags,
                        int64_t row_stride, unsigned char* out, void* stream);
+
+/* Text labels and dimmed rectangles on a composed frame, in place (the reference's cv2.putText / addWeighted calls:
+ * visualization/video_composer.py :60-63, :206-218, flow_processor.py :570-576).  The text is this project's own: the
+ * stroke font of visualization/stroke_font.py, positions in 1/64 px, integer coverage and blending (DESIGN.md section 9,
+ * "Text"; tests/text_oracle.py states the rule).  Not pinned against cv2.
+ * img: [h][w][3] u8, rows of row_stride bytes (>= 3 w; bytes past 3 w are not touched), channels in memory order - a
+ * colour's byte k goes to channel k; flags: VFML_COMPOSE_BOTTOM_UP when row 0 of the picture is the buffer's last row.
+ * Stream-ordered, no allocation, no synchronisation.
+ * plan: a HOST pointer to plan_words int32 words, written by visualization.text.build_plan.  The entry point checks
+ * these words completely before the launch (a truncated plan, an offset outside plan_words, a box or clip outside the
+ * image, intersecting boxes and out-of-range geometry are rejected; no GPU is needed for that).  The kernel reads an
+ * identical copy in device memory, whose address the host words carry (words 2..3), and bounds again every count,
+ * offset and coordinate it takes from that copy.
+ *   header   [0] 0x54584656  [1] plan_words  [2] [3] device address of the copy, low and high half
+ *            [4] boxes  [5] operations  [6] glyphs  [7] segments            the sections follow in this order, packed
+ *   box      x0 y0 x1 y1 (pixels, inclusive, inside the image)  first operation  operations  first block  0
+ *            Boxes are pairwise disjoint.  One thread owns one pixel of one box and applies the box's operations in
+ *            order; a box takes ceil(width / 32) * ceil(height / 8) blocks, `first block` is the running sum.
+ *   op       kind  clip x0 y0 x1 y1 (pixels, inclusive, inside the image)  colour c0 | c1 << 8 | c2 << 16
+ *            radius = 32 thickness  anti-aliased 0 / 1  origin x y (1/64 px)  first glyph  glyphs
+ *            kind 0 TEXT: out = (colour n + dst (16 - n) + 8) >> 4, n = samples of the pixel within `radius` of a segment
+ *            (16 samples at 4 (2 i + 1), 4 (2 j + 1) when anti-aliased, else the pixel centre and n = 0 or 16);
+ *            kind 1 DIM_RECT: out = (3 dst + 5) / 10 inside the clip; the words behind the clip are 0.
+ *   glyph    x0 y0 x1 y1: the box of its segments relative to the origin (1/64 px, at most 2^14 wide and high)
+ *            first segment  segments  0  0
+ *   segment  x0 y0 x1 y1 relative to the origin (1/64 px), inside its glyph's box */
+int vfml_text_draw(const int32_t* plan, int plan_words, unsigned char* img, int h, int w, int64_t row_stride, int flags,
+                   void* stream);
 
 /* Turbulence map of a flow field (reference flow_visualizer.py: generate_turbulence_map :2997-3052): a heat map of the
  * local standard deviation of the flow vectors, all on `stream`, no host synchronisation, no allocation.

@@ -77,10 +77,23 @@ def qa_tiles_resident(frame1, frame2, flow, kernel_size=25, threshold=0.8):
     return [frame1, wheel, quality, turbulence]
 
 
+QA_LABELS = ((0, "Original"), (2, "Quality map"), (3, "Turbulence map"))      # (tile of the 2x2 grid, its label)
+
+
+def qa_label_ops(h, w):
+    """The draw list of the QA grid's labels for tiles of h x w: each at its tile's top-left corner, clipped to it."""
+    from visualization import text as vtext
+    ops = []
+    for tile, label in QA_LABELS:
+        ops += vtext.overlay_ops(label, 'top-left', h, w, ((tile % 2) * w, (tile // 2) * h))
+    return ops
+
+
 def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', kernel_size=25, threshold=0.8,
-                    uncompressed=False, fps=30.0, log=print, sampling="4:2:0"):
+                    uncompressed=False, fps=30.0, log=print, sampling="4:2:0", labels=False):
     """Write the QA grid of every cache frame in `frame_indices` to `output`; -> the number of frames written.
-    sampling: '4:2:0', '4:2:2' or '4:4:4', the chroma sampling of the MJPG frames."""
+    sampling: '4:2:0', '4:2:2' or '4:4:4', the chroma sampling of the MJPG frames.  labels: draw "Original",
+    "Quality map" and "Turbulence map" on their tiles (vfml_text_draw behind the composer)."""
     from storage.avi_writer import AviWriter, dib_stride
     from storage.cache_manager import FlowCacheManager
     from vfml import hip
@@ -96,6 +109,10 @@ def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', ker
     if not uncompressed:           # MJPG frames are encoded on the device (vfml_jpeg_encode_rgb); only the scan comes back
         from storage.device_mjpg import DeviceMjpgEncoder
         jpeg = DeviceMjpgEncoder(writer, 2 * h, 2 * w, device, sampling=sampling)
+    text_plan = None
+    if labels:
+        from visualization.text import build_plan
+        text_plan = hip.TextPlan(build_plan(qa_label_ops(h, w), 2 * h, 2 * w), device)
     written = 0
     try:
         for i in frame_indices:
@@ -112,6 +129,8 @@ def render_qa_video(frames, cache_dir, output, frame_indices, device='cuda', ker
             fl = torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32)).to(device)
             out = hip.compose_frame(qa_tiles_resident(f1, f2, fl, k, threshold), hip.COMPOSE_GRID_2X2, bgr=uncompressed,
                                     bottom_up=uncompressed, row_stride=stride)
+            if text_plan is not None:
+                hip.text_draw(text_plan, out, 2 * h, 2 * w, row_stride=stride, bottom_up=uncompressed)
             if jpeg is not None:
                 jpeg.submit(out.view(2 * h, 2 * w, 3))
             else:
@@ -154,11 +173,13 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     _check_kernel_size(args.kernel_size)
     _require_cuda(args.device, "flow_maps")
+    from visualization.video_composer import labels_switch
+    labels = labels_switch()                # VFML_LABELS=1: the tiles are labelled; any value but 1 / 0 is refused
     frames = _load_frames(args.input)
     stop = len(frames) if args.frames is None else min(len(frames), args.start_frame + args.frames)
     written = render_qa_video(frames, args.flow_cache, args.output, list(range(args.start_frame, stop)),
                               device=args.device, kernel_size=args.kernel_size, threshold=args.threshold,
-                              uncompressed=args.uncompressed)
+                              uncompressed=args.uncompressed, labels=labels)
     print(f"wrote {written} QA frames to {args.output}")
     return 0
 

@@ -15,8 +15,10 @@ vfml_taa_blend / vfml_compose_frame, or with the host paths under --device cpu. 
 reference's comparison mode, :436-578, :724-765, :1009-1127) a second video carries external motion vectors in its
 bottom half - the layout `--flow-only --flow-format motion-vectors-rg8|rgb8` writes - and the output is a 2x3 grid:
 original | external flow picture over TAA | TAA simple over TAA with the external flow | flow difference
-(vfml_flow_decode, vfml_flow_diff_overlay, the GRID_2X3 layout of vfml_compose_frame).  Out of scope:
-text labels on the tiles and the Tk/Qt tools; flags that only concern those are accepted and reported as skipped.
+(vfml_flow_decode, vfml_flow_diff_overlay, the GRID_2X3 layout of vfml_compose_frame).  The reference's text labels
+("Original", "TAA + Inv.Flow", the legend's numbers, ...) are drawn with the project's own text (vfml_text_draw on the
+device path, visualization/text.py on the host) when DRAW_LABELS / VFML_LABELS=1 says so; off by default.  Out of scope
+(DESIGN.md): the Tk/Qt tools; flags that only concern those are accepted and reported as skipped.
 With --fast the frames are first reduced by the reference's rule (video/frame_extractor.py: fit 256x256, at most a
 quarter / a half of the source, even sides, at least 64) and the whole job runs at that size: on a GPU the frames go up at
 source size and vfml_resize_u8 reduces them behind the upload (vfml.runner.ClipFeeder), --device cpu resizes on the host.
@@ -377,6 +379,19 @@ def mjpg_sampling():
     return value
 
 
+# True: the output video carries the reference's text labels, drawn with the project's own text (DESIGN.md section 9,
+# "Text"): vfml_text_draw behind the composer on the device path, visualization/text.py under --device cpu.  The
+# environment variable VFML_LABELS=1|0 overrides it.  Off: the fixtures cut from the reference and the render tests pin
+# the frames without text.
+DRAW_LABELS = False
+
+
+def draw_labels():
+    """DRAW_LABELS, or VFML_LABELS when it is set; a value other than 1 or 0 is refused."""
+    from visualization.video_composer import labels_switch
+    return labels_switch(DRAW_LABELS)
+
+
 def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feeder=None, log=print):
     """Render the complete flow cache into the output AVI (reference process_video :958-1130, one frame at a time in
     its order): flow picture, the two TAA histories (--taa), the composed frame, the writer.  Device path: the frames
@@ -415,6 +430,8 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
             external = _ExternalFlowSource(args.flow_input, n, width, height, log, device=device)
             size = (width * 2, height * 3)
     sampling = mjpg_sampling()
+    labels = draw_labels()
+    model_name = "VideoFlow"    # (the reference's process_video :1124 never sees its other name: it has no `model` attribute)
     if args.uncompressed:
         log("Using uncompressed video codec. Output will be .avi and file size will be very large.")
     else:
@@ -459,14 +476,18 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
                                                      sequence_id='external_taa')
                     writer.write(create_6_video_grid(frames[i], encoder.encode(ext_flow, width, height), taa_frame,
                                                      taa_simple_frame, taa_ext,
-                                                     create_difference_overlay(field, ext_flow)))
+                                                     create_difference_overlay(field, ext_flow, labels=labels),
+                                                     labels=labels))
                     continue
                 writer.write(create_side_by_side(frames[i], viz, flow_only=flow_only, taa_frame=taa_frame,
-                                                 taa_simple_frame=taa_simple_frame, flow_format=args.flow_format))
+                                                 taa_simple_frame=taa_simple_frame, model_name=model_name,
+                                                 fast_mode=args.fast, flow_format=args.flow_format, labels=labels))
         else:
             _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size,
                            args.uncompressed, taa_flow, taa_simple, dib_stride, compose_device, external=external,
-                           taa_external=taa_external, variant=variant, clamp_range=args.motion_vectors_clamp_range)
+                           taa_external=taa_external, variant=variant, clamp_range=args.motion_vectors_clamp_range,
+                           label_ops=_label_ops(width, height, taa, flow_only, external is not None, model_name,
+                                                args.fast, args.flow_format) if labels else None)
     finally:
         if external is not None:
             external.close()
@@ -477,11 +498,29 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     return 0
 
 
+def _label_ops(width, height, taa, flow_only, grid6, model_name, fast_mode, flow_format):
+    """The draw list of a layout's labels in frame coordinates, as the host composer draws them: the tiles' labels with
+    tile clips; for the 2x3 grid the legend's numbers on the difference tile, then the six grid labels.  Black and
+    white only, so the list serves RGB and BGR frames alike."""
+    from visualization import text as vtext
+    if flow_only:
+        return []
+    if grid6:
+        return vtext.legend_ops(height, width, tile=(width, 2 * height)) + vtext.grid6_ops(height, width)
+    return vtext.side_by_side_ops(height, width, 2 if taa else 0, model_name, fast_mode, flow_format)
+
+
 def _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size, uncompressed,
                    taa_flow, taa_simple, dib_stride, compose_device, external=None, taa_external=None, variant=None,
-                   clamp_range=32.0):
+                   clamp_range=32.0, label_ops=None):
     from vfml import hip
     n = len(frames)
+    text_plan = None            # the labels of the layout, compiled once: drawn on every composed frame
+    if label_ops:
+        from visualization.text import build_plan
+        text_plan = hip.TextPlan(build_plan(label_ops, size[1], size[0]), device)
+        if text_plan.boxes == 0:
+            text_plan = None
     if feeder is None:
         feeder = ClipFeeder(frames, device, size=(height, width))      # (host frames of another size: --fast's source frames)
     stream = torch.cuda.current_stream()
@@ -557,6 +596,8 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
         out = compose_device(frame, viz, taa_frame, taa_simple_frame, flow_only=flow_only, bgr=uncompressed,
                              bottom_up=uncompressed, row_stride=stride, taa_external_frame=taa_ext,
                              difference_overlay=diff)
+        if text_plan is not None:
+            hip.text_draw(text_plan, out, size[1], size[0], row_stride=stride, bottom_up=uncompressed)
         if jpeg is not None:
             jpeg.submit(out.view(size[1], size[0], 3))
             continue
@@ -592,6 +633,7 @@ def main(argv=None):
     if args.flow_input is not None:
         check_flow_input(args)
     mjpg_sampling()             # a setting that is not built is refused before anything is computed or rendered
+    draw_labels()               # (likewise VFML_LABELS)
     if not (args.input.startswith('synthetic:') or os.path.exists(args.input)):
         log(f"Error: Input video not found: {args.input}")
         return 1

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -178,6 +178,7 @@ def lib():
     L.vfml_flow_diff_overlay.argtypes = [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vfml_compose_frame.argtypes = [POINTER(c_void_p), POINTER(c_int32), c_int, c_int, c_int, c_int, c_int64, c_void_p,
                                      c_void_p]
+    L.vfml_text_draw.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]
     L.vfml_flow_turbulence_workspace_bytes.argtypes = [c_int, c_int]
     L.vfml_flow_turbulence_workspace_bytes.restype = ctypes.c_size_t
     L.vfml_flow_turbulence_map.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -234,7 +235,7 @@ EXPORTS = [
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
-    "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay",
+    "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay", "vfml_text_draw",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
     "vfml_jpeg_workspace_bytes", "vfml_jpeg_scan_capacity", "vfml_jpeg_encode_rgb",
     "vfml_jpeg_sampled_workspace_bytes", "vfml_jpeg_sampled_scan_capacity", "vfml_jpeg_encode_rgb_sampled",
@@ -844,6 +845,38 @@ def compose_frame(tiles, layout, bgr=True, bottom_up=False, row_stride=None, out
     _check(lib().vfml_compose_frame(ptrs, types, h, w, layout, flags, stride, c_void_p(out.data_ptr()), _stream()),
            "vfml_compose_frame")
     return out
+
+
+class TextPlan:
+    """A compiled draw list (visualization.text.build_plan) ready for text_draw: the host words, which vfml_text_draw checks
+    before every launch, and their copy on `device`, which the kernel reads; the host words carry the copy's address."""
+
+    def __init__(self, words, device):
+        import numpy as np
+        self.host = np.array(words, dtype=np.int32)
+        if self.host.ndim != 1 or self.host.size < 8:
+            raise ValueError("TextPlan: a one-dimensional int32 plan of at least 8 words expected")
+        self.dev = torch.empty(self.host.size, dtype=torch.int32, device=device)
+        addr = self.dev.data_ptr()
+        self.host[2:4] = np.array([addr & 0xffffffff, addr >> 32], dtype=np.uint32).view(np.int32)
+        self.dev.copy_(torch.from_numpy(self.host))
+
+    @property
+    def boxes(self):
+        return int(self.host[4])
+
+
+def text_draw(plan, img, h, w, row_stride=None, bottom_up=False):
+    """Draw a TextPlan into a composed frame in place (vfml_text_draw): img is a contiguous uint8 device tensor holding
+    h rows of row_stride bytes (default 3 w), channels in memory order; bottom_up as compose_frame writes a DIB."""
+    stride = 3 * w if row_stride is None else int(row_stride)
+    if not (img.is_cuda and img.dtype == torch.uint8 and img.is_contiguous() and img.numel() >= h * stride):
+        raise ValueError(f"text_draw: img must be a contiguous uint8 device tensor of >= {h * stride} bytes")
+    if plan.dev.device != img.device:
+        raise ValueError(f"text_draw: the plan lives on {plan.dev.device}, the frame on {img.device}")
+    _check(lib().vfml_text_draw(plan.host.ctypes.data_as(c_void_p), plan.host.size, c_void_p(img.data_ptr()), h, w, stride,
+                                COMPOSE_BOTTOM_UP if bottom_up else 0, _stream()), "vfml_text_draw")
+    return img
 
 
 def flow_quality_map(frame1, frame2, flow, threshold):

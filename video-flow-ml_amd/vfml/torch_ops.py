@@ -10,6 +10,7 @@ custom-op boundaries, other PyTorch code):
     vfml::corr_volume(f1, f2, scale)                                     -> Tensor     K3 all-pairs correlation
     vfml::corr_lookup(pyramid, coords, hl, wl, radius)                   -> Tensor     K5 pyramid lookup
     vfml::convex_upsample(flow, mask)                                    -> Tensor     K8 8x convex upsampling
+    vfml::text_draw(frame, plan)                                         -> Tensor     text labels on a composed frame
 
 Only the CUDA (= HIP on ROCm) dispatch key has an implementation: on CPU tensors the dispatcher raises
 NotImplementedError - there is no CPU fallback, as everywhere in the engine.  Importing this module registers the ops
@@ -85,6 +86,16 @@ def _convex_upsample(flow, mask):
     return out
 
 
+def _text_draw(frame, plan):
+    """frame [h,w,3] u8 (device), plan: the int32 words of visualization.text.build_plan for an h x w frame (a CPU tensor)
+    -> a new frame with the plan's labels drawn (vfml_text_draw); channels in memory order."""
+    if frame.dim() != 3 or frame.shape[2] != 3 or frame.dtype != torch.uint8:
+        raise ValueError(f"text_draw: a [h,w,3] uint8 frame expected, got {frame.dtype} {tuple(frame.shape)}")
+    h, w = frame.shape[:2]
+    out = frame.contiguous().clone()
+    return hip.text_draw(hip.TextPlan(plan.cpu().to(torch.int32).numpy(), frame.device), out, h, w)
+
+
 def register():
     global _LIB
     if _LIB is not None:
@@ -94,10 +105,12 @@ def register():
     lib.define("corr_volume(Tensor f1, Tensor f2, float scale) -> Tensor")
     lib.define("corr_lookup(Tensor[] pyramid, Tensor coords, int[] hl, int[] wl, int radius) -> Tensor")
     lib.define("convex_upsample(Tensor flow, Tensor mask) -> Tensor")
+    lib.define("text_draw(Tensor frame, Tensor plan) -> Tensor")
     lib.impl("conv2d_nhwc", _conv2d_nhwc, "CUDA")
     lib.impl("corr_volume", _corr_volume, "CUDA")
     lib.impl("corr_lookup", _corr_lookup, "CUDA")
     lib.impl("convex_upsample", _convex_upsample, "CUDA")
+    lib.impl("text_draw", _text_draw, "CUDA")
     _LIB = lib
     return lib
 
