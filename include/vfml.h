@@ -210,6 +210,20 @@ int vfml_softmax_rows_s16(const float* x, int64_t rows, int cols, int64_t ld_in,
 int vfml_softmax_rows_f16(const float* x, int64_t rows, int cols, int64_t ld_in, void* out, int64_t ld_out, float scale,
                           void* stream);
 
+/* The attention plane of one frame in one call (csrc/attention.hip; SURVEY.md K7 for the GMA aggregator of MOF / BOF):
+ *   plane[i][j] = RTN_f16(prob_scale * softmax_j(score_scale * q_i . k_j)),  0 <= i, j < p;  columns p .. ld_plane-1 zero.
+ * q, k: f32 rows [p][d] (row strides ld_q, ld_k in floats: multiples of 4, 16-byte aligned bases), the layout a 1x1
+ * convolution with VFML_FMT_F32 output writes; d = 128 is the only value built; |q|, |k| < 4094 (the operands are split as
+ * f16 halves of 16 x).  plane: [p][ld_plane] f16, the weight plane vfml_conv2d_split takes with w_lo == NULL:
+ * ld_plane % 64 == 0, p <= ld_plane <= 32768, 16-byte aligned.  Two passes over the key tiles on the matrix cores, three
+ * split terms per product in both: pass 1 leaves every row's maximum and sum in `workspace`
+ * (vfml_attention_plane_workspace_bytes(p) = 2 p floats), pass 2 forms the scores again and stores the probabilities - the
+ * p x p scores never reach memory.  prob_scale in [1, 2^15].  Stream-ordered, no host synchronisation (capturable); a bad
+ * argument returns non-zero with vfml_last_error set and launches nothing. */
+int64_t vfml_attention_plane_workspace_bytes(int p);
+int vfml_attention_plane_f16(const float* q, int64_t ld_q, const float* k, int64_t ld_k, int p, int d, float score_scale,
+                             float prob_scale, void* plane, int64_t ld_plane, void* workspace, void* stream);
+
 /* src f32 [rows][c] (row stride ld) -> SPLIT ROWS of its transpose times scale: dst[c][ld_dst] (VFML_FMT_S16, ld_dst =
  * rows rounded up to 32, pad channels zero): the activation operand of out^T = V^T . A^T. */
 int vfml_transpose_to_s16(const float* src, int rows, int c, int ld, float scale, float* dst, int64_t ld_dst, void* stream);

@@ -97,4 +97,7 @@ def get_cfg():
         corr_volume="f32",
         # the update iterations of a field as one replayed HIP graph (None: on unless VFML_GRAPH=0; results identical)
         use_graph=None,
+        # the GMA global-motion aggregator of the update block: set by VideoFlowCore.load_model from
+        # the checkpoint's keys (`update_block.aggregator.gamma`); off for every checkpoint without them
+        gma=False,
     )

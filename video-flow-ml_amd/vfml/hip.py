@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -132,6 +132,10 @@ def lib():
     L.vfml_instnorm_workspace_bytes.argtypes = [c_int, c_int, c_int]
     L.vfml_instnorm_stats.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]
     L.vfml_softmax_rows_f16.argtypes = [c_void_p, c_int64, c_int, c_int64, c_void_p, c_int64, c_float, c_void_p]
+    L.vfml_attention_plane_workspace_bytes.restype = c_int64
+    L.vfml_attention_plane_workspace_bytes.argtypes = [c_int]
+    L.vfml_attention_plane_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_int64,
+                                           c_void_p, c_void_p]
     L.vfml_transpose_to_s16.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]
     L.vfml_add_to_s16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p]
     L.vfml_instnorm_finalize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]
@@ -230,7 +234,7 @@ def lib():
 
 
 EXPORTS = [
-    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
+    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
@@ -544,6 +548,27 @@ def softmax_rows_f16(x, rows, cols, ld_in, weight, x_off=0):
     """weight.scale * row softmax of f32 scores -> the f16 plane of a PlainWeight (rows of weight.kp halves)."""
     _check(lib().vfml_softmax_rows_f16(_ptr(_dev(x), x_off), rows, cols, ld_in, c_void_p(weight.hi.data_ptr()), weight.kp,
                                        weight.scale, _stream()), "vfml_softmax_rows_f16")
+
+
+def attention_plane_workspace_bytes(p):
+    return int(lib().vfml_attention_plane_workspace_bytes(p))
+
+
+def attention_plane(q, k, p, plane, score_scale=None, d=128, ld_q=None, ld_k=None, q_off=0, k_off=0, workspace=None):
+    """plane (a PlainWeight [p][kp]) = plane.scale * softmax_j(score_scale * q_i . k_j) as one f16 each, pad columns zero, from
+    f32 rows q, k [p][d] (float offsets q_off / k_off, row strides ld_q / ld_k) in one call (vfml_attention_plane_f16: the
+    scores never reach memory).  score_scale: 1 / sqrt(d) unless given.  workspace: a float32 device tensor of at least 2 p
+    elements (None: taken from torch's allocator for this call - stream-ordered)."""
+    if not isinstance(plane, PlainWeight):
+        raise ValueError("attention_plane: plane must be a PlainWeight")
+    if workspace is None:
+        workspace = torch.empty(max(1, attention_plane_workspace_bytes(p) // 4), dtype=torch.float32, device=plane.hi.device)
+    if workspace.dtype != torch.float32 or workspace.numel() * 4 < attention_plane_workspace_bytes(p) or plane.rows < p:
+        raise ValueError("attention_plane: workspace of 2 p floats and a plane of at least p rows")
+    _check(lib().vfml_attention_plane_f16(_ptr(_dev(q), q_off), ld_q or d, _ptr(_dev(k), k_off), ld_k or d, p, d,
+                                          float(score_scale if score_scale is not None else 1.0 / d ** 0.5), plane.scale,
+                                          c_void_p(plane.hi.data_ptr()), plane.kp, c_void_p(workspace.data_ptr()), _stream()),
+           "vfml_attention_plane_f16")
 
 
 def transpose_to_s16(src, rows, c, ld, dst, ld_dst, scale=1.0, src_off=0, dst_off=0):

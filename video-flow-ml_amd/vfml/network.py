@@ -27,7 +27,11 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .weights import conv_spec, corr_channel_subset, pack_conv_weight
+from .weights import GMA_NO_BIAS, conv_spec, corr_channel_subset, pack_conv_weight
+
+# GMA attention probabilities are stored times 2^14, as MemFlow's are (memflow_net.ATT_SCALE: an unscaled 1080p row would sit in
+# the f16 subnormals); the read-out divides it out again
+ATT_SCALE = 16384.0
 
 
 def cor_pad(cor, split):
@@ -139,13 +143,21 @@ class MOFNetHIP(_Holder):
         # 'BOFNet': the tri-frame member of the family - the same blocks on the centre triple of the
         # window (previous, current, next), output [B, 2, 2, H, W] = (forward, backward) of the centre frame
         self.tri_frame = getattr(cfg, "network", "MOFNetStack") == "BOFNet"
+        # the GMA global-motion aggregator: per centre frame, attention over its own cells computed
+        # once from the context map; every iteration adds gamma * (attention . to_v(mf)) to the motion features as a fourth
+        # input block `mg` of the GRU
+        self.gma = bool(getattr(cfg, "gma", False))
         self._spec = conv_spec(cfg)
         for name, cout, cin, kh, kw in self._spec:
             leaf = self
             for p in name.split("."):
                 leaf = leaf.child(p)
             leaf.weight = nn.Parameter(torch.zeros(cout, cin, kh, kw), requires_grad=False)
-            leaf.bias = nn.Parameter(torch.zeros(cout), requires_grad=False)
+            if name not in GMA_NO_BIAS:
+                leaf.bias = nn.Parameter(torch.zeros(cout), requires_grad=False)
+        if self.gma:
+            self.child("update_block").child("aggregator").gamma = nn.Parameter(torch.zeros(1), requires_grad=False)
+        self._att_store = None
         self._packed = None
         self._packed_key = None
         self._packed_serial = 0
@@ -222,14 +234,16 @@ class MOFNetHIP(_Holder):
             # update-block convolutions read split-row activations (all but convf1, whose input is the
             # 4-channel f32 flow), and so do the encoders behind their 4-channel stem: those weights go in
             # channel-block K order (include/vfml.h)
-            cb = split and ((name.startswith("update_block.") and (not name.endswith(".convf1") or name in rows7)) or
+            cb = split and (name == "att.to_qk" or (name.startswith("update_block.") and (not name.endswith(".convf1") or name in rows7)) or
                             (name.split(".")[0] in ("fnet", "cnet") and name.count(".") > 1) or
                             name in ("fnet.conv2", "cnet.conv2"))
             if cb:
                 cblock_names.add(name)
                 cb = block_of(name, w.shape[1], w.shape[1], cout)
+            if name in GMA_NO_BIAS:
+                cout_packed[name] = cout
             P[name] = (pack_conv_weight(w, cin_pad=4 if cin == 3 else None, cblock=cb),
-                       leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous())
+                       leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous() if name not in GMA_NO_BIAS else None)
         # GRU gates.  Input channels are [h | inp | motion | temporal]; `inp` (the context map) does not
         # change over the iterations, so its part of every gate convolution (+ bias) is computed once per
         # frame and added in the epilogue ("addend"); the per-iteration convolutions see [h | motion |
@@ -257,7 +271,7 @@ class MOFNetHIP(_Holder):
             # split-f16 planes (hi, lo*2^11) of every [cout][K] matrix, made once per load
             with torch.cuda.device(device):
                 for name, (wflat, b) in list(P.items()):
-                    cout = self._cout_of[name] if name in self._cout_of else cout_packed.get(name, b.numel())
+                    cout = self._cout_of[name] if name in self._cout_of else cout_packed[name] if name in cout_packed else b.numel()
                     sc = hip.SplitWeight.auto_scale(float(wflat.abs().max()))
                     sw = hip.SplitWeight(cout, wflat.numel() // cout, device).fill(wflat, scale=sc)
                     sw.order = (hip.KORDER_CBLOCK64 if name in cb64_names else
@@ -270,8 +284,13 @@ class MOFNetHIP(_Holder):
                     with torch.cuda.device(device):
                         P[f"{enc}.conv1.stem"] = (hip.pack_stem_weight(leaf.weight, device),
                                                   leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous())
-        self._tapsum = bool(cout_packed)
+        self._tapsum = any(n.endswith(".flow_head.conv2") for n in cout_packed)
         self._rows7 = bool(rows7)
+        if self.gma:
+            if not split:
+                raise ValueError("the GMA aggregator is built on the split-f16 kernels: cfg.precision 'f32' cannot run a "
+                                 "checkpoint that has it")
+            self._gamma = float(self._param("update_block.aggregator").gamma.item())   # read once per load: .item() synchronises
         self._packed, self._packed_key = P, key
         self._graphs.clear()              # captured launches hold the old planes' addresses
         self._packed_serial += 1          # new weights: cached encoder outputs are stale
@@ -379,6 +398,7 @@ class MOFNetHIP(_Holder):
         self._feat_cache.clear()
         self._ctx_store = None
         self._it0_store = None
+        self._att_store = None
 
     # ------------------------------------------------------------------ per-frame context parts of the gate convolutions
     # The context part of the four GRU gate convolutions is computed once per frame and ADDED by the gate convolutions of
@@ -423,6 +443,84 @@ class MOFNetHIP(_Holder):
             self._feat_cache.pop(old, None)
         st["owner"][s] = cache_key
         return s
+
+    # ------------------------------------------------------------------ per-frame attention of the GMA aggregator
+    # attn = softmax(q k^T / sqrt(128)) over the cells of ONE centre frame, q | k = att.to_qk(inp): it depends on the frame's
+    # context map alone, so it is built beside the gates' context parts (_frame_context) and kept like them - in a slot of a
+    # ring, named by the frame's context cache entry, reused by every window the frame is a centre of.  Two forms, chosen as
+    # MemFlow's read-out chooses (memflow_net.py): the probabilities times ATT_SCALE as ONE f16 each, the weight plane
+    # (hip.PlainWeight) of a long-K GEMM (2.1 GB per 1080p frame), or - small or odd frames - as split rows.
+    # The read-out GEMMs are fixed launches of the replayed graph and take the plane's ADDRESS, so the window's slots are part
+    # of the graph's key; the ring is therefore short (M + 2: a window's centres, the centre a prefetch adds, one spare) and a
+    # sliding job comes back to the same slots, and graphs, every M + 2 fields.
+    ATT_DIM = 128
+    gma = False                # (class defaults: engines that share this class's plumbing but have no such block)
+    _att_store = None
+
+    @staticmethod
+    def _attention_geometry(Pn):
+        """(row length of the probabilities in whole 8-cell units, their row stride, plain-f16 form?)"""
+        P8 = (Pn + 7) // 8 * 8
+        ldA = (P8 + 63) // 64 * 64
+        plain = Pn >= 1024 and Pn % 4 == 0 and Pn * ldA * 2 <= 0x7ffffff0 and ldA <= 32768
+        return P8, ldA, plain
+
+    def _attention_store(self, dev, Pn, M):
+        st = self._att_store
+        if st is None or st["key"] != (str(dev), Pn) or st["R"] < M + 2:
+            self._join_prefetch()
+            self._graphs.clear()           # captured read-outs hold the old planes' addresses
+            self._att_store = None         # (let the old planes go before the new ones are asked for)
+            P8, ldA, plain = self._attention_geometry(Pn)
+            R = M + 2
+            st = self._att_store = {
+                "key": (str(dev), Pn), "R": R, "next": 0, "owner": [None] * R, "live": set(), "plain": plain,
+                "P8": P8, "ldA": ldA, "serial": getattr(self, "_att_serial", 0) + 1,
+                "k": None if plain else hip.SplitWeight(Pn, self.ATT_DIM, dev),
+                "vt": None if plain else hip.SplitWeight(self.ATT_DIM, P8, dev),
+                "A": [hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE) if plain else torch.empty(Pn * ldA, device=dev)
+                      for _ in range(R)]}
+            self._att_serial = st["serial"]
+        return st
+
+    def _attention_slot(self, st, cache_key, busy):
+        """The next slot of the plane ring (not one of `busy`); whoever owned it loses its context cache entry."""
+        busy = set(busy) | st["live"]
+        for _ in range(st["R"]):
+            s = st["next"]
+            st["next"] = (s + 1) % st["R"]
+            if s not in busy:
+                break
+        else:
+            raise RuntimeError("attention store: every slot is in use by the current window")
+        old = st["owner"][s]
+        if old is not None and old != cache_key:
+            self._feat_cache.pop(old, None)
+        st["owner"][s] = cache_key
+        return s
+
+    def _build_attention(self, st, slot, cx, h8, w8, Pn, P, dev, AF):
+        """The attention of one frame (context map cx, [Pn][256] rows) into slot `slot` of the store."""
+        AD, ldA = self.ATT_DIM, st["ldA"]
+        wgt, _ = P["att.to_qk"]
+        nmq = self._nm("att.to_qk")
+        if st["plain"]:
+            # q | k as f32 rows of one map, then the plane in one call: scores and softmax on chip (csrc/attention.hip)
+            qk = self._buf("att_qk", Pn * 2 * AD, dev)
+            hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, 2 * AD, 1, 1, qk, 2 * AD, in0_off=128, in_fmt=AF, mfma=nmq)
+            hip.attention_plane(qk, qk, Pn, st["A"][slot], score_scale=1.0 / float(AD) ** 0.5, d=AD, ld_q=2 * AD, ld_k=2 * AD,
+                                k_off=AD, workspace=self._buf("att_stats", 2 * Pn, dev))
+            return
+        # small or odd frames: q (rows 0..127 of to_qk) as the score GEMM's split-row operand, k (rows 128..255) as f32 for its
+        # weight planes, f32 scores, row softmax to split rows - MemFlow's path
+        qmap = self._buf("att_q", Pn * AD, dev)
+        kmap = self._buf("att_k", Pn * AD, dev)
+        hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, AD, 1, 1, qmap, AD, in0_off=128, in_fmt=AF, out_fmt=AF, mfma=nmq)
+        hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, AD, 1, 1, kmap, AD, in0_off=128, weight_off=AD, in_fmt=AF, mfma=nmq)
+        kw_ = st["k"].fill(kmap, scale=16.0)
+        scores = self._buf("att_scores", Pn * ldA, dev)
+        hip.conv2d(qmap, AD, AD, 1, 1, Pn, kw_, None, Pn, 1, 1, scores, ldA, out_scale=1.0 / float(AD) ** 0.5, in_fmt=AF)
+        hip.softmax_rows_s16(scores, Pn, Pn, ldA, st["A"][slot], ldA, scale=ATT_SCALE)
 
     # ------------------------------------------------------------------ per-frame motion features of iteration 0
     # At iteration 0 the flow is zero and the lookups, convc1, convc2, the flow half and encoder.conv act on every centre
@@ -766,6 +864,14 @@ class MOFNetHIP(_Holder):
         for c in range(1, N - 1):
             for d, tgt in (("f", c + 1), ("b", c - 1)):
                 pk = ("p", keys[c], keys[tgt]) if keys is not None else None
+                if pk is not None and self.gma and d == "b" and keys[c] == keys[tgt]:
+                    # a frame against ITSELF (a window clamped at an end of the clip repeats a frame): the backward problem's
+                    # level 0 adds its cross terms in the order of a transposed forward volume (VFML_CONV_SWAP_CROSS below),
+                    # the forward problem's in the direct order - <a_i, a_j> then differs from itself in the last bit, so the
+                    # two directions must not share one entry.  Without this a keyed window's backward lookups read the
+                    # forward volume and the field is a few 1e-6 px from the same window run unkeyed.
+                    # GMA checkpoints only: every other checkpoint keeps the entries, and the bits, it had.
+                    pk += ("b",)
                 pyr = self._cache_get("p", pk) if pk is not None else None
                 if pyr is None:
                     if pk is None:    # uncached call: reuse one workspace set per problem slot
@@ -860,12 +966,14 @@ class MOFNetHIP(_Holder):
 
     def _frame_context(self, src, sel, keys, H, W, P, dev, Pn, M=1):
         """Context maps (tanh | relu halves, [Pn*256] f32) of frames `sel`, and the context part of their gate convolutions:
-        out[j] = (map, {gate: view of the frame's slot in the gate's store}, slot)."""
+        out[j] = (map, {gate: view of the frame's slot in the gate's store}, slot, store serial); with the GMA aggregator
+        the slot of the frame's attention in its store and that store's serial follow."""
         out, todo = {}, []
         st = self._context_store(dev, Pn, max(M, len(sel)))
+        att = self._attention_store(dev, Pn, max(M, len(sel))) if self.gma else None
         for j in sel:
             ent = self._cache_get("c", keys[j]) if keys is not None else None
-            if ent is not None and ent[3] == st["serial"]:
+            if ent is not None and ent[3] == st["serial"] and (att is None or ent[5] == att["serial"]):
                 out[j] = ent
             else:
                 todo.append(j)
@@ -895,7 +1003,13 @@ class MOFNetHIP(_Holder):
                         add[g + k] = S[slot * Pn * co:(slot + 1) * Pn * co]
                         if slot < Mst - 1:          # the ring's first slots again behind it: a window that wraps stays consecutive
                             S[(R + slot) * Pn * co:(R + slot + 1) * Pn * co].copy_(add[g + k])
-                out[j] = (cx, add, slot, st["serial"])
+                ent = (cx, add, slot, st["serial"])
+                if att is not None:
+                    aslot = self._attention_slot(att, ("c", keys[j]) if keys is not None else None,
+                                                 {e[4] for e in out.values()})
+                    self._build_attention(att, aslot, cx, h8, w8, Pn, P, dev, AF)
+                    ent += (aslot, att["serial"])
+                out[j] = ent
                 if keys is not None:
                     self._cache_put("c", keys[j], out[j])
         return out
@@ -919,6 +1033,9 @@ class MOFNetHIP(_Holder):
         self._join_prefetch()      # a prefetch shares the encoders' workspaces and fills the caches read below
         M = N - 2
         Pn = h * w          # cells per map
+        if self.gma and Pn > 32768:
+            raise ValueError(f"frame {H}x{W}: the GMA aggregator attends over all {Pn} cells of a frame and is built for at "
+                             f"most 32768; process larger frames in tiles (--tile)")
         MP = M * Pn
         P = self._pack(dev)
         win = (2 * R + 1) ** 2
@@ -942,9 +1059,26 @@ class MOFNetHIP(_Holder):
             # Recurrent state, one row of GLD floats per cell:  [ z | r*h | h | inp | mf | mt ]
             # (one allocation, so that cat([r*h, x]) and cat([h, x]) are channel slices of it)
             GLD, Z, RH, HH, INP, MF, MT = 768, 0, 128, 256, 384, 512, 640
+            XC = 256            # what the gates read behind h: [mf | mt]
+            if self.gma:        # ... | mg ]: the aggregated motion features, a fourth block of the gates' input
+                GLD, MG, XC = 896, 768, 384
+                if self._att_store is not None:
+                    self._att_store["live"] = set()     # (the last window's read-outs are ahead of this one on the stream)
             G = self._buf("gru_state", MP * GLD, dev)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
+            att_slots = ()
+            if self.gma:
+                att = self._att_store
+                att_slots = tuple(ctx[c][4] for c in range(1, N - 1))
+                att["live"] = set(att_slots)
+                AD, ldA = self.ATT_DIM, att["ldA"]
+                val = self._buf("att_v", MP * AD, dev)
+                if att["plain"]:
+                    vrows = self._buf("att_vt", AD * ldA, dev)            # V^T as split rows [AD][ldA]
+                    ro = self._buf("att_ro", AD * ldA, dev)               # the GEMM's primary output [AD][ldA] (unused)
+                    ro_t = self._buf("att_ro_t", Pn * AD, dev)            # its transpose: attn . v, [Pn][AD]
+                    ro_ws = self._buf("att_ro_ws", AD * ldA + Pn * AD, dev)   # second half of the K axis (vfml.h ksplit_ws)
             # h = tanh half of the context map (the relu half reaches the gates as their addends), and the `mf` columns of the
             # centres whose iteration 0 an earlier window ran: one launch inside the body (vfml_window_seed), told what to copy
             # by three device cells per centre.  The store applies where iteration 0 covers every centre of a keyed window.
@@ -1101,6 +1235,26 @@ class MOFNetHIP(_Holder):
                         # h of every centre from its context map; mf rows (with the zero flow in channels 124..127) out of the
                         # older centres' slots and into the new ones
                         hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
+                    if self.gma:
+                        # mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention (the read-out GEMM as
+                        # MemFlow runs it: memflow_net.py); on the ng centres whose GRU runs
+                        wgt, _ = P[f"{ub}.aggregator.to_v"]
+                        hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, AD, 1, 1, val, AD, in0_off=MF, in_fmt=AF,
+                                   mfma=mf(f"{ub}.aggregator.to_v"))
+                        for k in range(ng):
+                            a = att["A"][att_slots[k]]
+                            if att["plain"]:
+                                hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
+                                hip.conv2d(vrows, ldA, ldA, AD, 1, 1, a, None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
+                                           in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
+                                hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=self._gamma,
+                                               aux_off=k * Pn * GLD + MF, out_off=k * Pn * GLD + MG)
+                            else:
+                                vt = att["vt"].fill_transposed(val, Pn, ld=AD, scale=16.0, src_off=k * Pn * AD)
+                                hip.conv2d(a, att["P8"], ldA, Pn, 1, 1, vt, None, AD, 1, 1, G, GLD, out_off=k * Pn * GLD + MG,
+                                           out_scale=self._gamma / ATT_SCALE, epilogue=hip.EPI_ADD_AUX, aux0=G, ld_aux0=GLD,
+                                           aux0_off=k * Pn * GLD + MF, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
+                                           mfma=mf(f"{ub}.aggregator.readout"))
                     # temporal stack fusion: 3x1 conv along the frame axis of the motion features
                     wgt, b = P[f"{ub}.tprop"]
                     if self.tri_frame:     # every centre frame is its own problem: its neighbours are the zero padding
@@ -1116,7 +1270,7 @@ class MOFNetHIP(_Holder):
                         wgt, _ = P[f"{ub}.gru.convzr{k}.iter"]
                         # [z | r*h] = gates(conv([h | motion | temporal]) + context part)
                         hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, 256, kh, kw, G, GLD, in0_off=HH, out_off=Z,
-                                   in1=G, c1=256, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
+                                   in1=G, c1=XC, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
                                    epilogue=hip.EPI_GRU_ZR, split=128, aux0=G, ld_aux0=GLD, aux0_off=HH,
                                    addend=gate_add["zr" + k], ld_addend=256, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
                                    addend_off=0 if gate_ind else gate_off["zr" + k],
@@ -1125,7 +1279,7 @@ class MOFNetHIP(_Holder):
                         wgt, _ = P[f"{ub}.gru.convq{k}.iter"]
                         # h = (1 - z) h + z tanh(conv([r*h | motion | temporal]) + context part), in place
                         hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, 128, kh, kw, G, GLD, in0_off=RH, out_off=HH,
-                                   in1=G, c1=256, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
+                                   in1=G, c1=XC, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
                                    epilogue=hip.EPI_GRU_Q, aux0=G, ld_aux0=GLD, aux0_off=Z,
                                    aux1=G, ld_aux1=GLD, aux1_off=HH, addend=gate_add["q" + k], ld_addend=128,
                                    addend_off=0 if gate_ind else gate_off["q" + k],
@@ -1179,7 +1333,7 @@ class MOFNetHIP(_Holder):
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), vol16,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), warm)
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), warm, att_slots)
             self._pre_body = torch.cuda.Event()
             self._pre_body.record(torch.cuda.current_stream(dev))      # (what a prefetch of the next window waits for)
             try:

@@ -58,7 +58,8 @@ def conv_spec(cfg):
         (f"{ub}.encoder.conv", 128 - 4, 192 + 64, 3, 3),
         (f"{ub}.tprop", 128, 3 * 128, 1, 1),
     ]
-    gin = hid + 3 * 128
+    gma = bool(getattr(cfg, "gma", False))
+    gin = hid + (4 if gma else 3) * 128      # GMA: [inp | mf | mt | mg], the aggregated motion features last
     for nm, kh, kw in (("z1", 1, 5), ("r1", 1, 5), ("q1", 1, 5), ("z2", 5, 1), ("r2", 5, 1), ("q2", 5, 1)):
         s.append((f"{ub}.gru.conv{nm}", hid, gin, kh, kw))
     s += [
@@ -67,7 +68,16 @@ def conv_spec(cfg):
         (f"{ub}.mask.0", 256, hid, 3, 3),
         (f"{ub}.mask.2", 2 * 64 * 9, 256, 1, 1),
     ]
+    if gma:
+        s += [(n, co, ci, 1, 1) for n, (co, ci) in GMA_NO_BIAS.items()]
     return s
+
+
+# The two 1x1 convolutions of the GMA aggregator (cfg.gma), neither with a bias: `att.to_qk` maps the
+# context half `inp` onto q | k (one head, d = 128), `aggregator.to_v` the motion features onto the values.
+GMA_NO_BIAS = {"att.to_qk": (256, 128), "update_block.aggregator.to_v": (128, 128)}
+GMA_GAMMA = "update_block.aggregator.gamma"
+GMA_SEEDED_GAMMA = 0.5      # upstream initialises 0, which would switch the block off (seeded_memflow_state_dict chooses alike)
 
 
 def seeded_state_dict(cfg, seed=0):
@@ -78,7 +88,10 @@ def seeded_state_dict(cfg, seed=0):
     for name, cout, cin, kh, kw in conv_spec(cfg):
         bound = 1.0 / math.sqrt(cin * kh * kw)
         sd[f"{name}.weight"] = (torch.rand(cout, cin, kh, kw, generator=g) * 2 - 1) * bound
-        sd[f"{name}.bias"] = (torch.rand(cout, generator=g) * 2 - 1) * bound
+        if name not in GMA_NO_BIAS:
+            sd[f"{name}.bias"] = (torch.rand(cout, generator=g) * 2 - 1) * bound
+    if getattr(cfg, "gma", False):
+        sd[GMA_GAMMA] = torch.tensor([GMA_SEEDED_GAMMA])
     return sd
 
 
@@ -86,7 +99,9 @@ def load_checked(model, state, what):
     """Strict `load_state_dict` (reference processing/videoflow_core.py:110) with an error that names what does not
     fit: the engine hard-codes the RAFT BasicEncoder key layout (`fnet.conv1`, `fnet.layer1.0.conv1`, ...), while the
     released MOF / BOF configurations select Twins-SVT encoders (`fnet.svt.*`) - such a checkpoint
-    is refused with its unexpected key FAMILIES listed instead of hundreds of raw keys.  Numerical parity with the
+    is refused with its unexpected key FAMILIES listed instead of hundreds of raw keys.  The GMA aggregator's keys
+    (`att.to_qk`, `update_block.aggregator.*`) belong to the network when cfg.gma is set, which VideoFlowCore.load_model
+    does from the checkpoint: they are named as unexpected only for a network built without it.  Numerical parity with the
     published checkpoints is unverified: they are not available here (.MISSING_LARGE_BLOBS)."""
     want = set(model.state_dict().keys())
     have = set(state.keys())
@@ -100,9 +115,10 @@ def load_checked(model, state, what):
             return ", ".join(f"{f} ({n})" for f, n in sorted(fam.items())) or "none"
         raise RuntimeError(
             f"{what}: checkpoint does not match the network this engine builds (CNN BasicEncoder fnet/cnet, "
-            f"SepConvGRU update block).  Unexpected key families: {families(have - want)}.  Missing key families: "
+            f"SepConvGRU update block{', GMA aggregator' if GMA_GAMMA in want else ''}).  Unexpected key families: {families(have - want)}.  Missing key families: "
             f"{families(want - have)}.  Checkpoints of the upstream Twins-SVT configurations (fnet.svt.* / cnet.svt.*) "
-            f"are not supported.")
+            f"and of the SK update blocks are not supported; the GMA aggregator (att.to_qk, update_block.aggregator.*) is, "
+            f"through cfg.gma.")
     bad = [f"{k}: checkpoint {tuple(state[k].shape)} vs network {tuple(v.shape)}"
            for k, v in model.state_dict().items() if tuple(state[k].shape) != tuple(v.shape)]
     if bad:
