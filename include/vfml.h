@@ -31,7 +31,8 @@ extern "C" {
  * entry points (encoder and decoder): additions only, every earlier entry point keeps its signature and its results, so
  * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
  * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
- * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well. */
+ * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well; and likewise
+ * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows. */
 #define VFML_ABI_VERSION 26
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -227,6 +228,27 @@ int vfml_attention_plane_f16(const float* q, int64_t ld_q, const float* k, int64
 /* src f32 [rows][c] (row stride ld) -> SPLIT ROWS of its transpose times scale: dst[c][ld_dst] (VFML_FMT_S16, ld_dst =
  * rows rounded up to 32, pad channels zero): the activation operand of out^T = V^T . A^T. */
 int vfml_transpose_to_s16(const float* src, int rows, int c, int ld, float scale, float* dst, int64_t ld_dst, void* stream);
+
+/* Depthwise k x k convolution over NHWC rows, bias, optional residual and optional GELU fused (csrc/dwconv.hip; SURVEY.md
+ * K6 for the SK update block of MOF / BOF):
+ *   out[p][ch] = act(res ? x[p][ch] + conv : conv),  conv = bias[ch] + sum_{ky,kx} weight[ch][ky][kx] * x(p; ky - k/2, kx - k/2)[ch]
+ * a cross-correlation, as nn.Conv2d(groups = c) is, with zero padding at the edges of each of the n frames (which are
+ * independent).  x: [n][h][w] rows of ld_x floats, out: rows of ld_out floats - the pointers already at the first channel, so
+ * a block reads its input in place from a wider row; in_fmt / out_fmt: VFML_FMT_F32 (c, ld multiples of 4, 16-byte aligned)
+ * or VFML_FMT_S16 (c, ld multiples of 8, 32-byte aligned; x = hi + lo on load, hi = RTN f16(y), lo = f16(y - hi) on store).
+ * weight: [c][k][k] f32, bias: [c] f32, both 16-byte aligned; k odd, 1 <= k <= 15 (k = 1: a per-channel scale).  flags:
+ * VFML_DW_RESIDUAL | VFML_DW_GELU; GELU is the exact one, 0.5 v (1 + erf(v / sqrt 2)).  f32 FMAs on the vector ALU, the
+ * operands never rounded to f16.  In place (out == x) is refused: a tile's halo is another tile's output.  Stream-ordered,
+ * no host synchronisation (capturable); a bad argument returns non-zero with vfml_last_error set and launches nothing.
+ * Replaces: cuDNN's grouped convolution + add + GELU of SKFlow's PCBlock. */
+enum { VFML_DW_RESIDUAL = 1, VFML_DW_GELU = 2 };
+int vfml_dwconv2d(const float* x, int64_t ld_x, int n, int h, int w, int c, int k, const float* weight, const float* bias,
+                  float* out, int64_t ld_out, int in_fmt, int out_fmt, int flags, void* stream);
+
+/* out[r][ch] = gelu(x[r][ch]) over [rows][c] in either format (as vfml_dwconv2d's); in place allowed where format and row
+ * stride agree.  The GELU behind a dense 1x1 convolution of a PCBlock. */
+int vfml_gelu_rows(const float* x, int64_t ld_x, float* out, int64_t ld_out, int64_t rows, int c, int in_fmt, int out_fmt,
+                   void* stream);
 
 /* out = aux + scale * x:  x f32 [rows][ldx], aux / out split rows (c % 8 == 0 channels). */
 int vfml_add_to_s16(const float* x, int64_t ldx, const float* aux, int64_t ld_aux, float* out, int64_t ld_out, int64_t rows,

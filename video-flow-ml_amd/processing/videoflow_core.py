@@ -9,7 +9,7 @@ import os
 import torch
 
 from vfml import InputPadder, build_network, get_cfg
-from vfml.weights import GMA_GAMMA, checkpoint_name, load_checked
+from vfml.weights import GMA_GAMMA, SK_KEY, checkpoint_name, load_checked
 
 
 def _is_gpu_name(dev: str) -> bool:
@@ -72,6 +72,8 @@ class VideoFlowCore:
             state = {k.replace('module.', ''): v for k, v in state.items()}
         # the checkpoint decides whether the update block has the GMA aggregator (vfml/cfg.py `gma`)
         cfg.gma = GMA_GAMMA in state
+        # ... and whether it is the SK update block (vfml/cfg.py `sk`)
+        cfg.sk = SK_KEY in state
         model = build_network(cfg)
         load_checked(model, state, model_path)
         model.to(self.device)

@@ -100,4 +100,9 @@ def get_cfg():
         # the GMA global-motion aggregator of the update block: set by VideoFlowCore.load_model from
         # the checkpoint's keys (`update_block.aggregator.gamma`); off for every checkpoint without them
         gma=False,
+        # the SK ("super kernel") update block of SKFlow: PCBlocks with depthwise 15 x 15 / 7 x 7
+        # convolutions and GELU in place of the motion encoder's convolutions, the SepConvGRU and the flow head.  Set by
+        # VideoFlowCore.load_model from the checkpoint's keys (`update_block.encoder.convc1.conv_list.0.weight`); needs the
+        # base lookup (corr_levels, corr_radius) = (4, 4) and a split-f16 precision; off for every other checkpoint
+        sk=False,
     )

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -136,6 +136,9 @@ def lib():
     L.vfml_attention_plane_workspace_bytes.argtypes = [c_int]
     L.vfml_attention_plane_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_int64,
                                            c_void_p, c_void_p]
+    L.vfml_dwconv2d.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                c_int, c_void_p]
+    L.vfml_gelu_rows.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]
     L.vfml_transpose_to_s16.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]
     L.vfml_add_to_s16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p]
     L.vfml_instnorm_finalize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]
@@ -234,7 +237,7 @@ def lib():
 
 
 EXPORTS = [
-    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_transpose_to_s16", "vfml_add_to_s16",
+    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
@@ -569,6 +572,25 @@ def attention_plane(q, k, p, plane, score_scale=None, d=128, ld_q=None, ld_k=Non
                                           float(score_scale if score_scale is not None else 1.0 / d ** 0.5), plane.scale,
                                           c_void_p(plane.hi.data_ptr()), plane.kp, c_void_p(workspace.data_ptr()), _stream()),
            "vfml_attention_plane_f16")
+
+
+DW_RESIDUAL, DW_GELU = 1, 2      # flags of vfml_dwconv2d (include/vfml.h)
+
+
+def dwconv2d(x, ld_x, n, h, w, c, k, weight, bias, out, ld_out, x_off=0, out_off=0, in_fmt=FMT_F32, out_fmt=FMT_F32,
+             residual=False, gelu=False):
+    """out = act(x + conv | conv): depthwise k x k convolution (weight [c][k][k] f32, bias [c]) over [n][h][w] rows of ld_x
+    floats read at float offset x_off, written to rows of ld_out floats at out_off; residual and exact GELU fused
+    (vfml_dwconv2d: f32 FMAs on the vector ALU, zero padding, frames independent)."""
+    _check(lib().vfml_dwconv2d(_ptr(_dev(x), x_off), ld_x, n, h, w, c, k, _ptr(_dev(weight)), _ptr(_dev(bias)),
+                               _ptr(_dev(out), out_off), ld_out, in_fmt, out_fmt,
+                               (DW_RESIDUAL if residual else 0) | (DW_GELU if gelu else 0), _stream()), "vfml_dwconv2d")
+
+
+def gelu_rows(x, ld_x, out, ld_out, rows, c, x_off=0, out_off=0, in_fmt=FMT_F32, out_fmt=FMT_F32):
+    """out[r][:c] = gelu(x[r][:c]) (exact), rows of ld_x / ld_out floats in either format; in place allowed."""
+    _check(lib().vfml_gelu_rows(_ptr(_dev(x), x_off), ld_x, _ptr(_dev(out), out_off), ld_out, rows, c, in_fmt, out_fmt,
+                                _stream()), "vfml_gelu_rows")
 
 
 def transpose_to_s16(src, rows, c, ld, dst, ld_dst, scale=1.0, src_off=0, dst_off=0):

@@ -27,7 +27,8 @@ import torch
 import torch.nn as nn
 
 from . import hip
-from .weights import GMA_NO_BIAS, conv_spec, corr_channel_subset, pack_conv_weight
+from .weights import (BASE_CORR_LEVELS, BASE_CORR_RADIUS, GMA_NO_BIAS, conv_spec, corr_channel_subset, is_depthwise, pack_conv_weight,
+                      pcblock_hidden, sk_blocks)
 
 # GMA attention probabilities are stored times 2^14, as MemFlow's are (memflow_net.ATT_SCALE: an unscaled 1080p row would sit in
 # the f16 subnormals); the read-out divides it out again
@@ -147,6 +148,16 @@ class MOFNetHIP(_Holder):
         # once from the context map; every iteration adds gamma * (attention . to_v(mf)) to the motion features as a fourth
         # input block `mg` of the GRU
         self.gma = bool(getattr(cfg, "gma", False))
+        # the SK update block: PCBlocks - dense 1x1 pairs, depthwise 15 x 15 / 7 x 7 convolutions,
+        # residuals and GELU - in place of the motion encoder's convolutions, the SepConvGRU and the flow head
+        self.sk = bool(getattr(cfg, "sk", False))
+        self._sk_blocks = {}
+        if self.sk:
+            if (cfg.corr_levels, cfg.corr_radius) != (BASE_CORR_LEVELS, BASE_CORR_RADIUS):
+                raise ValueError(f"the SK update block needs the base lookup (corr_levels, corr_radius) = ({BASE_CORR_LEVELS}, "
+                                 f"{BASE_CORR_RADIUS}), got ({cfg.corr_levels}, {cfg.corr_radius}): --fast takes a channel subset of "
+                                 f"convc1's input, and a channel subset of a residual block is not defined")
+            self._sk_blocks = {n: (ci, co, k) for n, ci, co, k in sk_blocks(cfg)}
         self._spec = conv_spec(cfg)
         for name, cout, cin, kh, kw in self._spec:
             leaf = self
@@ -184,6 +195,9 @@ class MOFNetHIP(_Holder):
     def _pack(self, device):
         """Repack every conv weight into the kernels' [cout][kh][kw][cin] order (once per load)."""
         split = self._split()
+        if self.sk and not split:
+            raise ValueError("the SK update block is built on the split-f16 kernels: cfg.precision 'f32' cannot run a "
+                             "checkpoint that has it")
         key = (str(device), split, self._plan_key(), tuple(p._version for p in self.parameters()),
                tuple(p.data_ptr() for p in self.parameters()))
         if self._packed is not None and self._packed_key == key:
@@ -201,7 +215,10 @@ class MOFNetHIP(_Holder):
                 cb64_names.add(layer)
                 return 64
             return True
+        sk_names = self._pack_sk(P, device, block_of, cblock_names, cout_packed) if self.sk else ()
         for name, cout, cin, kh, kw in self._spec:
+            if name in sk_names:
+                continue
             leaf = self._param(name)
             w = leaf.weight.detach().to(device=device, dtype=torch.float32)
             if name.endswith(".encoder.convc1"):
@@ -250,7 +267,7 @@ class MOFNetHIP(_Holder):
         # temporal] only (K 2560 -> 1920).  z and r share their input: one conv with 2*hidden outputs.
         hid = self.hidden_dim
         self._cout_of = {}
-        for k in ("1", "2"):
+        for k in () if self.sk else ("1", "2"):      # (the SK block's `gru` is a PCBlock: no gates)
             self._cout_of[f"update_block.gru.convzr{k}.iter"] = 2 * hid
             self._cout_of[f"update_block.gru.convq{k}.iter"] = hid
             raw = {g: self._param(f"update_block.gru.conv{g}{k}") for g in "zrq"}
@@ -271,6 +288,8 @@ class MOFNetHIP(_Holder):
             # split-f16 planes (hi, lo*2^11) of every [cout][K] matrix, made once per load
             with torch.cuda.device(device):
                 for name, (wflat, b) in list(P.items()):
+                    if is_depthwise(name):      # [c][k][k] f32 with their bias: the vector-ALU kernel's operands, no planes
+                        continue
                     cout = self._cout_of[name] if name in self._cout_of else cout_packed[name] if name in cout_packed else b.numel()
                     sc = hip.SplitWeight.auto_scale(float(wflat.abs().max()))
                     sw = hip.SplitWeight(cout, wflat.numel() // cout, device).fill(wflat, scale=sc)
@@ -296,6 +315,101 @@ class MOFNetHIP(_Holder):
         self._packed_serial += 1          # new weights: cached encoder outputs are stale
         self._feat_cache.clear()
         return P
+
+    sk = False                 # (class defaults: engines that share this class's plumbing but have no such block)
+    _sk_blocks = {}
+
+    def _sk_padded(self, bname):
+        """(positions of a PCBlock's channels in its padded rows, padded width, padded hidden width).  convc1 reads the
+        lookup's rows, each direction's 324 channels in a block of cor_pad's 336; the hidden width (int(1.5 C)) is padded
+        to whole 32-channel K steps of the dense kernel's uniform-step loader.  Pad channels carry zero weights and biases:
+        gelu(0 + 0) = 0 keeps them zero through the block."""
+        cin = self._sk_blocks[bname][0]
+        hp = (pcblock_hidden(cin) + 31) // 32 * 32
+        if bname.endswith(".encoder.convc1"):
+            cor = cin // 2
+            cp = cor_pad(cor, True)
+            return torch.cat([torch.arange(cor), cp + torch.arange(cor)]), 2 * cp, hp
+        return torch.arange(cin), cin, hp
+
+    def _pack_sk(self, P, device, block_of, cblock_names, cout_packed):
+        """The PCBlocks' weights into P: depthwise ones as flat [c][k][k] f32 with their bias, the dense 1x1 ones as padded
+        [cout][cin] matrices in the dense kernel's K order (split into planes by _pack).  Returns the names handled."""
+        done = set()
+
+        def grow(t, dim, n, at):
+            shape = list(t.shape)
+            shape[dim] = n
+            out = torch.zeros(shape, device=device)
+            out.index_copy_(dim, at, t)
+            return out
+        for bname, (cin, cout, ks) in self._sk_blocks.items():
+            pos, cp, hp = self._sk_padded(bname)
+            pos = pos.to(device)
+            hpos = torch.arange(pcblock_hidden(cin), device=device)
+            opos = torch.arange(cout, device=device)
+
+            def get(sub):
+                leaf = self._param(f"{bname}.{sub}")
+                return (leaf.weight.detach().to(device=device, dtype=torch.float32),
+                        leaf.bias.detach().to(device=device, dtype=torch.float32))
+            for i, k in enumerate(ks):
+                w, b = get(f"conv_list.{i}")
+                P[f"{bname}.conv_list.{i}"] = (grow(w.reshape(cin, k * k), 0, cp, pos).reshape(-1).contiguous(), grow(b, 0, cp, pos))
+                done.add(f"{bname}.conv_list.{i}")
+            for sub, (orow, on), (icol, inn) in (("ffn1.0", (hpos, hp), (pos, cp)), ("ffn1.2", (pos, cp), (hpos, hp)),
+                                                 ("pw", (pos, cp), (pos, cp)), ("ffn2.0", (hpos, hp), (pos, cp)),
+                                                 ("ffn2.2", (opos, cout), (hpos, hp))):
+                name = f"{bname}.{sub}"
+                w, b = get(sub)
+                w = grow(grow(w, 0, on, orow), 1, inn, icol)
+                cblock_names.add(name)
+                cout_packed[name] = on
+                P[name] = (pack_conv_weight(w, cblock=block_of(name, inn, inn, on)), grow(b, 0, on, orow).contiguous())
+                done.add(name)
+        return done
+
+    def _sk_workspace(self, rows, dev):
+        """The three scratch maps a PCBlock's launches pass through, sized for the widest block (allocated with cfg.sk only)."""
+        cp = max(self._sk_padded(b)[1] for b in self._sk_blocks)
+        hp = max(self._sk_padded(b)[2] for b in self._sk_blocks)
+        return (self._buf("sk_a", rows * cp, dev), self._buf("sk_b", rows * cp, dev), self._buf("sk_hid", rows * hp, dev))
+
+    def _pcblock(self, name, P, x, ld_x, x_off, n, h, w, out, ld_out, out_off, ws, out_fmt=hip.FMT_S16, gelu_out=False):
+        """One PCBlock on n frames of h x w cells: split rows x (row stride ld_x, float offset x_off,
+        read in place) -> out (ld_out, out_off; out_fmt).  Twelve launches: the dense 1x1 convolutions on vfml_conv2d_split
+        (the residual of ffn1.2 and pw through VFML_EPI_ADD_AUX), a GELU pass behind four of them, the two depthwise
+        convolutions with residual and GELU fused (vfml_dwconv2d).  ws: _sk_workspace's maps."""
+        cin, cout, ks = self._sk_blocks[name]
+        _, cp, hp = self._sk_padded(name)
+        A, B, Hd = ws
+        S, rows = hip.FMT_S16, n * h * w
+
+        def dense(sub, src, c, ld, off, dst, co, ldo, dst_off=0, aux=None, ld_aux=0, aux_off=0, fmt=S):
+            wgt, b = P[f"{name}.{sub}"]
+            hip.conv2d(src, c, ld, n, h, w, wgt, b, co, 1, 1, dst, ldo, in0_off=off, out_off=dst_off,
+                       epilogue=hip.EPI_ADD_AUX if aux is not None else hip.EPI_NONE, aux0=aux, ld_aux0=ld_aux, aux0_off=aux_off,
+                       in_fmt=S, out_fmt=fmt, aux_fmt=S, mfma=self._nm(f"{name}.{sub}"))
+
+        def gelu(t, ld, c, off=0, fmt=S):
+            hip.gelu_rows(t, ld, t, ld, rows, c, x_off=off, out_off=off, in_fmt=fmt, out_fmt=fmt)
+
+        def depthwise(i, src, dst):
+            wgt, b = P[f"{name}.conv_list.{i}"]
+            hip.dwconv2d(src, cp, n, h, w, cp, ks[i], wgt, b, dst, cp, in_fmt=S, out_fmt=S, residual=True, gelu=True)
+        dense("ffn1.0", x, cp, ld_x, x_off, Hd, hp, hp)
+        gelu(Hd, hp, hp)
+        dense("ffn1.2", Hd, hp, hp, 0, A, cp, cp, aux=x, ld_aux=ld_x, aux_off=x_off)
+        gelu(A, cp, cp)
+        depthwise(0, A, B)
+        depthwise(1, B, A)
+        dense("pw", A, cp, cp, 0, B, cp, cp, aux=A, ld_aux=cp)
+        gelu(B, cp, cp)
+        dense("ffn2.0", B, cp, cp, 0, Hd, hp, hp)
+        gelu(Hd, hp, hp)
+        dense("ffn2.2", Hd, hp, hp, 0, out, cout, ld_out, dst_off=out_off, fmt=out_fmt)
+        if gelu_out:
+            gelu(out, ld_out, cout, off=out_off, fmt=out_fmt)
 
     PRECISIONS = ("f16x3", "f16x2", "f16", "mixed", "f32")
 
@@ -326,7 +440,7 @@ class MOFNetHIP(_Holder):
             plan = self._mixed_plan()
             best, nm = -1, 3
             for prefix, n in plan.items():
-                if layer.startswith(prefix) and len(prefix) > best:
+                if layer.startswith(prefix) and len(prefix) > best and self._plan_applies(layer, prefix):
                     best, nm = len(prefix), (n if isinstance(n, str) else int(n))
             if nm == "2w":
                 nm = 2
@@ -335,6 +449,18 @@ class MOFNetHIP(_Holder):
         if layer == "corr" and nm in (2, "2a"):
             nm = 3       # a volume and its transpose must stay the same numbers: the symmetric forms only
         return nm
+
+    def _plan_applies(self, layer, prefix):
+        """An SK checkpoint's layers carry their parameter names (`update_block.encoder.convc1.ffn1.0`, ...), which the
+        plain block's layer names prefix: an entry measured for the plain `convc1` must not reach the PCBlock of that name.
+        A layer of a PCBlock (and the SK block's 1x1 convf1) takes the "" default or an entry that names it INSIDE its
+        block (longer than the block's name); no plan shipped has one, and no EPE budget is claimed for SK under them."""
+        if not self.sk:
+            return True
+        for b in list(self._sk_blocks) + ["update_block.encoder.convf1"]:
+            if layer == b or layer.startswith(b + "."):
+                return prefix == "" or len(prefix) > len(b)
+        return True
 
     def _mixed_plan(self):
         """cfg.mfma_plan, or - as vfml/cfg.py says - DEFAULT_MIXED_PLAN when precision is 'mixed' and none is given
@@ -423,7 +549,7 @@ class MOFNetHIP(_Holder):
             st = self._ctx_store = {
                 "key": (str(dev), Pn), "M": M, "R": R, "next": 0, "owner": [None] * R, "live": set(),
                 "serial": getattr(self, "_ctx_serial", 0) + 1,
-                "S": {g: torch.empty((R + 2 * M - 1) * Pn * co, device=dev) for g, co in self.CTX_GATES}}
+                "S": {g: torch.empty((R + 2 * M - 1) * Pn * co, device=dev) for g, co in (() if self.sk else self.CTX_GATES)}}
             self._ctx_serial = st["serial"]
         return st
 
@@ -993,7 +1119,7 @@ class MOFNetHIP(_Holder):
                 slot = self._context_slot(st, ("c", keys[j]) if keys is not None else None, busy)
                 # context part of the GRU gate convolutions (+ bias), per pass: [z|r] (256) and q (128), into the frame's slot
                 add = {}
-                for k, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
+                for k, (kh, kw) in () if self.sk else (("1", (1, 5)), ("2", (5, 1))):      # (the SK block has no gates)
                     for g, co in (("zr", 256), ("q", 128)):
                         wgt, b = P[f"update_block.gru.conv{g}{k}.ctx"]
                         S = st["S"][g + k]
@@ -1064,6 +1190,10 @@ class MOFNetHIP(_Holder):
                 GLD, MG, XC = 896, 768, 384
                 if self._att_store is not None:
                     self._att_store["live"] = set()     # (the last window's read-outs are ahead of this one on the stream)
+            if self.sk:
+                # the SK block's `gru` is a PCBlock over [h | inp | mf | mt (| mg)], read in place: no gate columns, and the
+                # context half `inp` sits in the row (the plain block's gates take it as a per-frame addend)
+                GLD, HH, INP, MF, MT, MG = (640 if self.gma else 512), 0, 128, 256, 384, 512
             G = self._buf("gru_state", MP * GLD, dev)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
@@ -1083,7 +1213,9 @@ class MOFNetHIP(_Holder):
             # centres whose iteration 0 an earlier window ran: one launch inside the body (vfml_window_seed), told what to copy
             # by three device cells per centre.  The store applies where iteration 0 covers every centre of a keyed window.
             it0 = None
-            if (self.iter0_store and keys is not None and self._split() and not self.tri_frame and M >= 2
+            # (not for SK checkpoints: the window set-up copies h | inp as ONE 256-column block, and vfml_window_seed moves a
+            # slot of the same width as the context block - DESIGN.md section 16)
+            if (self.iter0_store and not self.sk and keys is not None and self._split() and not self.tri_frame and M >= 2
                     and cfg.decoder_depth >= 1 and not (pick_only and cfg.decoder_depth + 1 < M)):
                 it0 = self._iter0_store(dev, Pn, M)
                 warm, seeds, it0_new = it0["ring"].plan(keys, tail=(R,))
@@ -1103,17 +1235,17 @@ class MOFNetHIP(_Holder):
             first = slots[0]
             # (the exact-f32 kernel takes the pointer itself - a captured launch needs it fixed: always the gathered copy)
             # (A/B switch: VFML_CTX_GATHER=1 gathers every window, as round 2 did)
-            if (not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or
+            if not self.sk and (not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or
                     not all(s == first + i or (first + i >= RING and s == first + i - RING and s < Mst - 1)
                             for i, s in enumerate(slots))):
                 first = RING + Mst - 1
                 for i, c in enumerate(range(1, N - 1)):
                     for name, co in self.CTX_GATES:
                         st["S"][name][(first + i) * Pn * co:(first + i + 1) * Pn * co].copy_(ctx[c][1][name])
-            gate_add = {name: st["S"][name] for name, _ in self.CTX_GATES}
+            gate_add = {name: st["S"].get(name) for name, _ in self.CTX_GATES}
             gate_off = {name: first * Pn * co for name, co in self.CTX_GATES}
             gate_ind = None
-            if self._split():      # (the exact-f32 kernel takes the pointer itself)
+            if self._split() and not self.sk:      # (the exact-f32 kernel takes the pointer itself)
                 cells = self._buf("gate_add_cells", 8, dev, torch.int64)
                 hip.ptr_table_set(cells, [st["S"][name][gate_off[name]:] for name, _ in self.CTX_GATES])
                 gate_ind = {name: (cells, i) for i, (name, _) in enumerate(self.CTX_GATES)}
@@ -1128,6 +1260,7 @@ class MOFNetHIP(_Holder):
             fh_taps = self._buf("fh_taps", 2 * MP * 36, dev)     # (two partial maps with the fused flow head)
             frows = self._buf("flow_rows7", MP * 32, dev)
             coords1 = self._buf("coords1", MP * 4, dev)
+            sk_ws = self._sk_workspace(MP, dev) if self.sk else None
 
             # ---- the update iterations + mask head + upsampling: a FIXED launch sequence for a given geometry,
             # window length and arithmetic - only the correlation pyramids it looks up differ from field to field,
@@ -1161,6 +1294,63 @@ class MOFNetHIP(_Holder):
                     if branch is None:
                         branch = self._side2[dev] = torch.cuda.Stream(device=dev)
                 fuse = AF == hip.FMT_S16          # the fused flow-head / flow-half launches read split rows
+
+                def gma_readout(ng):
+                    # mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention (the read-out GEMM as
+                    # MemFlow runs it: memflow_net.py); on the ng centres whose GRU runs
+                    wgt, _ = P[f"{ub}.aggregator.to_v"]
+                    hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, AD, 1, 1, val, AD, in0_off=MF, in_fmt=AF,
+                               mfma=mf(f"{ub}.aggregator.to_v"))
+                    for k in range(ng):
+                        a = att["A"][att_slots[k]]
+                        if att["plain"]:
+                            hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
+                            hip.conv2d(vrows, ldA, ldA, AD, 1, 1, a, None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
+                                       in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
+                            hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=self._gamma,
+                                           aux_off=k * Pn * GLD + MF, out_off=k * Pn * GLD + MG)
+                        else:
+                            vt = att["vt"].fill_transposed(val, Pn, ld=AD, scale=16.0, src_off=k * Pn * AD)
+                            hip.conv2d(a, att["P8"], ldA, Pn, 1, 1, vt, None, AD, 1, 1, G, GLD, out_off=k * Pn * GLD + MG,
+                                       out_scale=self._gamma / ATT_SCALE, epilogue=hip.EPI_ADD_AUX, aux0=G, ld_aux0=GLD,
+                                       aux0_off=k * Pn * GLD + MF, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
+                                       mfma=mf(f"{ub}.aggregator.readout"))
+
+                def sk_iteration(ng, nm):
+                    """One iteration of the SK update block: lookup, the five PCBlocks of the motion encoder, the GMA read-out,
+                    the temporal fusion, `gru` and `flow_head`."""
+                    blk = self._pcblock
+                    if bidir:
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF,
+                                        table=tab_fb, nmaps=nm, vol_fmt=VF, vol_tile=TILE, bidir=(2, cor_p, M))
+                    else:
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF,
+                                        table=tab_f, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
+                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 2, 4, corr, cor_p, 2 * cor_p,
+                                        out_fmt=AF, table=tab_b, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
+                    blk(f"{ub}.encoder.convc1", P, corr, 2 * cor_p, 0, nm, h, w, c1, 256, 0, sk_ws, gelu_out=True)
+                    blk(f"{ub}.encoder.convc2", P, c1, 256, 0, nm, h, w, cf, 256, 0, sk_ws)
+                    wgt, b = P[f"{ub}.encoder.convf1"]
+                    hip.conv2d(flow4, 4, 4, nm, h, w, wgt, b, 128, 1, 1, f1, 128, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
+                    blk(f"{ub}.encoder.convf2", P, f1, 128, 0, nm, h, w, cf, 256, 192, sk_ws)
+                    blk(f"{ub}.encoder.conv", P, cf, 256, 0, nm, h, w, G, GLD, MF, sk_ws)
+                    if self.gma:
+                        gma_readout(ng)
+                    wgt, b = P[f"{ub}.tprop"]
+                    if self.tri_frame:
+                        hip.conv2d(G, 128, GLD, M, 1, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
+                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
+                    else:
+                        hip.conv2d(G, 128, GLD, 1, nm, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
+                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
+                    blk(f"{ub}.gru", P, G, GLD, 0, ng, h, w, G, GLD, HH, sk_ws)
+                    blk(f"{ub}.flow_head", P, G, GLD, HH, ng, h, w, delta, 4, 0, sk_ws, out_fmt=hip.FMT_F32)
+                    hip.coords_update(coords1, delta, ng, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD, flow_b_off=MF + 124,
+                                      fmt_b=AF)
+
+                if self.sk:
+                    # h | inp of every centre from its context map (one 256-column block), before the first iteration
+                    hip.window_seed(seed_cells, M, Pn, 256, G, GLD, HH, MF, 256)
                 for it in range(cfg.decoder_depth):
                     # pick_only: the caller takes flow M (the backward flow of the first centre frame - the reference's
                     # `[0, shape[1]//2]`).  Going back from the last iteration, centre 0's result depends on one centre
@@ -1169,6 +1359,9 @@ class MOFNetHIP(_Holder):
                     left = cfg.decoder_depth - 1 - it
                     ng = min(M, left + 1) if pick_only and not self.tri_frame else M
                     nm = min(M, left + 2) if pick_only and not self.tri_frame else M
+                    if self.sk:
+                        sk_iteration(ng, nm)
+                        continue
                     # The flow half of the motion encoder (flow -> convf1 -> convf2 -> channels 192..255 of `cf`) needs
                     # nothing of the correlation half (lookups -> convc1 -> convc2 -> channels 0..191): on a second stream
                     # its small MFMA-bound convolutions run BESIDE the HBM-bound lookups (a fork / join of two events; inside
@@ -1236,25 +1429,7 @@ class MOFNetHIP(_Holder):
                         # older centres' slots and into the new ones
                         hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
                     if self.gma:
-                        # mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention (the read-out GEMM as
-                        # MemFlow runs it: memflow_net.py); on the ng centres whose GRU runs
-                        wgt, _ = P[f"{ub}.aggregator.to_v"]
-                        hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, AD, 1, 1, val, AD, in0_off=MF, in_fmt=AF,
-                                   mfma=mf(f"{ub}.aggregator.to_v"))
-                        for k in range(ng):
-                            a = att["A"][att_slots[k]]
-                            if att["plain"]:
-                                hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
-                                hip.conv2d(vrows, ldA, ldA, AD, 1, 1, a, None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
-                                           in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
-                                hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=self._gamma,
-                                               aux_off=k * Pn * GLD + MF, out_off=k * Pn * GLD + MG)
-                            else:
-                                vt = att["vt"].fill_transposed(val, Pn, ld=AD, scale=16.0, src_off=k * Pn * AD)
-                                hip.conv2d(a, att["P8"], ldA, Pn, 1, 1, vt, None, AD, 1, 1, G, GLD, out_off=k * Pn * GLD + MG,
-                                           out_scale=self._gamma / ATT_SCALE, epilogue=hip.EPI_ADD_AUX, aux0=G, ld_aux0=GLD,
-                                           aux0_off=k * Pn * GLD + MF, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
-                                           mfma=mf(f"{ub}.aggregator.readout"))
+                        gma_readout(ng)
                     # temporal stack fusion: 3x1 conv along the frame axis of the motion features
                     wgt, b = P[f"{ub}.tprop"]
                     if self.tri_frame:     # every centre frame is its own problem: its neighbours are the zero padding
@@ -1314,7 +1489,7 @@ class MOFNetHIP(_Holder):
                     hip.coords_update(coords1, delta, ng, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD,
                                       flow_b_off=MF + 124, fmt_b=AF)
 
-                if cfg.decoder_depth == 0:       # (no iteration ran the window set-up: h for the mask head)
+                if cfg.decoder_depth == 0 and not self.sk:       # (no iteration ran the window set-up: h for the mask head)
                     hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
                 # mask head on the final hidden state, then K8 for every flow of the output tensor (pick_only: of
                 # the first centre frame, and its backward flow alone)
@@ -1334,6 +1509,8 @@ class MOFNetHIP(_Holder):
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), vol16,
                     self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), warm, att_slots)
+            if self.sk:
+                gkey += ("sk",)
             self._pre_body = torch.cuda.Event()
             self._pre_body.record(torch.cuda.current_stream(dev))      # (what a prefetch of the next window waits for)
             try:

@@ -11,6 +11,7 @@ custom-op boundaries, other PyTorch code):
     vfml::corr_lookup(pyramid, coords, hl, wl, radius)                   -> Tensor     K5 pyramid lookup
     vfml::convex_upsample(flow, mask)                                    -> Tensor     K8 8x convex upsampling
     vfml::text_draw(frame, plan)                                         -> Tensor     text labels on a composed frame
+    vfml::dwconv2d_nhwc(x, weight, bias, residual, act)                  -> Tensor     K6 depthwise k x k (SK update block)
 
 Only the CUDA (= HIP on ROCm) dispatch key has an implementation: on CPU tensors the dispatcher raises
 NotImplementedError - there is no CPU fallback, as everywhere in the engine.  Importing this module registers the ops
@@ -96,6 +97,19 @@ def _text_draw(frame, plan):
     return hip.text_draw(hip.TextPlan(plan.cpu().to(torch.int32).numpy(), frame.device), out, h, w)
 
 
+def _dwconv2d_nhwc(x, weight, bias, residual, act):
+    """x [n,h,w,c] f32 (c % 4 == 0), weight [c,k,k] (k odd, <= 15), bias [c] -> act(x + conv | conv), [n,h,w,c] f32: the
+    depthwise convolution of vfml_dwconv2d with `residual` and exact GELU (`act`) fused."""
+    n, h, w, c = x.shape
+    if weight.dim() != 3 or weight.shape[0] != c or weight.shape[1] != weight.shape[2] or bias.shape != (c,):
+        raise ValueError(f"dwconv2d_nhwc: weight [c,k,k] and bias [c] expected for c = {c}, got {tuple(weight.shape)}, {tuple(bias.shape)}")
+    x = x.contiguous().float()
+    out = torch.empty_like(x)
+    hip.dwconv2d(x.reshape(-1), c, n, h, w, c, int(weight.shape[1]), weight.contiguous().float().reshape(-1),
+                 bias.contiguous().float(), out.reshape(-1), c, residual=bool(residual), gelu=bool(act))
+    return out
+
+
 def register():
     global _LIB
     if _LIB is not None:
@@ -106,11 +120,13 @@ def register():
     lib.define("corr_lookup(Tensor[] pyramid, Tensor coords, int[] hl, int[] wl, int radius) -> Tensor")
     lib.define("convex_upsample(Tensor flow, Tensor mask) -> Tensor")
     lib.define("text_draw(Tensor frame, Tensor plan) -> Tensor")
+    lib.define("dwconv2d_nhwc(Tensor x, Tensor weight, Tensor bias, bool residual, bool act) -> Tensor")
     lib.impl("conv2d_nhwc", _conv2d_nhwc, "CUDA")
     lib.impl("corr_volume", _corr_volume, "CUDA")
     lib.impl("corr_lookup", _corr_lookup, "CUDA")
     lib.impl("convex_upsample", _convex_upsample, "CUDA")
     lib.impl("text_draw", _text_draw, "CUDA")
+    lib.impl("dwconv2d_nhwc", _dwconv2d_nhwc, "CUDA")
     _LIB = lib
     return lib
 

@@ -43,9 +43,60 @@ def corr_channel_subset(levels, radius, base_levels=BASE_CORR_LEVELS, base_radiu
             for l in range(levels) for i in range(2 * radius + 1) for j in range(2 * radius + 1)]
 
 
+# The SK ("super kernel") update block (cfg.sk): its first depthwise weight names the family in a
+# checkpoint.  A depthwise entry of the table is (name, C, 1, k, k) - PyTorch's shape of a grouped convolution's weight.
+SK_KEY = "update_block.encoder.convc1.conv_list.0.weight"
+
+
+def is_depthwise(name):
+    return ".conv_list." in name
+
+
+def pcblock_hidden(cin):
+    return int(1.5 * cin)
+
+
+def _pcblock_spec(name, cin, cout, k):
+    """PCBlock(cin, cout, k) of SKFlow in state-dict order: two depthwise convolutions, the first feed-forward pair, the
+    pointwise convolution, the second feed-forward pair (every convolution biased)."""
+    hid = pcblock_hidden(cin)
+    return [(f"{name}.conv_list.0", cin, 1, k[0], k[0]), (f"{name}.conv_list.1", cin, 1, k[1], k[1]),
+            (f"{name}.ffn1.0", hid, cin, 1, 1), (f"{name}.ffn1.2", cin, hid, 1, 1), (f"{name}.pw", cin, cin, 1, 1),
+            (f"{name}.ffn2.0", hid, cin, 1, 1), (f"{name}.ffn2.2", cout, hid, 1, 1)]
+
+
+def sk_blocks(cfg):
+    """[(name, cin, cout, (k0, k1))] of the seven PCBlocks of the SK update block, in state-dict order."""
+    cor = BASE_CORR_LEVELS * (2 * BASE_CORR_RADIUS + 1) ** 2
+    hid = cfg.feat_dim // 2
+    gin = hid + (4 if getattr(cfg, "gma", False) else 3) * 128
+    ub = "update_block"
+    return [(f"{ub}.encoder.convc1", 2 * cor, 256, (1, 15)), (f"{ub}.encoder.convc2", 256, 192, (1, 15)),
+            (f"{ub}.encoder.convf2", 128, 64, (1, 15)), (f"{ub}.encoder.conv", 192 + 64, 128 - 4, (1, 15)),
+            (f"{ub}.gru", gin, hid, (1, 7)), (f"{ub}.flow_head", hid, 4, (1, 15))]
+
+
+def _sk_spec(cfg):
+    hid = cfg.feat_dim // 2
+    ub = "update_block"
+    blocks = {n: _pcblock_spec(n, ci, co, k) for n, ci, co, k in sk_blocks(cfg)}
+    s = _encoder_spec("fnet", cfg.feat_dim) + _encoder_spec("cnet", cfg.feat_dim)
+    s += blocks[f"{ub}.encoder.convc1"] + blocks[f"{ub}.encoder.convc2"]
+    s += [(f"{ub}.encoder.convf1", 128, 4, 1, 1)]
+    s += blocks[f"{ub}.encoder.convf2"] + blocks[f"{ub}.encoder.conv"]
+    s += [(f"{ub}.tprop", 128, 3 * 128, 1, 1)]
+    s += blocks[f"{ub}.gru"] + blocks[f"{ub}.flow_head"]
+    s += [(f"{ub}.mask.0", 256, hid, 3, 3), (f"{ub}.mask.2", 2 * 64 * 9, 256, 1, 1)]
+    if getattr(cfg, "gma", False):
+        s += [(n, co, ci, 1, 1) for n, (co, ci) in GMA_NO_BIAS.items()]
+    return s
+
+
 def conv_spec(cfg):
     """[(name, cout, cin, kh, kw)] for every convolution, in state-dict order (checkpoint shapes: the
-    correlation input is always the base 4-level radius-4 lookup)."""
+    correlation input is always the base 4-level radius-4 lookup).  cfg.sk: the SK update block's table (_sk_spec)."""
+    if getattr(cfg, "sk", False):
+        return _sk_spec(cfg)
     cor = BASE_CORR_LEVELS * (2 * BASE_CORR_RADIUS + 1) ** 2
     hid = cfg.feat_dim // 2
     s = _encoder_spec("fnet", cfg.feat_dim) + _encoder_spec("cnet", cfg.feat_dim)
@@ -82,7 +133,8 @@ GMA_SEEDED_GAMMA = 0.5      # upstream initialises 0, which would switch the blo
 
 def seeded_state_dict(cfg, seed=0):
     """PyTorch's default Conv2d initialisation (uniform +-1/sqrt(fan_in) for weight and bias),
-    drawn layer by layer from one seeded generator, so the values depend only on (cfg, seed)."""
+    drawn layer by layer from one seeded generator, so the values depend only on (cfg, seed).  (A depthwise entry's fan-in
+    is k * k: its bound is 1 / k, PyTorch's default for a grouped convolution.)"""
     g = torch.Generator().manual_seed(seed)
     sd = {}
     for name, cout, cin, kh, kw in conv_spec(cfg):
@@ -101,7 +153,8 @@ def load_checked(model, state, what):
     released MOF / BOF configurations select Twins-SVT encoders (`fnet.svt.*`) - such a checkpoint
     is refused with its unexpected key FAMILIES listed instead of hundreds of raw keys.  The GMA aggregator's keys
     (`att.to_qk`, `update_block.aggregator.*`) belong to the network when cfg.gma is set, which VideoFlowCore.load_model
-    does from the checkpoint: they are named as unexpected only for a network built without it.  Numerical parity with the
+    does from the checkpoint: they are named as unexpected only for a network built without it; the SK update block's
+    keys (`update_block.*.conv_list.*`, `.ffn1.*`, `.pw`, `.ffn2.*`) likewise with cfg.sk.  Numerical parity with the
     published checkpoints is unverified: they are not available here (.MISSING_LARGE_BLOBS)."""
     want = set(model.state_dict().keys())
     have = set(state.keys())
@@ -115,10 +168,10 @@ def load_checked(model, state, what):
             return ", ".join(f"{f} ({n})" for f, n in sorted(fam.items())) or "none"
         raise RuntimeError(
             f"{what}: checkpoint does not match the network this engine builds (CNN BasicEncoder fnet/cnet, "
-            f"SepConvGRU update block{', GMA aggregator' if GMA_GAMMA in want else ''}).  Unexpected key families: {families(have - want)}.  Missing key families: "
+            f"{'SK' if SK_KEY in want else 'SepConvGRU'} update block{', GMA aggregator' if GMA_GAMMA in want else ''}).  Unexpected key families: {families(have - want)}.  Missing key families: "
             f"{families(want - have)}.  Checkpoints of the upstream Twins-SVT configurations (fnet.svt.* / cnet.svt.*) "
-            f"and of the SK update blocks are not supported; the GMA aggregator (att.to_qk, update_block.aggregator.*) is, "
-            f"through cfg.gma.")
+            f"are the one family that is not supported; the GMA aggregator (att.to_qk, update_block.aggregator.*) is, "
+            f"through cfg.gma, and the SK update block (update_block.*.conv_list.*) is, through cfg.sk.")
     bad = [f"{k}: checkpoint {tuple(state[k].shape)} vs network {tuple(v.shape)}"
            for k, v in model.state_dict().items() if tuple(state[k].shape) != tuple(v.shape)]
     if bad:
