@@ -46,7 +46,14 @@ struct SplitArgs {
   // tile's slice of a second [proj_n][cout] weight (two f16 planes, lo plane proj_lo_off bytes behind the hi plane)
   const char* proj_w; int proj_lo_off, proj_bytes, proj_n, proj_kp; float proj_inv; float* proj_out; int ld_proj;
   const float* const* addend_ind;   // vfml_conv_desc.addend_ind: a device cell holding the addend pointer to use (or null)
+  // resident-A form of the persistent GEMM (SplitPlan::resident; the launch fills the walk): mtiles x ntiles are then
+  // 128 x 64 tiles, a work unit is one row tile x res_cl consecutive column tiles, res_nc units per row tile
+  int resident, res_nc, res_cl;
 };
+// longest K axis the resident-A form holds: a 128-row tile's hi halves are staged whole (four 64-channel steps, 64 KB
+// of LDS) and then kept as fragments, 64 registers per wave
+#define VFML_RESIDENT_KMAX 256
+#define VFML_RESIDENT_LDS (80 * 1024)      // its LDS per workgroup: two per CU
 // conv_gemm_tapx.hip: the kernel that shares one activation stage between the taps of a filter row
 #define VFML_TAPX_KWMAX 5      // widest filter row it is built for
 
@@ -62,6 +69,7 @@ struct SplitPlan {
   bool persist, fastk, cswap, mf16, h16;    // SPLIT_DMA
   int nm;
   bool add_rows;                            // the K split's add_rows launches follow (no part of the kernel's name)
+  bool resident;                            // SPLIT_DMA persistent form: the kernel takes its resident-A walk (no part of the name either)
 };
 // the forced tile shape is VFML_DMA_TILE's "TM,TN,WM,WN" as digits, 0 = none; 0, or 1 with the error set
 int plan_split(const SplitArgs& a, bool in16, int flags, int forced_tile, SplitPlan* plan);
