@@ -32,8 +32,8 @@ extern "C" {
  * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
  * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
  * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well; and likewise
- * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows. */
-#define VFML_ABI_VERSION 26
+ * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows.  27 adds vfml_conv2d_split_variant_at. */
+#define VFML_ABI_VERSION 27
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
 enum {
@@ -155,6 +155,11 @@ int vfml_conv2d(const vfml_conv_desc* d, void* stream);
 int vfml_conv2d_variant(const vfml_conv_desc* d, char* buf, int len);
 int vfml_conv2d_split_variant(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale,
                               int in_fmt, int out_fmt, int aux_fmt, int k_order, char* buf, int len);
+/* The instantiations of the vfml_conv2d_split kernels that exist, one per index from 0: the rows of the register-staged
+ * kernel's table, then the LDS-DMA kernel's, then the shared-stage kernel's, each named as vfml_conv2d_split_variant names
+ * it.  Non-zero (and no error text) past the last row; for the test that holds the tables against the calls that reach
+ * them.  Needs no GPU. */
+int vfml_conv2d_split_variant_at(int index, char* buf, int len);
 
 /* Same contract on the f16 matrix cores with fp32-grade accuracy ("split-f16": x = hi + lo with
  * hi = f16(x), lo = f16(x - hi); a*b ~= ah*bh + ah*bl + al*bh, 3 MFMAs per product, ~22 mantissa

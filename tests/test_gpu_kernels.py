@@ -260,7 +260,9 @@ def test_to_s16_roundtrip(gpu):
 def test_conv2d_split_rows_in_and_out(gpu, cin, cout, kh, kw, stride, cblock):
     """Split-row (S16) activations in, split-row activations out == the f32-in/f32-out result, with
     the weights in tap order and in channel-block order (incl. channel counts that are not multiples
-    of 32 and every tile width of the LDS-DMA kernel)."""
+    of 32).  At 546 pixels the planner picks the LDS-DMA kernel's 128 x 64 tile for every case (128 x 32 for
+    the 4-channel one): one to four column tiles of it, not its wider tiles - those are forced in
+    tests/test_gpu_conv_tiles.py."""
     from vfml import hip
     from vfml.weights import pack_conv_weight
     g = torch.Generator().manual_seed(13)
@@ -512,7 +514,8 @@ def test_conv_leaves_instnorm_partials(gpu, n, cin, cout, k, stride, H, W, src16
     """conv2d(stats_part=...) + instnorm_finalize == conv2d + instnorm_stats on the stored result (the encoder's
     fused path): ragged last row tile, column tiles that end inside a tile, several images with whole tiles each;
     f32 sources (the register-staged kernel, blocks of 128 pixels) and split-row sources (the LDS-DMA kernel: blocks
-    of 32 pixels, every tile shape the dispatcher picks for these sizes)."""
+    of 32 pixels - on the 128 x 64 tile, which is what the dispatcher picks for every one of these sizes, the 270 x 480
+    one included; the larger tiles: tests/test_gpu_conv_tiles.py::test_instnorm_partials_on_forced_tiles)."""
     from vfml import hip
     g = torch.Generator().manual_seed(n * 1000 + cout + k)
     x = torch.randn(n, cin, H, W, generator=g)
@@ -764,11 +767,13 @@ def _f16(t):
 
 @pytest.mark.parametrize("mfma", [2, "2a", 1])
 @pytest.mark.parametrize("cin,cout,kh,kw,stride,src16,cblock", [
-    (64, 192, 3, 3, 1, True, True),       # 128 x 192 / 192 x 128 tiles, uniform-step loader
+    # (748 pixels: the planner's cost model gives every split-row case here the 128 x 64 tile, 128 x 32 up to 32 output
+    # channels - the larger tiles are tests/test_gpu_conv_tiles.py's, forced with VFML_DMA_TILE)
+    (64, 192, 3, 3, 1, True, True),       # three 64-column tiles, uniform-step loader
     (96, 128, 1, 5, 1, True, False),      # tap order: the general loader
-    (72, 100, 3, 3, 2, True, True),       # channel count not a multiple of 32, strided, ragged cout
-    (128, 64, 3, 3, 1, True, True),       # 128 x 64 tiles
-    (256, 4, 3, 3, 1, True, True),        # 128 x 32 tiles (flow head)
+    (72, 100, 3, 3, 2, True, True),       # channel count not a multiple of 32 (general loader), strided, ragged cout
+    (128, 64, 3, 3, 1, True, True),       # one 64-column tile
+    (256, 4, 3, 3, 1, True, True),        # 128 x 32 tiles (flow head), general loader
     (64, 96, 3, 3, 2, False, False),      # f32 sources: the register-staged kernel
     (4, 64, 7, 7, 2, False, False),       # encoder stem
 ])
@@ -797,8 +802,14 @@ def test_conv2d_reduced_mfma_counts_drop_exactly_the_lo_terms(gpu, mfma, cin, co
         hip.to_s16(nhwc(x), n * H * W, cin, cin, src, cin)
     else:
         src = nhwc(x)
-    hip.conv2d(src, cin, cin, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, stride=stride, pad_h=ph, pad_w=pw,
-               in_fmt=hip.FMT_S16 if src16 else hip.FMT_F32, mfma=mfma)
+    call = dict(stride=stride, pad_h=ph, pad_w=pw, in_fmt=hip.FMT_S16 if src16 else hip.FMT_F32, mfma=mfma)
+    hip.conv2d(src, cin, cin, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, **call)
+    if src16:       # the tile and the product the comments above name
+        name = hip.conv2d(src, cin, cin, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, variant_only=True, **call)
+        nm = {2: 2, "2a": 4, 1: 1}[mfma]
+        loader = "true" if cblock and cin % 32 == 0 and cout > 32 else "false"
+        tile = "1, 1, 4, 1" if cout <= 32 else "2, 1, 2, 2"
+        assert name == f"conv_gemm_dma_kernel<{tile}, false, {loader}, false, {nm}, true, false>"
     got = from_nhwc(out, n, ho, wo, cout)
     assert torch.isfinite(got).all()
     assert rel_err(got, emu) < CONV_TOL["f16x3"], rel_err(got, emu)
@@ -836,9 +847,9 @@ def test_gemm_form_reduced_mfma_counts(gpu):
             assert torch.equal(rev.view(S, ldt)[:, :P].cpu(), got.t())
 
 
-@pytest.mark.parametrize("c0,c1,cout,kh,kw,stride", [(128, 0, 192, 3, 3, 1),     # 128 x 192 / 192 x 128 tiles
+@pytest.mark.parametrize("c0,c1,cout,kh,kw,stride", [(128, 0, 192, 3, 3, 1),     # three 64-column tiles (every case here: 128 x 64 tiles)
                                                     (64, 128, 256, 1, 5, 1),    # two sources (the GRU gate shape)
-                                                    (64, 0, 64, 3, 3, 2),       # 128 x 64 tiles, strided
+                                                    (64, 0, 64, 3, 3, 2),       # one 64-column tile, strided
                                                     (256, 0, 136, 1, 1, 1),     # 1x1: any weight order
                                                     (192, 0, 128, 5, 1, 1)])    # three 64-channel blocks, vertical taps
 def test_conv2d_one_mfma_64_channel_steps(gpu, c0, c1, cout, kh, kw, stride):
@@ -866,9 +877,12 @@ def test_conv2d_one_mfma_64_channel_steps(gpu, c0, c1, cout, kh, kw, stride):
     if c1:
         hip.to_s16(xs[:, c0:].contiguous().reshape(-1), P, c1, c1, buf, LD, dst_off=32 + c0)
     out = torch.full((n * ho * wo * cout,), float("nan"), device=gpu)
-    hip.conv2d(buf, c0, LD, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, stride=stride, pad_h=ph, pad_w=pw, in0_off=32,
-               in1=buf if c1 else None, c1=c1, ld1=LD if c1 else 0, in1_off=32 + c0, epilogue=hip.EPI_RELU,
-               in_fmt=hip.FMT_S16, mfma=1)
+    call = dict(stride=stride, pad_h=ph, pad_w=pw, in0_off=32, in1=buf if c1 else None, c1=c1, ld1=LD if c1 else 0,
+                in1_off=32 + c0, epilogue=hip.EPI_RELU, in_fmt=hip.FMT_S16, mfma=1)
+    hip.conv2d(buf, c0, LD, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, **call)
+    # (NM 5 = the 64-channel steps; at 988 pixels on the 128 x 64 tile - the larger ones: tests/test_gpu_conv_tiles.py)
+    assert hip.conv2d(buf, c0, LD, n, H, W, w, b.cuda(), cout, kh, kw, out, cout, variant_only=True, **call) == \
+        "conv_gemm_dma_kernel<2, 1, 2, 2, false, true, false, 5, true, false>"
     got = from_nhwc(out, n, ho, wo, cout)
     assert torch.isfinite(got).all()
     assert rel_err(got, emu) < CONV_TOL["f16x3"], rel_err(got, emu)

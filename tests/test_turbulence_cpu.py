@@ -78,7 +78,7 @@ def test_header_declares_and_library_exports_the_symbols():
     for name in SYMBOLS:
         assert hasattr(lib, name)
     lib.vfml_abi_version.restype = ctypes.c_int
-    assert lib.vfml_abi_version() == 26
+    assert lib.vfml_abi_version() == 27
 
 
 def test_kernel_size_is_rejected_before_any_launch():

@@ -1914,3 +1914,16 @@ extern "C" int vfml_conv2d_split_variant(const vfml_conv_desc* d, const void* w_
   VFML_REQUIRE(vfml_detail::variant_name(row->key, buf, len) < len, "vfml_conv2d_split_variant: the name needs more than %d bytes", len);
   return 0;
 }
+
+
+extern "C" int vfml_conv2d_split_variant_at(int index, char* buf, int len) {
+  VFML_REQUIRE(buf && len > 0, "vfml_conv2d_split_variant_at: no buffer");
+  constexpr int nreg = (int)(sizeof(REG_VARIANTS) / sizeof(REG_VARIANTS[0])), ndma = (int)(sizeof(DMA_VARIANTS) / sizeof(DMA_VARIANTS[0]));
+  if (index < 0) return 1;
+  const SplitVariant* row = index < nreg          ? &REG_VARIANTS[index]
+                            : index < nreg + ndma ? &DMA_VARIANTS[index - nreg]
+                                                  : vfml_detail::tapx_variant_at(index - nreg - ndma);
+  if (!row) return 1;
+  VFML_REQUIRE(vfml_detail::variant_name(row->key, buf, len) < len, "vfml_conv2d_split_variant_at: the name needs more than %d bytes", len);
+  return 0;
+}

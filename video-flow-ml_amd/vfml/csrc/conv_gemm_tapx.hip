@@ -322,3 +322,8 @@ const SplitVariant TAPX_VARIANTS[] = {TAPX_ROWS(3, 2, 2, 2), TAPX_ROWS(2, 3, 2, 
 const SplitVariant* vfml_detail::tapx_variant(const SplitPlan& plan) {
   return find_variant(TAPX_VARIANTS, sizeof(TAPX_VARIANTS) / sizeof(TAPX_VARIANTS[0]), plan);
 }
+
+const SplitVariant* vfml_detail::tapx_variant_at(int index) {
+  const int n = (int)(sizeof(TAPX_VARIANTS) / sizeof(TAPX_VARIANTS[0]));
+  return index >= 0 && index < n ? &TAPX_VARIANTS[index] : nullptr;
+}

@@ -90,6 +90,7 @@ struct SplitVariant {
 const SplitVariant* find_variant(const SplitVariant* rows, size_t n, const SplitPlan& plan);   // null: no such instantiation
 int variant_name(const SplitPlan& key, char* buf, int len);     // the kernel's name as rocprofv3 prints it
 const SplitVariant* tapx_variant(const SplitPlan& plan);        // conv_gemm_tapx.hip's table
+const SplitVariant* tapx_variant_at(int index);                 // its rows in order, null past the last
 }  // namespace vfml_detail
 using vfml_detail::SplitArgs;
 using vfml_detail::SplitPlan;
@@ -186,6 +187,11 @@ __device__ __forceinline__ void epilogue_rows(const SplitArgs& a, const float* s
   // 8 channels (one split-row unit) per thread, as two quads
   constexpr int C8 = BN / 8;
   constexpr int RPP = NT / C8;       // rows per pass
+  // (192- and 96-column tiles: NT is no multiple of C8, and the threads left over would go over rows of thread row 0 a
+  // second time - the same store twice for most epilogues, but a second update of h for a q gate written in place)
+  if constexpr (NT % C8 != 0) {
+    if (t >= RPP * C8) return;
+  }
   const int c8 = t % C8;
   const int gcol = n0 + c8 * 8;
   if (gcol >= a.cout) return;
@@ -311,6 +317,9 @@ __device__ __forceinline__ void epilogue_rows_fast_k(const SplitArgs& a, const f
   constexpr int LDC = BN + 4;
   constexpr int C8 = BN / 8;
   constexpr int RPP = NT / C8;
+  if constexpr (NT % C8 != 0) {      // (as in epilogue_rows: no (row, unit) twice)
+    if (t >= RPP * C8) return;
+  }
   const int c8 = t % C8;
   const int gcol = n0 + c8 * 8;
   if (gcol >= a.cout) return;
