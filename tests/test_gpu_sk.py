@@ -288,7 +288,9 @@ def test_pcblock_through_the_engines_helper(gpu, name, cin, cout):
                                         (3, 136, 152, {"gma": True})], ids=["mof3", "mof5", "bof5", "sk+gma3"])
 def test_sk_forward_matches_oracle(gpu, T, H, W, over):
     """f16x3, depth 4, against the float64 oracle: mean EPE <= 8 N, N = the float32 oracle's own mean EPE against float64 on
-    that input (nothing in the bound comes from the engine), and < EPE_TOL."""
+    that input (nothing in the bound comes from the engine), and < EPE_TOL.  The mean alone: maximum, worst block, outer ring
+    and the 1/8-resolution flows of the same fields, and a field two depthwise tiles wide, are in
+    tests/test_gpu_elementwise_variants.py."""
     from vfml.weights import seeded_state_dict
     cfg, _ = _cfgs(**over)
     net = _engine(cfg, seeded_state_dict(cfg, 0))

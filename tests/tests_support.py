@@ -112,6 +112,32 @@ def oracle_f64(cfg, state_dict):
 _PAIRS = {}
 
 
+def _networks(cfg, state_dict, plan, corr_volume, builder, n):
+    """n fresh float32 oracles (eval mode, weights loaded) from `builder`, a module with build_network: oracle.mof_oracle (the
+    default), tests/mof_gma_oracle.py, tests/mof_sk_oracle.py, or oracle.plan_oracle (the default with a `plan`), whose
+    build_network also takes the plan and the correlation volume's format."""
+    from oracle import plan_oracle as po
+    if builder is None:
+        from oracle import mof_oracle as mo
+        builder = mo if plan is None else po
+    if builder is po:
+        nets = [po.build_network(cfg, {} if plan is None else plan, corr_volume) for _ in range(n)]
+    elif plan is not None:
+        raise ValueError(f"{builder.__name__} builds no oracle of a plan: there is none for this variant")
+    else:
+        nets = [builder.build_network(cfg) for _ in range(n)]
+    for net in nets:
+        net.load_state_dict(state_dict)
+        net.eval()
+    return nets
+
+
+def _key(x, cfg, state_dict, plan, corr_volume, builder):
+    return (_digest(x), repr(sorted(vars(cfg).items())), _digest(*state_dict.values()),
+            None if plan is None else repr(sorted((k, str(v)) for k, v in plan.items())), corr_volume,
+            None if builder is None else builder.__name__)
+
+
 def _digest(*tensors):
     h = hashlib.sha1()
     for t in tensors:
@@ -120,23 +146,17 @@ def _digest(*tensors):
     return h.hexdigest()
 
 
-def oracle_pair(x, cfg, state_dict, plan=None, corr_volume="f32"):
+def oracle_pair(x, cfg, state_dict, plan=None, corr_volume="f32", builder=None):
     """The oracle's fields for frames x [1, T, 3, H, W] (float32) in float32 and in float64, computed once per session and
     input: {"f32": (flow, low), "f64": (flow, low), "seconds": (t32, t64)}.  With `plan` (an mfma_plan dict; {} counts) the
-    oracle of that plan (oracle/plan_oracle.py) instead of the plain one."""
-    key = (_digest(x), repr(sorted(vars(cfg).items())), _digest(*state_dict.values()),
-           None if plan is None else repr(sorted((k, str(v)) for k, v in plan.items())), corr_volume)
+    oracle of that plan (oracle/plan_oracle.py) instead of the plain one; with `builder` (a module with build_network, see
+    _networks) that variant's oracle."""
+    key = _key(x, cfg, state_dict, plan, corr_volume, builder)
     ent = _PAIRS.get(key)
     if ent is None:
         torch.set_num_threads(min(16, torch.get_num_threads()))
-        if plan is None:
-            nets = oracle_f32(cfg, state_dict), oracle_f64(cfg, state_dict)
-        else:
-            from oracle import plan_oracle as po
-            nets = (po.build_network(cfg, plan, corr_volume).eval(), po.build_network(cfg, plan, corr_volume).eval())
-            for n in nets:
-                n.load_state_dict(state_dict)
-            nets[1].double()
+        nets = _networks(cfg, state_dict, plan, corr_volume, builder, 2)
+        nets[1].double()
         ent, secs = {}, []
         for name, net, xin in (("f32", nets[0], x.float()), ("f64", nets[1], x.double())):
             t0 = time.time()
@@ -147,52 +167,49 @@ def oracle_pair(x, cfg, state_dict, plan=None, corr_volume="f32"):
     return ent
 
 
-def noise_floor(x, cfg, state_dict, plan=None, corr_volume="f32"):
+def noise_floor(x, cfg, state_dict, plan=None, corr_volume="f32", builder=None):
     """N: the statistics of the float32 oracle's field against the float64 oracle's, on input x.  Every bound of the
     elementwise tests is a multiple of this; nothing in it comes from the engine."""
-    p = oracle_pair(x, cfg, state_dict, plan, corr_volume)
+    p = oracle_pair(x, cfg, state_dict, plan, corr_volume, builder)
     return error_stats(p["f32"][0], p["f64"][0])
 
 
-def noise_floor_low(x, cfg, state_dict, plan=None, corr_volume="f32"):
-    p = oracle_pair(x, cfg, state_dict, plan, corr_volume)
+def noise_floor_low(x, cfg, state_dict, plan=None, corr_volume="f32", builder=None):
+    p = oracle_pair(x, cfg, state_dict, plan, corr_volume, builder)
     return low_stats(p["f32"][1], p["f64"][1])
 
 
 # ----------------------------------------------------------------------------- large flow from the seeded weights
 DRIFT_DIRECTION = (1.0, -0.5, -1.0, 0.75)       # forward x, forward y, backward x, backward y: cells per iteration and unit c
 DRIFT_KEY = "update_block.flow_head.conv2.bias"
+DRIFT_KEY_SK = "update_block.flow_head.ffn2.2.bias"     # the SK flow head is a PCBlock: its last 1x1's bias
 
 
-def drift_state_dict(sd, c):
+def drift_state_dict(sd, c, key=DRIFT_KEY):
     """A copy of state dict `sd` whose flow head adds c * DRIFT_DIRECTION cells to the flow in every iteration: the seeded
     weights' own flow stays near one cell, with this the 1/8-resolution flow reaches about depth * c cells (forward and
-    backward, x and y each another way).  Every other entry is the same tensor's clone; oracle and engine load the same
-    dict."""
+    backward, x and y each another way).  `key` names the bias of the flow head's last convolution (DRIFT_KEY_SK for an SK
+    checkpoint).  Every other entry is the same tensor's clone; oracle and engine load the same dict."""
     out = {k: v.clone() for k, v in sd.items()}
-    b = out[DRIFT_KEY]
-    out[DRIFT_KEY] = b + float(c) * torch.tensor(DRIFT_DIRECTION, dtype=b.dtype, device=b.device)
+    b = out[key]
+    out[key] = b + float(c) * torch.tensor(DRIFT_DIRECTION, dtype=b.dtype, device=b.device)
     return out
 
 
 _F64 = {}
 
 
-def oracle_f64_fields(x, cfg, state_dict, plan=None, corr_volume="f32"):
-    """(flow, low) of the float64 oracle alone - the plain one, or with `plan` the plan oracle - for frames x
-    [1, T, 3, H, W], computed once per session and input (half the work of oracle_pair where no float32 run is needed)."""
-    key = (_digest(x), repr(sorted(vars(cfg).items())), _digest(*state_dict.values()),
-           None if plan is None else repr(sorted((k, str(v)) for k, v in plan.items())), corr_volume)
+def oracle_f64_fields(x, cfg, state_dict, plan=None, corr_volume="f32", builder=None):
+    """(flow, low) of the float64 oracle alone - the plain one, with `plan` the plan oracle, with `builder` that variant's (see
+    _networks) - for frames x [1, T, 3, H, W], computed once per session and input (half the work of oracle_pair where no
+    float32 run is needed)."""
+    key = _key(x, cfg, state_dict, plan, corr_volume, builder)
     ent = _F64.get(key)
+    if ent is None and key in _PAIRS:          # (the same network on the same input: oracle_pair has run it already)
+        ent = _F64[key] = _PAIRS[key]["f64"]
     if ent is None:
         torch.set_num_threads(min(16, torch.get_num_threads()))
-        if plan is None:
-            net = oracle_f64(cfg, state_dict)
-        else:
-            from oracle import plan_oracle as po
-            net = po.build_network(cfg, plan, corr_volume).eval()
-            net.load_state_dict(state_dict)
-            net.double()
+        net = _networks(cfg, state_dict, plan, corr_volume, builder, 1)[0].double()
         ent = _F64[key] = net(x.double(), {}, return_lowres=True)
     return ent
 
