@@ -15,7 +15,7 @@ iteration is one long-K GEMM  attn[P,P] . v[P,128]  on the MFMA kernel with the 
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, update_block
 from .network import MOFNetHIP, _Holder
 from .weights import pack_conv_weight
 
@@ -96,7 +96,7 @@ class MemFlowNetHIP(MOFNetHIP):
                tuple(p.data_ptr() for p in self.parameters()))
         if self._packed is not None and self._packed_key == key:
             return self._packed
-        P, hid, cblock_names = {}, self.hidden_dim, set()
+        P, cblock_names = {}, set()
         ub = "update_block"
         for name, cout, cin, kh, kw in self._spec:
             leaf = self._param(name)
@@ -112,30 +112,10 @@ class MemFlowNetHIP(MOFNetHIP):
             if cb:
                 cblock_names.add(name)
             P[name] = (pack_conv_weight(w, cin_pad=4 if cin in (2, 3) else None, cblock=cb), b)
-        self._cout_of = {}
-        for k in ("1", "2"):
-            raw = {g: self._param(f"{ub}.gru.conv{g}{k}") for g in "zrq"}
-            wzr = torch.cat([raw["z"].weight, raw["r"].weight]).detach().to(device=device, dtype=torch.float32)
-            bzr = torch.cat([raw["z"].bias, raw["r"].bias]).detach().to(device=device, dtype=torch.float32)
-            wq = raw["q"].weight.detach().to(device=device, dtype=torch.float32)
-            bq = raw["q"].bias.detach().to(device=device, dtype=torch.float32)
-            for nm, wfull, bfull, co in ((f"{ub}.gru.convzr{k}", wzr, bzr, 2 * hid), (f"{ub}.gru.convq{k}", wq, bq, hid)):
-                it = torch.cat([wfull[:, :hid], wfull[:, 2 * hid:]], dim=1)
-                P[nm + ".iter"] = (pack_conv_weight(it, cblock=split), None)
-                P[nm + ".ctx"] = (pack_conv_weight(wfull[:, hid:2 * hid], cblock=split), bfull.contiguous())
-                if split:
-                    cblock_names.update((nm + ".iter", nm + ".ctx"))
-                self._cout_of[nm + ".iter"] = co
-            for g in "zrq":
-                del P[f"{ub}.gru.conv{g}{k}"]
+        # (three MFMAs per product everywhere: every split-row layer in 32-channel K blocks)
+        self._pack_gates(P, device, split, self._block_of(split, set()), cblock_names)
         if split:
-            with torch.cuda.device(device):
-                for name, (wflat, b) in list(P.items()):
-                    cout = self._cout_of[name] if name in self._cout_of else b.numel()
-                    sc = hip.SplitWeight.auto_scale(float(wflat.abs().max()))
-                    sw = hip.SplitWeight(cout, wflat.numel() // cout, device).fill(wflat, scale=sc)
-                    sw.order = hip.KORDER_CBLOCK if name in cblock_names else hip.KORDER_TAP
-                    P[name] = (sw, b)
+            self._split_planes(P, device, cblock_names)
         self._gamma = float(self._param(ub).gamma.item())   # read once per load: .item() synchronises
         self._packed, self._packed_key = P, key
         self._packed_serial += 1
@@ -181,68 +161,61 @@ class MemFlowNetHIP(MOFNetHIP):
         P = self._pack(dev)
         if self._precision() != "f16x3":
             raise ValueError("the MemFlow path is built on the split-f16 kernels: cfg.precision must be 'f16x3'")
-        split, AF = True, hip.FMT_S16
-        cor = L * (2 * R + 1) ** 2
-        cor_p = (cor + 31) // 32 * 32 if split else (cor + 3) // 4 * 4
-        ub = "update_block"
-        gamma = self._gamma
+        AF = hip.FMT_S16
+        cor_p = (L * (2 * R + 1) ** 2 + 31) // 32 * 32        # the lookup block in whole K steps: the uniform-step loader
 
         with torch.cuda.device(dev):
-            hl, wl = [h], [w]
-            for l in range(1, L):
-                hl.append(hl[-1] // 2)
-                wl.append(wl[-1] // 2)
-            Sl = [hl[l] * wl[l] for l in range(L)]
-            # volumes in tiles under tile-ordered rows, row strides an odd number of 128-byte lines (network.py _tile / _run)
-            VT = self._tile()
-            Nl = [VT.count(hl[l], wl[l]) for l in range(L)] if VT is not None else Sl
-            Pv, TILE = Nl[0], (VT.code if VT is not None else 0)
-            ldl = [(s + 31) // 32 * 32 for s in Nl]
-            ldl = [n if (n // 32) % 2 else n + 32 for n in ldl]
+            # volumes in tiles under tile-ordered rows, row strides an odd number of 128-byte lines, as the MOF engine's
+            geo = self._volume_geometry(H, W, L, AF)
             keys = None
             if frame_keys is not None:
                 if len(frame_keys) != B + 1:
                     raise ValueError("frame_keys must hold one id per frame")
-                keys = [("memflow", k, H, W, L, self._precision(), TILE, self._packed_serial) for k in frame_keys]
-            feats = self._frame_features(src, list(range(B + 1)), keys, H, W, P, dev, L, hl, wl, Sl, vt=VT)
+                keys = [("memflow", k, H, W, L, self._precision(), geo.TILE, self._packed_serial) for k in frame_keys]
+            feats = self._frame_features(src, list(range(B + 1)), keys, H, W, P, dev, L, geo.hl, geo.wl, geo.Sl, vt=geo.VT)
             ctx = self._frame_context_plain(src, B, H, W, P, dev, Pn, AF)       # cnet on the B previous frames
             pyrs = []
             for k in range(B):       # pair k: queries = frame k, targets = frame k+1
-                pyr = [self._buf(f"mpyr{k}_{l}", Pv * ldl[l], dev) for l in range(L)]
+                pyr = [self._buf(f"mpyr{k}_{l}", geo.psz[l], dev) for l in range(L)]
                 for l in range(L):
-                    hip.conv2d(feats[k][0], D, D, 1, 1, Pv, feats[k + 1][1][l], None, Nl[l], 1, 1, pyr[l], ldl[l],
+                    hip.conv2d(feats[k][0], D, D, 1, 1, geo.Pv, feats[k + 1][1][l], None, geo.Nl[l], 1, 1, pyr[l], geo.ldl[l],
                                out_scale=1.0 / float(D) ** 0.5 / self.FMAP_ROW_SCALE, in_fmt=AF)   # query rows carry x16
                 pyrs.append(pyr)
 
-            GLD, Z, RH, HH, INP, MF, MT = 768, 0, 128, 256, 384, 512, 640
-            G = self._buf("gru_state", MP * GLD, dev)
-            G.view(MP, GLD)[:, HH:HH + 256].copy_(ctx.view(MP, 256))
+            def rows(name, c, zero=False):
+                return self._buf(name, MP * c, dev, zero=zero)
+            GLD, cols = self._state_columns()
+            s = update_block.window_state(
+                P, self._nm, AF, h, w, geo, R, rows("gru_state", GLD), GLD, cols, cor_p, cor_p, False, False,
+                corr=rows("mcorr", cor_p, zero=True), c1=rows("c1", 256), cf=rows("cf", 256), f1=rows("f1", 128),
+                fh=rows("fh", 256), flow4=rows("flow4", 4), coords1=rows("coords1", 4),
+                delta=rows("mdelta", 4, zero=True),     # channels 2,3 stay zero: no backward flow here
+                fh_taps=None, frows=None)
+            G, INP = s.G, s.INP
+            G.view(MP, GLD)[:, s.HH:s.HH + 256].copy_(ctx.view(MP, 256))
             # context parts of the GRU gates (+ bias), once per field
             gate_add = {}
             for k, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
                 for g, co in (("zr", 256), ("q", 128)):
-                    wgt, b = P[f"{ub}.gru.conv{g}{k}.ctx"]
+                    wgt, b = P[f"update_block.gru.conv{g}{k}.ctx"]
                     a = self._buf(f"gate_add_{g}{k}", MP * co, dev)
                     hip.conv2d(G, 128, GLD, B, h, w, wgt, b, co, kh, kw, a, co, in0_off=INP, pad_h=kh // 2,
                                pad_w=kw // 2, in_fmt=AF)
                     gate_add[g + k] = a
 
             # memory read-out operator: attn = softmax(q k^T / sqrt(d)), P x P per pair, once per field
-            P8 = (Pn + 7) // 8 * 8
-            # V as plain f16 in the read-out (one MFMA per product, 64-channel steps of hi halves: the kernel's NM 5): row
-            # stride a multiple of 64
-            ldA = (P8 + 63) // 64 * 64
             qmap = self._buf("att_q", MP * AD, dev)
             kmap = self._buf("att_k", MP * AD, dev)
             wgt, b = P["query"]
             hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, qmap, AD, in0_off=INP, in_fmt=AF, out_fmt=AF)
             wgt, b = P["key"]
             hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, kmap, AD, in0_off=INP, in_fmt=AF)
+            # probabilities as ONE f16 each (round to nearest, times ATT_SCALE): 2^-12 relative per probability, unbiased -
+            # the 1080p EPE does not move (tests/test_gpu_memflow.py); else - small or odd frames - as split rows
+            # (update_block.attention_readout has the two forms of the read-out)
+            P8, ldA, plain = self._attention_geometry(Pn)
+            plain = ATT_PLAIN and plain
             scores = self._buf("att_scores", Pn * ldA, dev)
-            # probabilities as ONE f16 each (round to nearest, times ATT_SCALE): the read-out streams the matrix 12 times
-            # per field and is bound by its bytes; 2^-12 relative per probability, unbiased - the 1080p EPE does not move
-            # (tests/test_gpu_memflow.py).  The matrix is then the WEIGHT plane of the read-out GEMM (out^T = V^T . A^T).
-            plain = ATT_PLAIN and Pn >= 1024 and Pn % 4 == 0 and Pn * ldA * 2 <= 0x7ffffff0 and ldA <= 32768
             attn = []
             for k in range(B):
                 kw_ = hip.SplitWeight(Pn, AD, dev).fill(kmap, src_off=k * Pn * AD, scale=16.0)
@@ -257,91 +230,29 @@ class MemFlowNetHIP(MOFNetHIP):
                     a = self._buf(f"att_probs{k}", Pn * ldA, dev)
                     hip.softmax_rows_s16(scores, Pn, Pn, ldA, a, ldA, scale=ATT_SCALE)
                 attn.append(a)
+            ro = update_block.readout_scratch(self._buf, dev, MP, Pn, AD, ldA, plain,
+                                              None if plain else hip.SplitWeight(AD, P8, dev))
+            gate_off = dict.fromkeys(gate_add, 0)
 
-            corr = self._buf("mcorr", MP * cor_p, dev, zero=True)
-            c1 = self._buf("c1", MP * 256, dev)
-            cf = self._buf("cf", MP * 256, dev)
-            f1 = self._buf("f1", MP * 128, dev)
-            fh = self._buf("fh", MP * 256, dev)
-            val = self._buf("att_v", MP * AD, dev)
-            flow4 = self._buf("flow4", MP * 4, dev)
-            delta = self._buf("mdelta", MP * 4, dev, zero=True)     # channels 2,3 stay zero: no backward flow here
-            coords1 = self._buf("coords1", MP * 4, dev)
-            if plain:
-                vrows = self._buf("att_vt", AD * ldA, dev)            # V^T as split rows [AD][ldA]
-                ro = self._buf("att_ro", AD * ldA, dev)               # the GEMM's primary output [AD][ldA] (unused)
-                ro_t = self._buf("att_ro_t", Pn * AD, dev)            # its transpose: attn . v, [Pn][AD]
-                ro_ws = self._buf("att_ro_ws", AD * ldA + Pn * AD, dev)   # second half of the K axis (vfml.h ksplit_ws)
-            else:
-                vt = hip.SplitWeight(AD, P8, dev)
-
-            hip.coords_init(coords1, B, h, w)
-            hip.coords_update(coords1, None, B, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD, flow_b_off=MF + 124,
-                              fmt_b=AF)
+            update_block.init_coords(s, B)
             for it in range(cfg.decoder_depth):
-                hip.corr_lookup(pyrs, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, cor_p, out_fmt=AF, vol_tile=TILE)
-                wgt, b = P[f"{ub}.encoder.convc1"]
-                hip.conv2d(corr, cor_p, cor_p, B, h, w, wgt, b, 256, 1, 1, c1, 256, epilogue=hip.EPI_RELU,
-                           in_fmt=AF, out_fmt=AF)
-                wgt, b = P[f"{ub}.encoder.convc2"]
-                hip.conv2d(c1, 256, 256, B, h, w, wgt, b, 192, 3, 3, cf, 256, pad_h=1, pad_w=1, epilogue=hip.EPI_RELU,
-                           in_fmt=AF, out_fmt=AF)
-                wgt, b = P[f"{ub}.encoder.convf1"]
-                hip.conv2d(flow4, 4, 4, B, h, w, wgt, b, 128, 7, 7, f1, 128, pad_h=3, pad_w=3, epilogue=hip.EPI_RELU,
-                           out_fmt=AF)
-                wgt, b = P[f"{ub}.encoder.convf2"]
-                hip.conv2d(f1, 128, 128, B, h, w, wgt, b, 64, 3, 3, cf, 256, out_off=192, pad_h=1, pad_w=1,
-                           epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF)
-                # motion features [conv out (124) | fx, fy, 0, 0]: the flow quad is written by coords_update
-                wgt, b = P[f"{ub}.encoder.conv"]
-                hip.conv2d(cf, 256, 256, B, h, w, wgt, b, 124, 3, 3, G, GLD, out_off=MF, pad_h=1, pad_w=1,
-                           epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF)
+                update_block.lookup(s, B, 0, pyrs=pyrs)
+                update_block.convc1(s, B, 0)
+                update_block.convc2(s, B, 0)
+                update_block.flow_half(s, B, 0)
+                update_block.encoder_conv(s, B, 0)
                 # value map and memory read-out  m_global = m + gamma * attn . v  (per pair: its own attention)
-                wgt, b = P[f"{ub}.value"]
-                hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, val, AD, in0_off=MF, in_fmt=AF)
-                for k in range(B if plain else 0):
-                    hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
-                    hip.conv2d(vrows, ldA, ldA, AD, 1, 1, attn[k], None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
-                               in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
-                    hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=gamma, aux_off=k * Pn * GLD + MF,
-                                   out_off=k * Pn * GLD + MT)
-                for k in range(0 if plain else B):
-                    vt.fill_transposed(val, Pn, ld=AD, scale=16.0, src_off=k * Pn * AD)
-                    # rows as the batch axis (1x1 "images"): one GEMM over the whole 4.2 GB attention matrix -
-                    # the LDS-DMA kernel bases its source descriptor at each tile's first row
-                    hip.conv2d(attn[k], P8, ldA, Pn, 1, 1, vt, None, AD, 1, 1, G, GLD, out_off=k * Pn * GLD + MT,
-                               out_scale=gamma / ATT_SCALE, epilogue=hip.EPI_ADD_AUX, aux0=G, ld_aux0=GLD, aux0_off=k * Pn * GLD + MF,
-                               in_fmt=AF, out_fmt=AF, aux_fmt=AF)
-                for k, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
-                    wgt, _ = P[f"{ub}.gru.convzr{k}.iter"]
-                    hip.conv2d(G, 128, GLD, B, h, w, wgt, None, 256, kh, kw, G, GLD, in0_off=HH, out_off=Z,
-                               in1=G, c1=256, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
-                               epilogue=hip.EPI_GRU_ZR, split=128, aux0=G, ld_aux0=GLD, aux0_off=HH,
-                               addend=gate_add["zr" + k], ld_addend=256, in_fmt=AF, out_fmt=AF, aux_fmt=AF)
-                    wgt, _ = P[f"{ub}.gru.convq{k}.iter"]
-                    hip.conv2d(G, 128, GLD, B, h, w, wgt, None, 128, kh, kw, G, GLD, in0_off=RH, out_off=HH,
-                               in1=G, c1=256, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
-                               epilogue=hip.EPI_GRU_Q, aux0=G, ld_aux0=GLD, aux0_off=Z,
-                               aux1=G, ld_aux1=GLD, aux1_off=HH, addend=gate_add["q" + k], ld_addend=128,
-                               in_fmt=AF, out_fmt=AF, aux_fmt=AF)
-                wgt, b = P[f"{ub}.flow_head.conv1"]
-                hip.conv2d(G, 128, GLD, B, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
-                           epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF)
-                wgt, b = P[f"{ub}.flow_head.conv2"]
-                hip.conv2d(fh, 256, 256, B, h, w, wgt, b, 2, 3, 3, delta, 4, pad_h=1, pad_w=1, in_fmt=AF)
-                hip.coords_update(coords1, delta, B, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD,
-                                  flow_b_off=MF + 124, fmt_b=AF)
+                update_block.attention_readout(s, "update_block.value", attn, plain, ldA, P8, self._gamma, ATT_SCALE,
+                                               s.MF, s.MT, ro)
+                update_block.sep_conv_gru(s, B, gate_add, gate_off)
+                update_block.flow_head(s, B, cout=2)
 
             mask = self._buf("mmask", MP * 576, dev)
-            wgt, b = P[f"{ub}.mask.0"]
-            hip.conv2d(G, 128, GLD, B, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
-                       epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF)
-            wgt, b = P[f"{ub}.mask.2"]
-            hip.conv2d(fh, 256, 256, B, h, w, wgt, b, 576, 1, 1, mask, 576, out_scale=0.25, in_fmt=AF)
+            update_block.mask_head(s, B, mask, 576)
             up = torch.empty(B, H, W, 2, device=dev, dtype=torch.float32)
             for k in range(B):
-                hip.convex_upsample(coords1, k * Pn * 4, 0, mask, k * Pn * 576, 576, h, w, up.view(-1), out_off=k * H * W * 2)
-            low = flow4.view(B, h, w, 4)[..., :2].permute(0, 3, 1, 2).clone()
+                hip.convex_upsample(s.coords1, k * Pn * 4, 0, mask, k * Pn * 576, 576, h, w, up.view(-1), out_off=k * H * W * 2)
+            low = s.flow4.view(B, h, w, 4)[..., :2].permute(0, 3, 1, 2).clone()
         return low, up.permute(0, 3, 1, 2)
 
     def _frame_context_plain(self, src, B, H, W, P, dev, Pn, AF):

@@ -18,15 +18,16 @@ Pipeline per call (names from SURVEY.md §2b):
   loop decoder_depth times:
      K5 lookup (fwd, bwd)                  vfml_corr_lookup
      K6 motion encoder, temporal fusion, SepConvGRU (gates fused into the conv epilogues),
-        flow head                          vfml_conv2d, vfml_coords_update
+        flow head                          vfml_conv2d, vfml_coords_update   (each layer's launch: vfml/update_block.py)
   mask head (last iteration only) + K8 8x convex upsampling   vfml_conv2d, vfml_convex_upsample
 """
 import os
+import types
 
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, update_block
 from .weights import (BASE_CORR_LEVELS, BASE_CORR_RADIUS, GMA_NO_BIAS, conv_spec, corr_channel_subset, is_depthwise, pack_conv_weight,
                       pcblock_hidden, sk_blocks)
 
@@ -174,7 +175,7 @@ class MOFNetHIP(_Holder):
         self._packed_serial = 0
         self._ws = {}
         self._graphs = {}
-        self._side2 = {}      # per device: the stream of the flow half of the motion encoder (_run body)
+        self._side2 = {}      # per device: the stream of the flow half of the motion encoder (_iteration)
         self._pyr_free = []
         self._side = {}                # per device: the stream the next window's encoders run on (prefetch_frames)
         self._prefetch_done = None     # event: the last prefetch's launches
@@ -206,15 +207,7 @@ class MOFNetHIP(_Holder):
         P, cblock_names, cb64_names = {}, set(), set()
         cout_packed = {}       # layers whose packed matrix has another row count than their bias
         rows7 = set()          # convf1 as a 7x1 convolution over the horizontal taps' rows
-
-        def block_of(layer, c0, ctot, cout):
-            """K-axis block of a split-row layer's weight planes: 64 channels where the layer runs one MFMA per product
-            over whole 64-channel blocks, more than 32 outputs wide (the kernel then steps 64 channels of hi halves at a
-            time: include/vfml.h VFML_KORDER_CBLOCK64), else 32."""
-            if split and self._nm(layer) == 1 and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32:
-                cb64_names.add(layer)
-                return 64
-            return True
+        block_of = self._block_of(split, cb64_names)
         sk_names = self._pack_sk(P, device, block_of, cblock_names, cout_packed) if self.sk else ()
         for name, cout, cin, kh, kw in self._spec:
             if name in sk_names:
@@ -261,42 +254,9 @@ class MOFNetHIP(_Holder):
                 cout_packed[name] = cout
             P[name] = (pack_conv_weight(w, cin_pad=4 if cin == 3 else None, cblock=cb),
                        leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous() if name not in GMA_NO_BIAS else None)
-        # GRU gates.  Input channels are [h | inp | motion | temporal]; `inp` (the context map) does not
-        # change over the iterations, so its part of every gate convolution (+ bias) is computed once per
-        # frame and added in the epilogue ("addend"); the per-iteration convolutions see [h | motion |
-        # temporal] only (K 2560 -> 1920).  z and r share their input: one conv with 2*hidden outputs.
-        hid = self.hidden_dim
-        self._cout_of = {}
-        for k in () if self.sk else ("1", "2"):      # (the SK block's `gru` is a PCBlock: no gates)
-            self._cout_of[f"update_block.gru.convzr{k}.iter"] = 2 * hid
-            self._cout_of[f"update_block.gru.convq{k}.iter"] = hid
-            raw = {g: self._param(f"update_block.gru.conv{g}{k}") for g in "zrq"}
-            wzr = torch.cat([raw["z"].weight, raw["r"].weight]).detach().to(device=device, dtype=torch.float32)
-            bzr = torch.cat([raw["z"].bias, raw["r"].bias]).detach().to(device=device, dtype=torch.float32)
-            wq = raw["q"].weight.detach().to(device=device, dtype=torch.float32)
-            bq = raw["q"].bias.detach().to(device=device, dtype=torch.float32)
-            for nm, wfull, bfull in ((f"update_block.gru.convzr{k}", wzr, bzr), (f"update_block.gru.convq{k}", wq, bq)):
-                it = torch.cat([wfull[:, :hid], wfull[:, 2 * hid:]], dim=1)
-                P[nm + ".iter"] = (pack_conv_weight(it, cblock=block_of(nm + ".iter", hid, it.shape[1], it.shape[0]) if split else False), None)
-                P[nm + ".ctx"] = (pack_conv_weight(wfull[:, hid:2 * hid], cblock=block_of(nm + ".ctx", hid, hid, wfull.shape[0]) if split else False),
-                                  bfull.contiguous())
-                if split:
-                    cblock_names.update((nm + ".iter", nm + ".ctx"))
-            for g in "zrq":
-                del P[f"update_block.gru.conv{g}{k}"]
+        self._pack_gates(P, device, split, block_of, cblock_names, () if self.sk else ("1", "2"))   # (SK: `gru` is a PCBlock)
         if split:
-            # split-f16 planes (hi, lo*2^11) of every [cout][K] matrix, made once per load
-            with torch.cuda.device(device):
-                for name, (wflat, b) in list(P.items()):
-                    if is_depthwise(name):      # [c][k][k] f32 with their bias: the vector-ALU kernel's operands, no planes
-                        continue
-                    cout = self._cout_of[name] if name in self._cout_of else cout_packed[name] if name in cout_packed else b.numel()
-                    sc = hip.SplitWeight.auto_scale(float(wflat.abs().max()))
-                    sw = hip.SplitWeight(cout, wflat.numel() // cout, device).fill(wflat, scale=sc)
-                    sw.order = (hip.KORDER_CBLOCK64 if name in cb64_names else
-                                hip.KORDER_CBLOCK if name in cblock_names else hip.KORDER_TAP)
-                    P[name] = (sw, b)
-        if split:
+            self._split_planes(P, device, cblock_names, cb64_names, cout_packed)
             for enc in ("fnet", "cnet"):
                 leaf = self._param(f"{enc}.conv1")
                 if tuple(leaf.weight.shape) == (64, 3, 7, 7):
@@ -315,6 +275,56 @@ class MOFNetHIP(_Holder):
         self._packed_serial += 1          # new weights: cached encoder outputs are stale
         self._feat_cache.clear()
         return P
+
+    def _block_of(self, split, cb64_names):
+        def block_of(layer, c0, ctot, cout):
+            """K-axis block of a split-row layer's weight planes: 64 channels where the layer runs one MFMA per product
+            over whole 64-channel blocks, more than 32 outputs wide (the kernel then steps 64 channels of hi halves at a
+            time: include/vfml.h VFML_KORDER_CBLOCK64), else 32."""
+            if split and self._nm(layer) == 1 and c0 % 64 == 0 and ctot % 64 == 0 and cout > 32:
+                cb64_names.add(layer)
+                return 64
+            return True
+        return block_of
+
+    def _pack_gates(self, P, device, split, block_of, cblock_names, passes=("1", "2")):
+        """GRU gates.  Input channels are [h | inp | motion | temporal]; `inp` (the context map) does not
+        change over the iterations, so its part of every gate convolution (+ bias) is computed once per
+        frame and added in the epilogue ("addend"): P[gate + ".ctx"]; the per-iteration convolutions, P[gate + ".iter"],
+        see [h | motion | temporal] only (K 2560 -> 1920).  z and r share their input: one conv with 2*hidden outputs."""
+        hid = self.hidden_dim
+        self._cout_of = {}
+        for k in passes:
+            self._cout_of[f"update_block.gru.convzr{k}.iter"] = 2 * hid
+            self._cout_of[f"update_block.gru.convq{k}.iter"] = hid
+            raw = {g: self._param(f"update_block.gru.conv{g}{k}") for g in "zrq"}
+            wzr = torch.cat([raw["z"].weight, raw["r"].weight]).detach().to(device=device, dtype=torch.float32)
+            bzr = torch.cat([raw["z"].bias, raw["r"].bias]).detach().to(device=device, dtype=torch.float32)
+            wq = raw["q"].weight.detach().to(device=device, dtype=torch.float32)
+            bq = raw["q"].bias.detach().to(device=device, dtype=torch.float32)
+            for nm, wfull, bfull in ((f"update_block.gru.convzr{k}", wzr, bzr), (f"update_block.gru.convq{k}", wq, bq)):
+                it = torch.cat([wfull[:, :hid], wfull[:, 2 * hid:]], dim=1)
+                P[nm + ".iter"] = (pack_conv_weight(it, cblock=block_of(nm + ".iter", hid, it.shape[1], it.shape[0]) if split else False), None)
+                P[nm + ".ctx"] = (pack_conv_weight(wfull[:, hid:2 * hid], cblock=block_of(nm + ".ctx", hid, hid, wfull.shape[0]) if split else False),
+                                  bfull.contiguous())
+                if split:
+                    cblock_names.update((nm + ".iter", nm + ".ctx"))
+            for g in "zrq":
+                del P[f"update_block.gru.conv{g}{k}"]
+
+    def _split_planes(self, P, device, cblock_names, cb64_names=(), cout_packed={}):
+        """split-f16 planes (hi, lo*2^11) of every [cout][K] matrix of P, made once per load.  cout_packed: layers whose
+        packed matrix has another row count than their bias."""
+        with torch.cuda.device(device):
+            for name, (wflat, b) in list(P.items()):
+                if is_depthwise(name):      # [c][k][k] f32 with their bias: the vector-ALU kernel's operands, no planes
+                    continue
+                cout = self._cout_of[name] if name in self._cout_of else cout_packed[name] if name in cout_packed else b.numel()
+                sc = hip.SplitWeight.auto_scale(float(wflat.abs().max()))
+                sw = hip.SplitWeight(cout, wflat.numel() // cout, device).fill(wflat, scale=sc)
+                sw.order = (hip.KORDER_CBLOCK64 if name in cb64_names else
+                            hip.KORDER_CBLOCK if name in cblock_names else hip.KORDER_TAP)
+                P[name] = (sw, b)
 
     sk = False                 # (class defaults: engines that share this class's plumbing but have no such block)
     _sk_blocks = {}
@@ -573,8 +583,8 @@ class MOFNetHIP(_Holder):
     # ------------------------------------------------------------------ per-frame attention of the GMA aggregator
     # attn = softmax(q k^T / sqrt(128)) over the cells of ONE centre frame, q | k = att.to_qk(inp): it depends on the frame's
     # context map alone, so it is built beside the gates' context parts (_frame_context) and kept like them - in a slot of a
-    # ring, named by the frame's context cache entry, reused by every window the frame is a centre of.  Two forms, chosen as
-    # MemFlow's read-out chooses (memflow_net.py): the probabilities times ATT_SCALE as ONE f16 each, the weight plane
+    # ring, named by the frame's context cache entry, reused by every window the frame is a centre of.  Two forms, chosen by
+    # _attention_geometry for this engine and for MemFlow (update_block.attention_readout reads both): the probabilities times ATT_SCALE as ONE f16 each, the weight plane
     # (hip.PlainWeight) of a long-K GEMM (2.1 GB per 1080p frame), or - small or odd frames - as split rows.
     # The read-out GEMMs are fixed launches of the replayed graph and take the plane's ADDRESS, so the window's slots are part
     # of the graph's key; the ring is therefore short (M + 2: a window's centres, the centre a prefetch adds, one spare) and a
@@ -939,7 +949,6 @@ class MOFNetHIP(_Holder):
 
     def _volume_geometry(self, H, W, L, AF):
         """Shapes of a window's correlation volumes: level sizes, the tile layout, element format, row strides, buffer sizes."""
-        import types
         cfg = self.cfg
         h, w = H // 8, W // 8
         hl, wl = [h], [w]
@@ -1140,6 +1149,163 @@ class MOFNetHIP(_Holder):
                     self._cache_put("c", keys[j], out[j])
         return out
 
+    # ------------------------------------------------------------------ a window's recurrent state (vfml/update_block.py)
+    def _state_columns(self):
+        """(GLD, columns) of the recurrent state, one row of GLD floats per cell:  [ z | r*h | h | inp | mf | mt ]"""
+        # (one allocation, so that cat([r*h, x]) and cat([h, x]) are channel slices of it; XC: what the gates read behind h,
+        # [mf | mt])
+        GLD, cols = 768, dict(Z=0, RH=128, HH=256, INP=384, MF=512, MT=640, MG=None, XC=256)
+        if self.gma:        # ... | mg ]: the aggregated motion features, a fourth block of the gates' input
+            GLD = 896
+            cols.update(MG=768, XC=384)
+        if self.sk:
+            # the SK block's `gru` is a PCBlock over [h | inp | mf | mt (| mg)], read in place: no gate columns, and the
+            # context half `inp` sits in the row (the plain block's gates take it as a per-frame addend)
+            GLD = 640 if self.gma else 512
+            cols.update(HH=0, INP=128, MF=256, MT=384, MG=512)
+        return GLD, cols
+
+    def _window_state(self, P, dev, M, h, w, geo, R, AF, cor_p):
+        """Window layout and buffers: the update block's record of a window of M centre frames."""
+        MP = M * h * w
+        GLD, cols = self._state_columns()
+        if self.gma and self._att_store is not None:
+            self._att_store["live"] = set()     # (the last window's read-outs are ahead of this one on the stream)
+
+        def rows(name, c):
+            return self._buf(name, MP * c, dev)
+        return update_block.window_state(
+            P, self._nm if self._split() else (lambda layer: 3),      # MFMAs per product of a layer (cfg.precision)
+            AF, h, w, geo, R, rows("gru_state", GLD), GLD, cols, 2 * cor_p, cor_p, self._rows7, self._tapsum,
+            corr=self._buf("corr", MP * 2 * cor_p, dev, zero=True),   # pad channels stay zero
+            c1=rows("c1", 256), cf=rows("cf", 256), f1=rows("f1", 128), fh=rows("fh", 256), flow4=rows("flow4", 4),
+            delta=rows("delta", 4), fh_taps=rows("fh_taps", 2 * 36),     # (two partial maps with the fused flow head)
+            frows=rows("flow_rows7", 32), coords1=rows("coords1", 4))
+
+    def _seed_plan(self, s, ctx, keys, dev, M, R, pick_only):
+        """The iteration-zero seed plan -> (store, warm, keys of the entries this window fills, seed cells)."""
+        # h = tanh half of the context map (the relu half reaches the gates as their addends), and the `mf` columns of the
+        # centres whose iteration 0 an earlier window ran: one launch inside the body (vfml_window_seed), told what to copy
+        # by three device cells per centre.  The store applies where iteration 0 covers every centre of a keyed window.
+        cfg, it0 = self.cfg, None
+        # (not for SK checkpoints: the window set-up copies h | inp as ONE 256-column block, and vfml_window_seed moves a
+        # slot of the same width as the context block - DESIGN.md section 16)
+        if (self.iter0_store and not self.sk and keys is not None and self._split() and not self.tri_frame and M >= 2
+                and cfg.decoder_depth >= 1 and not (pick_only and cfg.decoder_depth + 1 < M)):
+            it0 = self._iter0_store(dev, s.Pn, M)
+            warm, seeds, it0_new = it0["ring"].plan(keys, tail=(R,))
+            self.iter0_stats["warm" if warm else "cold"] += 1
+            self.iter0_last = (warm, [slot for slot, _ in seeds])
+        else:
+            warm, seeds, it0_new = False, [(None, hip.SEED_NONE)] * M, []
+        seed_cells = self._buf("seed_cells", 64, dev, torch.int64)
+        hip.ptr_table_set(seed_cells, [v for i, (slot, mode) in enumerate(seeds) for v in
+                                       (ctx[i + 1][0], it0["S"][slot * s.Pn * 128:] if slot is not None else 0, mode)])
+        return it0, warm, it0_new, seed_cells
+
+    def _gate_addends(self, ctx, dev, Pn, M):
+        """The gates' context parts -> (gate_add, gate_off, gate_ind) of update_block.sep_conv_gru."""
+        # the centre frames' slots, consecutive in a sliding job (through the mirror when the ring wraps) - else gathered
+        # into the store's spare slots
+        st = self._ctx_store
+        RING, Mst = st["R"], st["M"]
+        slots = [ctx[c][2] for c in range(1, M + 1)]
+        st["live"] = set(slots)
+        first = slots[0]
+        # (the exact-f32 kernel takes the pointer itself - a captured launch needs it fixed: always the gathered copy)
+        # (A/B switch: VFML_CTX_GATHER=1 gathers every window, as round 2 did)
+        if not self.sk and (not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or
+                            not all(s == first + i or (first + i >= RING and s == first + i - RING and s < Mst - 1)
+                                    for i, s in enumerate(slots))):
+            first = RING + Mst - 1
+            for i, c in enumerate(range(1, M + 1)):
+                for name, co in self.CTX_GATES:
+                    st["S"][name][(first + i) * Pn * co:(first + i + 1) * Pn * co].copy_(ctx[c][1][name])
+        gate_add = {name: st["S"].get(name) for name, _ in self.CTX_GATES}
+        gate_off = {name: first * Pn * co for name, co in self.CTX_GATES}
+        gate_ind = None
+        if self._split() and not self.sk:      # (the exact-f32 kernel takes the pointer itself)
+            cells = self._buf("gate_add_cells", 8, dev, torch.int64)
+            hip.ptr_table_set(cells, [st["S"][name][gate_off[name]:] for name, _ in self.CTX_GATES])
+            gate_ind = {name: (cells, i) for i, (name, _) in enumerate(self.CTX_GATES)}
+        return gate_add, gate_off, gate_ind
+
+    def _pyramid_tables(self, pyrs, dev, M, L, cor_p):
+        """The device tables that name a window's pyramids -> (tables, bidir) of update_block.lookup."""
+        # both directions behind one another in one table where they fit: the two lookups of an iteration as ONE launch
+        # (at most 8 maps)
+        if 2 * M <= 8 and 2 * M * L <= 48:
+            tab_fb = self._buf("pyr_table_fb", 64, dev, torch.int64)
+            hip.ptr_table_set(tab_fb, [p for d in ("f", "b") for m in pyrs[d] for p in m])
+            return (tab_fb,), (2, cor_p, M)
+        tab_f = self._buf("pyr_table_f", 64, dev, torch.int64)
+        tab_b = self._buf("pyr_table_b", 64, dev, torch.int64)
+        hip.ptr_table_set(tab_f, [p for m in pyrs["f"] for p in m])
+        hip.ptr_table_set(tab_b, [p for m in pyrs["b"] for p in m])
+        return (tab_f, tab_b), None
+
+    def _gma_readout(self, s, win, ng):
+        """mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention, on the ng centres whose GRU runs."""
+        att = self._att_store
+        update_block.attention_readout(s, "update_block.aggregator.to_v", [att["A"][k] for k in win.att_slots[:ng]],
+                                       att["plain"], att["ldA"], att["P8"], self._gamma, ATT_SCALE, s.MF, s.MG, win.readout)
+
+    def _iteration(self, s, win, it, ng, nm, branch):
+        """One iteration of the plain update block: GRU + flow head on `ng` centres, lookups + motion encoder on `nm`."""
+        # The flow half of the motion encoder (flow -> convf1 -> convf2 -> channels 192..255 of `cf`) needs nothing of the
+        # correlation half (lookups -> convc1 -> convc2 -> channels 0..191): on a second stream (`branch`, VFML_FLOW_BRANCH)
+        # its small MFMA-bound convolutions run BESIDE the HBM-bound lookups (a fork / join of two events; inside a captured
+        # graph, two branches).  Same kernels on the same inputs: bit-identical fields.
+        # Iteration 0 of a warm window: the per-frame launches (lookups, motion encoder up to encoder.conv) run on the newest
+        # centre alone - ne frames from row r0 on - and the seed pass brings the other centres' rows.
+        ub = update_block
+        ne, r0 = (1, (win.M - 1) * s.Pn) if win.warm and it == 0 else (nm, 0)
+        join = None
+        if branch is not None:
+            fork = torch.cuda.Event()
+            fork.record()                      # (flow4 of the previous iteration is complete on this stream)
+            with torch.cuda.stream(branch):
+                branch.wait_event(fork)
+                ub.flow_half(s, ne, r0)
+                join = torch.cuda.Event()
+                join.record()
+        ub.lookup(s, ne, r0, win.tables, win.bidir)
+        ub.convc1(s, ne, r0)
+        ub.convc2(s, ne, r0)
+        if join is None:
+            ub.flow_half(s, ne, r0)
+        else:
+            torch.cuda.current_stream(win.dev).wait_event(join)
+        ub.encoder_conv(s, ne, r0)
+        if it == 0:
+            # h of every centre from its context map; mf rows (with the zero flow in channels 124..127) out of the
+            # older centres' slots and into the new ones
+            hip.window_seed(win.seed_cells, win.M, s.Pn, 128, s.G, s.GLD, s.HH, s.MF, 256)
+        if self.gma:
+            self._gma_readout(s, win, ng)
+        update_block.temporal_fusion(s, win.M if self.tri_frame else nm, stack=not self.tri_frame)
+        ub.sep_conv_gru(s, ng, *win.gates)
+        ub.flow_head(s, ng)
+
+    def _sk_iteration(self, s, win, ng, nm):
+        """One iteration of the SK update block: lookup, the five PCBlocks of the motion encoder, the GMA read-out,
+        the temporal fusion, `gru` and `flow_head`."""
+        ub, P, h, w, G, GLD, ws = "update_block", s.P, s.h, s.w, s.G, s.GLD, win.sk_ws
+        blk = self._pcblock
+        update_block.lookup(s, nm, 0, win.tables, win.bidir)
+        blk(f"{ub}.encoder.convc1", P, s.corr, s.ld_corr, 0, nm, h, w, s.c1, 256, 0, ws, gelu_out=True)
+        blk(f"{ub}.encoder.convc2", P, s.c1, 256, 0, nm, h, w, s.cf, 256, 0, ws)
+        wgt, b = P[f"{ub}.encoder.convf1"]
+        hip.conv2d(s.flow4, 4, 4, nm, h, w, wgt, b, 128, 1, 1, s.f1, 128, out_fmt=s.AF, mfma=s.nm(f"{ub}.encoder.convf1"))
+        blk(f"{ub}.encoder.convf2", P, s.f1, 128, 0, nm, h, w, s.cf, 256, 192, ws)
+        blk(f"{ub}.encoder.conv", P, s.cf, 256, 0, nm, h, w, G, GLD, s.MF, ws)
+        if self.gma:
+            self._gma_readout(s, win, ng)
+        update_block.temporal_fusion(s, win.M if self.tri_frame else nm, stack=not self.tri_frame)
+        blk(f"{ub}.gru", P, G, GLD, 0, ng, h, w, G, GLD, s.HH, ws)
+        blk(f"{ub}.flow_head", P, G, GLD, s.HH, ng, h, w, s.delta, 4, 0, ws, out_fmt=hip.FMT_F32)
+        update_block.update_coords(s, ng)
+
     def _run(self, src, N, H, W, return_lowres, frame_keys=None, tri_batch=False, pick_only=False):
         cfg = self.cfg
         if N < 3:
@@ -1151,7 +1317,7 @@ class MOFNetHIP(_Holder):
             N = 3
         if H % 8 or W % 8:
             raise ValueError("H and W must be multiples of 8 (use InputPadder)")
-        L, R, D = cfg.corr_levels, cfg.corr_radius, cfg.feat_dim
+        L, R = cfg.corr_levels, cfg.corr_radius
         h, w = H // 8, W // 8
         if (h >> (L - 1)) < 2 or (w >> (L - 1)) < 2:
             raise ValueError(f"frame {H}x{W} too small for a {L}-level correlation pyramid")
@@ -1164,351 +1330,80 @@ class MOFNetHIP(_Holder):
                              f"most 32768; process larger frames in tiles (--tile)")
         MP = M * Pn
         P = self._pack(dev)
-        win = (2 * R + 1) ** 2
-        cor = L * win
         AF = hip.FMT_S16 if self._split() else hip.FMT_F32   # update-block activations
-        cor_p = cor_pad(cor, AF == hip.FMT_S16)   # per-direction channel block
+        cor_p = cor_pad(L * (2 * R + 1) ** 2, AF == hip.FMT_S16)   # per-direction channel block
+        short = pick_only and not self.tri_frame      # only the reference's pick is wanted: flow M of the full output
 
         with torch.cuda.device(dev):
             geo = self._volume_geometry(H, W, L, AF)
-            hl, wl, Sl, VT, TILE, vol16, VF, ldl = geo.hl, geo.wl, geo.Sl, geo.VT, geo.TILE, geo.vol16, geo.VF, geo.ldl
             keys = None
             if frame_keys is not None:   # geometry and arithmetic are part of a cached frame's identity
                 keys = [(k, H, W, L, self._plan_key(), self._packed_serial) for k in frame_keys]
 
             # K1 + K2: feature maps and pooled target pyramids, per frame (cached across windows)
-            feats = self._frame_features(src, list(range(N)), keys, H, W, P, dev, L, hl, wl, Sl, vt=VT)
-
+            feats = self._frame_features(src, list(range(N)), keys, H, W, P, dev, L, geo.hl, geo.wl, geo.Sl, vt=geo.VT)
             # K3/K4 correlation pyramids, one per problem (query frame -> target frame)
             pyrs = self._window_pyramids(feats, keys, N, geo, dev)
-
-            # Recurrent state, one row of GLD floats per cell:  [ z | r*h | h | inp | mf | mt ]
-            # (one allocation, so that cat([r*h, x]) and cat([h, x]) are channel slices of it)
-            GLD, Z, RH, HH, INP, MF, MT = 768, 0, 128, 256, 384, 512, 640
-            XC = 256            # what the gates read behind h: [mf | mt]
-            if self.gma:        # ... | mg ]: the aggregated motion features, a fourth block of the gates' input
-                GLD, MG, XC = 896, 768, 384
-                if self._att_store is not None:
-                    self._att_store["live"] = set()     # (the last window's read-outs are ahead of this one on the stream)
-            if self.sk:
-                # the SK block's `gru` is a PCBlock over [h | inp | mf | mt (| mg)], read in place: no gate columns, and the
-                # context half `inp` sits in the row (the plain block's gates take it as a per-frame addend)
-                GLD, HH, INP, MF, MT, MG = (640 if self.gma else 512), 0, 128, 256, 384, 512
-            G = self._buf("gru_state", MP * GLD, dev)
+            s = self._window_state(P, dev, M, h, w, geo, R, AF, cor_p)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
-            att_slots = ()
+            win = types.SimpleNamespace(M=M, dev=dev, att_slots=(), readout=None)
             if self.gma:
                 att = self._att_store
-                att_slots = tuple(ctx[c][4] for c in range(1, N - 1))
-                att["live"] = set(att_slots)
-                AD, ldA = self.ATT_DIM, att["ldA"]
-                val = self._buf("att_v", MP * AD, dev)
-                if att["plain"]:
-                    vrows = self._buf("att_vt", AD * ldA, dev)            # V^T as split rows [AD][ldA]
-                    ro = self._buf("att_ro", AD * ldA, dev)               # the GEMM's primary output [AD][ldA] (unused)
-                    ro_t = self._buf("att_ro_t", Pn * AD, dev)            # its transpose: attn . v, [Pn][AD]
-                    ro_ws = self._buf("att_ro_ws", AD * ldA + Pn * AD, dev)   # second half of the K axis (vfml.h ksplit_ws)
-            # h = tanh half of the context map (the relu half reaches the gates as their addends), and the `mf` columns of the
-            # centres whose iteration 0 an earlier window ran: one launch inside the body (vfml_window_seed), told what to copy
-            # by three device cells per centre.  The store applies where iteration 0 covers every centre of a keyed window.
-            it0 = None
-            # (not for SK checkpoints: the window set-up copies h | inp as ONE 256-column block, and vfml_window_seed moves a
-            # slot of the same width as the context block - DESIGN.md section 16)
-            if (self.iter0_store and not self.sk and keys is not None and self._split() and not self.tri_frame and M >= 2
-                    and cfg.decoder_depth >= 1 and not (pick_only and cfg.decoder_depth + 1 < M)):
-                it0 = self._iter0_store(dev, Pn, M)
-                warm, seeds, it0_new = it0["ring"].plan(keys, tail=(R,))
-                self.iter0_stats["warm" if warm else "cold"] += 1
-                self.iter0_last = (warm, [s for s, _ in seeds])
-            else:
-                warm, seeds, it0_new = False, [(None, hip.SEED_NONE)] * M, []
-            seed_cells = self._buf("seed_cells", 64, dev, torch.int64)
-            hip.ptr_table_set(seed_cells, [v for i, (s, mode) in enumerate(seeds) for v in
-                                           (ctx[i + 1][0], it0["S"][s * Pn * 128:] if s is not None else 0, mode)])
-            # the gates' context parts: the centre frames' slots, consecutive in a sliding job (through the mirror when the ring
-            # wraps) - else gathered into the store's spare slots
-            st = self._ctx_store
-            RING, Mst = st["R"], st["M"]
-            slots = [ctx[c][2] for c in range(1, N - 1)]
-            st["live"] = set(slots)
-            first = slots[0]
-            # (the exact-f32 kernel takes the pointer itself - a captured launch needs it fixed: always the gathered copy)
-            # (A/B switch: VFML_CTX_GATHER=1 gathers every window, as round 2 did)
-            if not self.sk and (not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or
-                    not all(s == first + i or (first + i >= RING and s == first + i - RING and s < Mst - 1)
-                            for i, s in enumerate(slots))):
-                first = RING + Mst - 1
-                for i, c in enumerate(range(1, N - 1)):
-                    for name, co in self.CTX_GATES:
-                        st["S"][name][(first + i) * Pn * co:(first + i + 1) * Pn * co].copy_(ctx[c][1][name])
-            gate_add = {name: st["S"].get(name) for name, _ in self.CTX_GATES}
-            gate_off = {name: first * Pn * co for name, co in self.CTX_GATES}
-            gate_ind = None
-            if self._split() and not self.sk:      # (the exact-f32 kernel takes the pointer itself)
-                cells = self._buf("gate_add_cells", 8, dev, torch.int64)
-                hip.ptr_table_set(cells, [st["S"][name][gate_off[name]:] for name, _ in self.CTX_GATES])
-                gate_ind = {name: (cells, i) for i, (name, _) in enumerate(self.CTX_GATES)}
-
-            corr = self._buf("corr", MP * 2 * cor_p, dev, zero=True)   # pad channels stay zero
-            c1 = self._buf("c1", MP * 256, dev)
-            cf = self._buf("cf", MP * 256, dev)
-            f1 = self._buf("f1", MP * 128, dev)
-            fh = self._buf("fh", MP * 256, dev)
-            flow4 = self._buf("flow4", MP * 4, dev)
-            delta = self._buf("delta", MP * 4, dev)
-            fh_taps = self._buf("fh_taps", 2 * MP * 36, dev)     # (two partial maps with the fused flow head)
-            frows = self._buf("flow_rows7", MP * 32, dev)
-            coords1 = self._buf("coords1", MP * 4, dev)
-            sk_ws = self._sk_workspace(MP, dev) if self.sk else None
-
-            # ---- the update iterations + mask head + upsampling: a FIXED launch sequence for a given geometry,
-            # window length and arithmetic - only the correlation pyramids it looks up differ from field to field,
-            # and those are named by two device tables.  With cfg.use_graph the sequence is captured into a HIP
-            # graph the second time a configuration is seen and replayed from then on (~250 launches per field
-            # become one; same kernels, same order: bit-identical results).
-            # both directions behind one another in one table: the two lookups of an iteration as ONE launch (at most 8 maps)
-            bidir = 2 * M <= 8 and 2 * M * L <= 48
-            if bidir:
-                tab_fb = self._buf("pyr_table_fb", 64, dev, torch.int64)
-                hip.ptr_table_set(tab_fb, [p for d in ("f", "b") for m in pyrs[d] for p in m])
-            else:
-                tab_f = self._buf("pyr_table_f", 64, dev, torch.int64)
-                tab_b = self._buf("pyr_table_b", 64, dev, torch.int64)
-                hip.ptr_table_set(tab_f, [p for m in pyrs["f"] for p in m])
-                hip.ptr_table_set(tab_b, [p for m in pyrs["b"] for p in m])
-            no = 1 if pick_only and not self.tri_frame else M
-            nflows = 1 if pick_only and not self.tri_frame else 2 * M
+                win.att_slots = tuple(ctx[c][4] for c in range(1, N - 1))
+                att["live"] = set(win.att_slots)
+                win.readout = update_block.readout_scratch(self._buf, dev, MP, Pn, self.ATT_DIM, att["ldA"], att["plain"],
+                                                           att["vt"])
+            it0, win.warm, it0_new, win.seed_cells = self._seed_plan(s, ctx, keys, dev, M, R, pick_only)
+            win.gates = self._gate_addends(ctx, dev, Pn, M)
+            win.sk_ws = self._sk_workspace(MP, dev) if self.sk else None
+            win.tables, win.bidir = self._pyramid_tables(pyrs, dev, M, L, cor_p)
+            no, nflows = (1, 1) if short else (M, 2 * M)
             up_fixed = self._buf("up_out", nflows * H * W * 2, dev)
             mask = self._buf("mask", MP * 1152, dev)
 
+            # ---- the update iterations + mask head + upsampling: a FIXED launch sequence for a given geometry,
+            # window length and arithmetic - only the correlation pyramids it looks up differ from field to field,
+            # and those are named by device tables.  With cfg.use_graph the sequence is captured into a HIP
+            # graph the second time a configuration is seen and replayed from then on (~250 launches per field
+            # become one; same kernels, same order: bit-identical results).
             def body():
-                hip.coords_init(coords1, M, h, w)
-                hip.coords_update(coords1, None, M, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD, flow_b_off=MF + 124,
-                                  fmt_b=AF)
-                ub = "update_block"
-                mf = self._nm if self._split() else (lambda layer: 3)     # MFMAs per product of a layer (cfg.precision)
+                update_block.init_coords(s, M)
                 branch = None
                 if os.environ.get("VFML_FLOW_BRANCH", "0") == "1" and self._split():
                     branch = self._side2.get(dev)
                     if branch is None:
                         branch = self._side2[dev] = torch.cuda.Stream(device=dev)
-                fuse = AF == hip.FMT_S16          # the fused flow-head / flow-half launches read split rows
-
-                def gma_readout(ng):
-                    # mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention (the read-out GEMM as
-                    # MemFlow runs it: memflow_net.py); on the ng centres whose GRU runs
-                    wgt, _ = P[f"{ub}.aggregator.to_v"]
-                    hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, AD, 1, 1, val, AD, in0_off=MF, in_fmt=AF,
-                               mfma=mf(f"{ub}.aggregator.to_v"))
-                    for k in range(ng):
-                        a = att["A"][att_slots[k]]
-                        if att["plain"]:
-                            hip.transpose_to_s16(val, Pn, AD, AD, vrows, ldA, scale=16.0, src_off=k * Pn * AD)
-                            hip.conv2d(vrows, ldA, ldA, AD, 1, 1, a, None, Pn, 1, 1, ro, ldA, out_scale=1.0 / 16.0,
-                                       in_fmt=AF, out_t=ro_t, ld_out_t=AD, mfma=1, ksplit_ws=ro_ws)
-                            hip.add_to_s16(ro_t, AD, G, GLD, G, GLD, Pn, AD, scale=self._gamma,
-                                           aux_off=k * Pn * GLD + MF, out_off=k * Pn * GLD + MG)
-                        else:
-                            vt = att["vt"].fill_transposed(val, Pn, ld=AD, scale=16.0, src_off=k * Pn * AD)
-                            hip.conv2d(a, att["P8"], ldA, Pn, 1, 1, vt, None, AD, 1, 1, G, GLD, out_off=k * Pn * GLD + MG,
-                                       out_scale=self._gamma / ATT_SCALE, epilogue=hip.EPI_ADD_AUX, aux0=G, ld_aux0=GLD,
-                                       aux0_off=k * Pn * GLD + MF, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
-                                       mfma=mf(f"{ub}.aggregator.readout"))
-
-                def sk_iteration(ng, nm):
-                    """One iteration of the SK update block: lookup, the five PCBlocks of the motion encoder, the GMA read-out,
-                    the temporal fusion, `gru` and `flow_head`."""
-                    blk = self._pcblock
-                    if bidir:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF,
-                                        table=tab_fb, nmaps=nm, vol_fmt=VF, vol_tile=TILE, bidir=(2, cor_p, M))
-                    else:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 0, 4, corr, 0, 2 * cor_p, out_fmt=AF,
-                                        table=tab_f, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, 2, 4, corr, cor_p, 2 * cor_p,
-                                        out_fmt=AF, table=tab_b, nmaps=nm, vol_fmt=VF, vol_tile=TILE)
-                    blk(f"{ub}.encoder.convc1", P, corr, 2 * cor_p, 0, nm, h, w, c1, 256, 0, sk_ws, gelu_out=True)
-                    blk(f"{ub}.encoder.convc2", P, c1, 256, 0, nm, h, w, cf, 256, 0, sk_ws)
-                    wgt, b = P[f"{ub}.encoder.convf1"]
-                    hip.conv2d(flow4, 4, 4, nm, h, w, wgt, b, 128, 1, 1, f1, 128, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
-                    blk(f"{ub}.encoder.convf2", P, f1, 128, 0, nm, h, w, cf, 256, 192, sk_ws)
-                    blk(f"{ub}.encoder.conv", P, cf, 256, 0, nm, h, w, G, GLD, MF, sk_ws)
-                    if self.gma:
-                        gma_readout(ng)
-                    wgt, b = P[f"{ub}.tprop"]
-                    if self.tri_frame:
-                        hip.conv2d(G, 128, GLD, M, 1, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
-                    else:
-                        hip.conv2d(G, 128, GLD, 1, nm, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
-                    blk(f"{ub}.gru", P, G, GLD, 0, ng, h, w, G, GLD, HH, sk_ws)
-                    blk(f"{ub}.flow_head", P, G, GLD, HH, ng, h, w, delta, 4, 0, sk_ws, out_fmt=hip.FMT_F32)
-                    hip.coords_update(coords1, delta, ng, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD, flow_b_off=MF + 124,
-                                      fmt_b=AF)
-
                 if self.sk:
                     # h | inp of every centre from its context map (one 256-column block), before the first iteration
-                    hip.window_seed(seed_cells, M, Pn, 256, G, GLD, HH, MF, 256)
+                    hip.window_seed(win.seed_cells, M, Pn, 256, s.G, s.GLD, s.HH, s.MF, 256)
                 for it in range(cfg.decoder_depth):
                     # pick_only: the caller takes flow M (the backward flow of the first centre frame - the reference's
                     # `[0, shape[1]//2]`).  Going back from the last iteration, centre 0's result depends on one centre
                     # more per iteration (through the temporal fusion), so the last iterations run on the centres
                     # that still matter only: GRU + flow head on `ng`, lookups + motion encoder on `nm` of them.
                     left = cfg.decoder_depth - 1 - it
-                    ng = min(M, left + 1) if pick_only and not self.tri_frame else M
-                    nm = min(M, left + 2) if pick_only and not self.tri_frame else M
+                    ng = min(M, left + 1) if short else M
+                    nm = min(M, left + 2) if short else M
                     if self.sk:
-                        sk_iteration(ng, nm)
-                        continue
-                    # The flow half of the motion encoder (flow -> convf1 -> convf2 -> channels 192..255 of `cf`) needs
-                    # nothing of the correlation half (lookups -> convc1 -> convc2 -> channels 0..191): on a second stream
-                    # its small MFMA-bound convolutions run BESIDE the HBM-bound lookups (a fork / join of two events; inside
-                    # a captured graph, two branches).  Same kernels on the same inputs: bit-identical fields.
-                    # Iteration 0 of a warm window: the per-frame launches (lookups, motion encoder up to encoder.conv) run on
-                    # the newest centre alone - ne frames from row r0 on - and the seed pass brings the other centres' rows.
-                    ne, r0 = (1, (M - 1) * Pn) if warm and it == 0 else (nm, 0)
-
-                    def flow_half(ne=ne, r0=r0):
-                        wgt, b = P[f"{ub}.encoder.convf1"]
-                        wgt2, b2 = P[f"{ub}.encoder.convf2"]
-                        if (fuse and self._rows7 and mf(f"{ub}.encoder.convf1") == 1 and mf(f"{ub}.encoder.convf2") == 1
-                                and getattr(wgt2, "order", None) == hip.KORDER_CBLOCK64 and wgt.kp == 224 and wgt2.kp == 1152):
-                            # both layers in one launch, the 128-channel map between them in LDS (vfml_flow_half; same bits)
-                            hip.flow_half(flow4[r0 * 4:], ne, h, w, wgt, b, wgt2, b2, cf, 256, out_off=r0 * 256 + 192)
-                            return
-                        if self._rows7:
-                            hip.flow_rows7(flow4[r0 * 4:], ne, h, w, frows[r0 * 32:])
-                            hip.conv2d(frows, 32, 32, ne, h, w, wgt, b, 128, 7, 1, f1, 128, pad_h=3, epilogue=hip.EPI_RELU,
-                                       in0_off=r0 * 32, out_off=r0 * 128, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
-                        else:
-                            hip.conv2d(flow4, 4, 4, ne, h, w, wgt, b, 128, 7, 7, f1, 128, pad_h=3, pad_w=3, epilogue=hip.EPI_RELU,
-                                       in0_off=r0 * 4, out_off=r0 * 128, out_fmt=AF, mfma=mf(f"{ub}.encoder.convf1"))
-                        wgt, b = P[f"{ub}.encoder.convf2"]
-                        hip.conv2d(f1, 128, 128, ne, h, w, wgt, b, 64, 3, 3, cf, 256, in0_off=r0 * 128, out_off=r0 * 256 + 192,
-                                   pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF,
-                                   mfma=mf(f"{ub}.encoder.convf2"))
-
-                    join = None
-                    if branch is not None:
-                        fork = torch.cuda.Event()
-                        fork.record()                      # (flow4 of the previous iteration is complete on this stream)
-                        with torch.cuda.stream(branch):
-                            branch.wait_event(fork)
-                            flow_half()
-                            join = torch.cuda.Event()
-                            join.record()
-                    # K5
-                    # (the tables from the first looked-up centre's pyramids on: the second direction's lie M maps behind still)
-                    t0 = r0 // Pn * L
-                    if bidir:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4, 4, corr, r0 * 2 * cor_p, 2 * cor_p, out_fmt=AF,
-                                        table=tab_fb[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE, bidir=(2, cor_p, M))
+                        self._sk_iteration(s, win, ng, nm)
                     else:
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4, 4, corr, r0 * 2 * cor_p, 2 * cor_p, out_fmt=AF,
-                                        table=tab_f[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE)
-                        hip.corr_lookup(None, hl, wl, ldl, R, Pn, coords1, r0 * 4 + 2, 4, corr, r0 * 2 * cor_p + cor_p, 2 * cor_p,
-                                        out_fmt=AF, table=tab_b[t0:], nmaps=ne, vol_fmt=VF, vol_tile=TILE)
-                    # motion encoder
-                    wgt, b = P[f"{ub}.encoder.convc1"]
-                    hip.conv2d(corr, 2 * cor_p, 2 * cor_p, ne, h, w, wgt, b, 256, 1, 1, c1, 256, epilogue=hip.EPI_RELU,
-                               in0_off=r0 * 2 * cor_p, out_off=r0 * 256, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc1"))
-                    wgt, b = P[f"{ub}.encoder.convc2"]
-                    hip.conv2d(c1, 256, 256, ne, h, w, wgt, b, 192, 3, 3, cf, 256, in0_off=r0 * 256, out_off=r0 * 256,
-                               pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.convc2"))
-                    if join is None:
-                        flow_half()
-                    else:
-                        torch.cuda.current_stream(dev).wait_event(join)
-                    wgt, b = P[f"{ub}.encoder.conv"]
-                    hip.conv2d(cf, 256, 256, ne, h, w, wgt, b, 124, 3, 3, G, GLD, in0_off=r0 * 256, out_off=r0 * GLD + MF,
-                               pad_h=1, pad_w=1, epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.encoder.conv"))
-                    if it == 0:
-                        # h of every centre from its context map; mf rows (with the zero flow in channels 124..127) out of the
-                        # older centres' slots and into the new ones
-                        hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
-                    if self.gma:
-                        gma_readout(ng)
-                    # temporal stack fusion: 3x1 conv along the frame axis of the motion features
-                    wgt, b = P[f"{ub}.tprop"]
-                    if self.tri_frame:     # every centre frame is its own problem: its neighbours are the zero padding
-                        hip.conv2d(G, 128, GLD, M, 1, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
-                    else:
-                        # (on the first nm frames: row nm-1 of a shortened stack sees zero padding where its lower
-                        # neighbour was - that row is not among the ng < nm the GRU reads)
-                        hip.conv2d(G, 128, GLD, 1, nm, Pn, wgt, b, 128, 3, 1, G, GLD, in0_off=MF, out_off=MT, pad_h=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.tprop"))
-                    # SepConvGRU, horizontal then vertical
-                    for k, (kh, kw) in (("1", (1, 5)), ("2", (5, 1))):
-                        wgt, _ = P[f"{ub}.gru.convzr{k}.iter"]
-                        # [z | r*h] = gates(conv([h | motion | temporal]) + context part)
-                        hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, 256, kh, kw, G, GLD, in0_off=HH, out_off=Z,
-                                   in1=G, c1=XC, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
-                                   epilogue=hip.EPI_GRU_ZR, split=128, aux0=G, ld_aux0=GLD, aux0_off=HH,
-                                   addend=gate_add["zr" + k], ld_addend=256, in_fmt=AF, out_fmt=AF, aux_fmt=AF,
-                                   addend_off=0 if gate_ind else gate_off["zr" + k],
-                                   addend_ind=gate_ind["zr" + k] if gate_ind else None,
-                                   mfma=mf(f"{ub}.gru.convzr{k}.iter"))
-                        wgt, _ = P[f"{ub}.gru.convq{k}.iter"]
-                        # h = (1 - z) h + z tanh(conv([r*h | motion | temporal]) + context part), in place
-                        hip.conv2d(G, 128, GLD, ng, h, w, wgt, None, 128, kh, kw, G, GLD, in0_off=RH, out_off=HH,
-                                   in1=G, c1=XC, ld1=GLD, in1_off=MF, pad_h=kh // 2, pad_w=kw // 2,
-                                   epilogue=hip.EPI_GRU_Q, aux0=G, ld_aux0=GLD, aux0_off=Z,
-                                   aux1=G, ld_aux1=GLD, aux1_off=HH, addend=gate_add["q" + k], ld_addend=128,
-                                   addend_off=0 if gate_ind else gate_off["q" + k],
-                                   addend_ind=gate_ind["q" + k] if gate_ind else None,
-                                   in_fmt=AF, out_fmt=AF, aux_fmt=AF, mfma=mf(f"{ub}.gru.convq{k}.iter"))
-                    # flow head
-                    wgt, b = P[f"{ub}.flow_head.conv1"]
-                    wgt2, b2 = P[f"{ub}.flow_head.conv2"]
-                    nm_head = mf(f"{ub}.flow_head.conv1")
-                    if self._tapsum and fuse and nm_head in (3, "2a") and mf(f"{ub}.flow_head.conv2") == nm_head:
-                        # both layers in ONE launch (vfml_conv_desc.proj_out): the 256-channel map stays in LDS, the launch
-                        # leaves two partial 36-column maps (one per 128-channel half) that the tap sum adds
-                        hip.conv2d(G, 128, GLD, ng, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
-                                   epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=nm_head, proj=wgt2, proj_out=fh_taps,
-                                   ld_proj=36)
-                        hip.tapsum3x3_update(fh_taps, 36, b2, ng, h, w, coords1, parts=2, part_stride=ng * Pn * 36, flow_a=flow4,
-                                             ld_a=4, flow_b=G, ld_b=GLD, flow_b_off=MF + 124, fmt_b=AF)
-                        continue
-                    hip.conv2d(G, 128, GLD, ng, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
-                               epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.flow_head.conv1"))
-                    wgt, b = P[f"{ub}.flow_head.conv2"]
-                    if self._tapsum:
-                        # 256 -> 4 over 3x3 as a 1x1 to 36 tap-major columns + the nine taps summed per pixel (_pack)
-                        hip.conv2d(fh, 256, 256, ng, h, w, wgt, None, 36, 1, 1, fh_taps, 36, in_fmt=AF,
-                                   mfma=mf(f"{ub}.flow_head.conv2"))
-                        hip.tapsum3x3_update(fh_taps, 36, b, ng, h, w, coords1, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD,
-                                             flow_b_off=MF + 124, fmt_b=AF)
-                        continue
-                    else:
-                        hip.conv2d(fh, 256, 256, ng, h, w, wgt, b, 4, 3, 3, delta, 4, pad_h=1, pad_w=1, in_fmt=AF,
-                                   mfma=mf(f"{ub}.flow_head.conv2"))
-                    hip.coords_update(coords1, delta, ng, h, w, flow_a=flow4, ld_a=4, flow_b=G, ld_b=GLD,
-                                      flow_b_off=MF + 124, fmt_b=AF)
-
+                        self._iteration(s, win, it, ng, nm, branch)
                 if cfg.decoder_depth == 0 and not self.sk:       # (no iteration ran the window set-up: h for the mask head)
-                    hip.window_seed(seed_cells, M, Pn, 128, G, GLD, HH, MF, 256)
+                    hip.window_seed(win.seed_cells, M, Pn, 128, s.G, s.GLD, s.HH, s.MF, 256)
                 # mask head on the final hidden state, then K8 for every flow of the output tensor (pick_only: of
                 # the first centre frame, and its backward flow alone)
-                wgt, b = P[f"{ub}.mask.0"]
-                hip.conv2d(G, 128, GLD, no, h, w, wgt, b, 256, 3, 3, fh, 256, in0_off=HH, pad_h=1, pad_w=1,
-                           epilogue=hip.EPI_RELU, in_fmt=AF, out_fmt=AF, mfma=mf(f"{ub}.mask.0"))
-                wgt, b = P[f"{ub}.mask.2"]
-                hip.conv2d(fh, 256, 256, no, h, w, wgt, b, 1152, 1, 1, mask, 1152, out_scale=0.25, in_fmt=AF,
-                           mfma=mf(f"{ub}.mask.2"))
-                if pick_only and not self.tri_frame:
-                    hip.convex_upsample(coords1, 0, 2, mask, 576, 1152, h, w, up_fixed)
+                update_block.mask_head(s, no, mask, 1152)
+                if short:
+                    hip.convex_upsample(s.coords1, 0, 2, mask, 576, 1152, h, w, up_fixed)
                 else:
                     for d in range(2):
                         for c in range(M):
-                            hip.convex_upsample(coords1, c * Pn * 4, 2 * d, mask, c * Pn * 1152 + d * 576, 1152, h, w,
+                            hip.convex_upsample(s.coords1, c * Pn * 4, 2 * d, mask, c * Pn * 1152 + d * 576, 1152, h, w,
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
-            gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), vol16,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), warm, att_slots)
+            gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), geo.vol16,
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), win.warm, win.att_slots)
             if self.sk:
                 gkey += ("sk",)
             self._pre_body = torch.cuda.Event()
@@ -1520,13 +1415,11 @@ class MOFNetHIP(_Holder):
                     it0["ring"].forget(it0_new)
                 raise
             up = up_fixed.clone().view(nflows, H, W, 2)          # the caller owns its field; the fixed buffer is reused
-            if pick_only and not self.tri_frame:
-                return up.permute(0, 3, 1, 2).unsqueeze(0), None        # [1, 1, 2, H, W]: flow M of the full output
-            # [2M,H,W,2] stored HWC; expose the reference's [B, 2M, 2, H, W] as a view
+            # [2M,H,W,2] stored HWC; expose the reference's [B, 2M, 2, H, W] as a view ([1, 1, 2, H, W] of a pick)
             flow = up.permute(0, 3, 1, 2).unsqueeze(0)
-            low = None
-            if return_lowres:
-                low = flow4.view(M, h, w, 4)[..., :].clone()
+            if short:
+                return flow, None
+            low = s.flow4.view(M, h, w, 4)[..., :].clone() if return_lowres else None
         return flow, low
 
 
