@@ -32,7 +32,8 @@ extern "C" {
  * the number did not move.  26 also covers the vfml_jpeg_decode_*_sampled entry points and VFML_JPEG_420 .. _GREY, in the
  * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
  * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well; and likewise
- * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows.  27 adds vfml_conv2d_split_variant_at. */
+ * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows.  27 adds vfml_conv2d_split_variant_at; it also covers
+ * vfml_layernorm_rows, vfml_window_attention and vfml_attention_shared_keys (the Twins-SVT encoders): additions only. */
 #define VFML_ABI_VERSION 27
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -254,6 +255,33 @@ int vfml_dwconv2d(const float* x, int64_t ld_x, int n, int h, int w, int c, int 
  * stride agree.  The GELU behind a dense 1x1 convolution of a PCBlock. */
 int vfml_gelu_rows(const float* x, int64_t ld_x, float* out, int64_t ld_out, int64_t rows, int c, int in_fmt, int out_fmt,
                    void* stream);
+
+/* The three kernels of the Twins-SVT encoders (csrc/twins.hip).  Rows are in either format, as
+ * vfml_dwconv2d's (the pointers already at the first channel of a possibly wider row); the head dimension is 32.  All three
+ * are stream-ordered without host synchronisation (capturable); a bad argument returns non-zero with vfml_last_error set and
+ * launches nothing.
+ *
+ * vfml_layernorm_rows: out[r][ch] = gamma[ch] * (x[r][ch] - mean_r) / sqrt(var_r + eps) + beta[ch] over the c channels of each
+ * row, biased variance, f32 statistics (mean first, then the variance of x - mean: no cancellation); c a multiple of 8, at
+ * most 2048; the row is read once.  In place allowed where the row strides agree (the formats may differ).
+ * Replaces: nn.LayerNorm over the token dimension. */
+int vfml_layernorm_rows(const float* x, int64_t ld_x, float* out, int64_t ld_out, int64_t rows, int c, const float* gamma,
+                        const float* beta, float eps, int in_fmt, int out_fmt, void* stream);
+
+/* vfml_window_attention: locally-grouped self attention.  qkv: [n*h*w] rows of the real token grid, channels q | k | v (c each,
+ * head-major, c = heads * 32); the grid is cut into ws x ws windows anchored at (0, 0) (ws = 7 is the only size built), and a
+ * window position outside the grid (right / bottom) takes pad_row ([3c] f32: its q | k | v) - it is a key like any other, not
+ * masked.  Per window and head out = softmax(q k^T / sqrt 32) v over the 49 tokens; out: [n*h*w] rows of c channels, real
+ * tokens only.  Scores, softmax and read-out stay on chip.  Replaces: timm's LocallyGroupedAttn between qkv and proj. */
+int vfml_window_attention(const float* qkv, int64_t ld, int n, int h, int w, int c, int heads, int ws, const float* pad_row,
+                          float* out, int64_t ld_out, int in_fmt, int out_fmt, void* stream);
+
+/* vfml_attention_shared_keys: per frame and head, p queries against the same pk keys and values.  q: [n*p] rows of c = heads * 32
+ * channels; kv: [n*pk] rows, channels k | v (c each); out[i] = softmax_j(q_i . k_j / sqrt 32) v_j, [n*p] rows of c channels.
+ * f32 products on the f32 matrix cores (v_mfma_f32_32x32x2_f32), online softmax over key chunks staged in LDS: no score
+ * reaches memory; pk >= 1, any size.  Replaces: timm's GlobalSubSampleAttn between q / kv and proj (cuBLAS bmm + softmax). */
+int vfml_attention_shared_keys(const float* q, int64_t ld_q, const float* kv, int64_t ld_kv, int n, int p, int pk, int c, int heads,
+                               float* out, int64_t ld_out, int q_fmt, int kv_fmt, int out_fmt, void* stream);
 
 /* out = aux + scale * x:  x f32 [rows][ldx], aux / out split rows (c % 8 == 0 channels). */
 int vfml_add_to_s16(const float* x, int64_t ldx, const float* aux, int64_t ld_aux, float* out, int64_t ld_out, int64_t rows,

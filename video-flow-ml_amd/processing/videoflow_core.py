@@ -9,7 +9,7 @@ import os
 import torch
 
 from vfml import InputPadder, build_network, get_cfg
-from vfml.weights import GMA_GAMMA, SK_KEY, checkpoint_name, load_checked
+from vfml.weights import GMA_GAMMA, SK_KEY, TWINS_KEY, checkpoint_name, load_checked
 
 
 def _is_gpu_name(dev: str) -> bool:
@@ -74,6 +74,8 @@ class VideoFlowCore:
         cfg.gma = GMA_GAMMA in state
         # ... and whether it is the SK update block (vfml/cfg.py `sk`)
         cfg.sk = SK_KEY in state
+        # ... and whether the encoders are the Twins-SVT ones (vfml/cfg.py `twins`)
+        cfg.twins = TWINS_KEY in state
         model = build_network(cfg)
         load_checked(model, state, model_path)
         model.to(self.device)

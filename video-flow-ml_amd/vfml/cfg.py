@@ -105,4 +105,8 @@ def get_cfg():
         # VideoFlowCore.load_model from the checkpoint's keys (`update_block.encoder.convc1.conv_list.0.weight`); needs the
         # base lookup (corr_levels, corr_radius) = (4, 4) and a split-f16 precision; off for every other checkpoint
         sk=False,
+        # Twins-SVT encoders in place of the two BasicEncoders: timm's twins_svt_large cut to two
+        # stages, as the released MOF / BOF configurations use it.  Set by VideoFlowCore.load_model from the checkpoint's keys
+        # (`fnet.svt.patch_embeds.0.proj.weight`); needs a split-f16 precision; off for every other checkpoint
+        twins=False,
     )

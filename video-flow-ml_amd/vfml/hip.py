@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -140,6 +140,12 @@ def lib():
     L.vfml_dwconv2d.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                 c_int, c_void_p]
     L.vfml_gelu_rows.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]
+    L.vfml_layernorm_rows.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_float, c_int, c_int,
+                                      c_void_p]
+    L.vfml_window_attention.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                                        c_int, c_int, c_void_p]
+    L.vfml_attention_shared_keys.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                             c_int64, c_int, c_int, c_int, c_void_p]
     L.vfml_transpose_to_s16.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p]
     L.vfml_add_to_s16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_float, c_void_p]
     L.vfml_instnorm_finalize.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p]
@@ -238,7 +244,7 @@ def lib():
 
 
 EXPORTS = [
-    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_transpose_to_s16", "vfml_add_to_s16",
+    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
@@ -592,6 +598,31 @@ def gelu_rows(x, ld_x, out, ld_out, rows, c, x_off=0, out_off=0, in_fmt=FMT_F32,
     """out[r][:c] = gelu(x[r][:c]) (exact), rows of ld_x / ld_out floats in either format; in place allowed."""
     _check(lib().vfml_gelu_rows(_ptr(_dev(x), x_off), ld_x, _ptr(_dev(out), out_off), ld_out, rows, c, in_fmt, out_fmt,
                                 _stream()), "vfml_gelu_rows")
+
+
+def layernorm_rows(x, ld_x, out, ld_out, rows, c, gamma, beta, eps=1e-5, x_off=0, out_off=0, in_fmt=FMT_F32, out_fmt=FMT_F32):
+    """out[r][:c] = LayerNorm(x[r][:c]) * gamma + beta (biased variance, f32 statistics), rows of ld_x / ld_out floats in
+    either format; in place allowed where the row strides agree (vfml_layernorm_rows)."""
+    _check(lib().vfml_layernorm_rows(_ptr(_dev(x), x_off), ld_x, _ptr(_dev(out), out_off), ld_out, rows, c, _ptr(_dev(gamma)),
+                                     _ptr(_dev(beta)), float(eps), in_fmt, out_fmt, _stream()), "vfml_layernorm_rows")
+
+
+def window_attention(qkv, ld, n, h, w, c, heads, ws, pad_row, out, ld_out, qkv_off=0, out_off=0, in_fmt=FMT_F32, out_fmt=FMT_F32):
+    """Locally-grouped attention of the Twins-SVT encoders: qkv [n*h*w][ld] rows (q | k | v, c = heads * 32 each) of the real
+    token grid, ws x ws windows anchored at (0, 0), positions outside the grid take pad_row ([3c] f32) and are NOT masked;
+    out [n*h*w][ld_out] rows of c channels (vfml_window_attention)."""
+    _check(lib().vfml_window_attention(_ptr(_dev(qkv), qkv_off), ld, n, h, w, c, heads, ws, _ptr(_dev(pad_row)),
+                                       _ptr(_dev(out), out_off), ld_out, in_fmt, out_fmt, _stream()), "vfml_window_attention")
+
+
+def attention_shared_keys(q, ld_q, kv, ld_kv, n, p, pk, c, heads, out, ld_out, q_off=0, kv_off=0, out_off=0, q_fmt=FMT_F32,
+                          kv_fmt=FMT_F32, out_fmt=FMT_F32):
+    """Per frame and head, p queries (q [n*p][ld_q]) against the same pk keys and values (kv [n*pk][ld_kv], k | v), head
+    dimension 32: out [n*p][ld_out] = softmax(q k^T / sqrt 32) v, online softmax on the f32 matrix cores
+    (vfml_attention_shared_keys)."""
+    _check(lib().vfml_attention_shared_keys(_ptr(_dev(q), q_off), ld_q, _ptr(_dev(kv), kv_off), ld_kv, n, p, pk, c, heads,
+                                            _ptr(_dev(out), out_off), ld_out, q_fmt, kv_fmt, out_fmt, _stream()),
+           "vfml_attention_shared_keys")
 
 
 def transpose_to_s16(src, rows, c, ld, dst, ld_dst, scale=1.0, src_off=0, dst_off=0):

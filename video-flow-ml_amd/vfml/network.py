@@ -28,8 +28,8 @@ import torch
 import torch.nn as nn
 
 from . import hip, update_block
-from .weights import (BASE_CORR_LEVELS, BASE_CORR_RADIUS, GMA_NO_BIAS, conv_spec, corr_channel_subset, is_depthwise, pack_conv_weight,
-                      pcblock_hidden, sk_blocks)
+from .weights import (BASE_CORR_LEVELS, BASE_CORR_RADIUS, GMA_NO_BIAS, TWINS_STAGES, TWINS_WS, conv_spec, corr_channel_subset,
+                      is_depthwise, pack_conv_weight, pcblock_hidden, sk_blocks, twins_spec)
 
 # GMA attention probabilities are stored times 2^14, as MemFlow's are (memflow_net.ATT_SCALE: an unscaled 1080p row would sit in
 # the f16 subnormals); the read-out divides it out again
@@ -159,6 +159,16 @@ class MOFNetHIP(_Holder):
                                  f"{BASE_CORR_RADIUS}), got ({cfg.corr_levels}, {cfg.corr_radius}): --fast takes a channel subset of "
                                  f"convc1's input, and a channel subset of a residual block is not defined")
             self._sk_blocks = {n: (ci, co, k) for n, ci, co, k in sk_blocks(cfg)}
+        # Twins-SVT encoders in place of the two BasicEncoders: their parameters - linear layers,
+        # LayerNorms, the patch and reduction convolutions, the depthwise position encodings - come first in the state dict
+        self.twins = bool(getattr(cfg, "twins", False))
+        self._twins_spec = twins_spec(cfg)
+        for name, _, shape in self._twins_spec:
+            leaf = self
+            for p in name.split("."):
+                leaf = leaf.child(p)
+            leaf.weight = nn.Parameter(torch.zeros(*shape), requires_grad=False)
+            leaf.bias = nn.Parameter(torch.zeros(shape[0]), requires_grad=False)
         self._spec = conv_spec(cfg)
         for name, cout, cin, kh, kw in self._spec:
             leaf = self
@@ -199,6 +209,9 @@ class MOFNetHIP(_Holder):
         if self.sk and not split:
             raise ValueError("the SK update block is built on the split-f16 kernels: cfg.precision 'f32' cannot run a "
                              "checkpoint that has it")
+        if self.twins and not split:
+            raise ValueError("the Twins-SVT encoders are built on the split-f16 kernels: cfg.precision 'f32' cannot run a "
+                             "checkpoint that has them")
         key = (str(device), split, self._plan_key(), tuple(p._version for p in self.parameters()),
                tuple(p.data_ptr() for p in self.parameters()))
         if self._packed is not None and self._packed_key == key:
@@ -209,6 +222,7 @@ class MOFNetHIP(_Holder):
         rows7 = set()          # convf1 as a 7x1 convolution over the horizontal taps' rows
         block_of = self._block_of(split, cb64_names)
         sk_names = self._pack_sk(P, device, block_of, cblock_names, cout_packed) if self.sk else ()
+        tw_raw = self._pack_twins(P, device, block_of, cblock_names, cout_packed) if self.twins else {}
         for name, cout, cin, kh, kw in self._spec:
             if name in sk_names:
                 continue
@@ -257,12 +271,13 @@ class MOFNetHIP(_Holder):
         self._pack_gates(P, device, split, block_of, cblock_names, () if self.sk else ("1", "2"))   # (SK: `gru` is a PCBlock)
         if split:
             self._split_planes(P, device, cblock_names, cb64_names, cout_packed)
-            for enc in ("fnet", "cnet"):
+            for enc in () if self.twins else ("fnet", "cnet"):
                 leaf = self._param(f"{enc}.conv1")
                 if tuple(leaf.weight.shape) == (64, 3, 7, 7):
                     with torch.cuda.device(device):
                         P[f"{enc}.conv1.stem"] = (hip.pack_stem_weight(leaf.weight, device),
                                                   leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous())
+        P.update(tw_raw)       # (f32 operands of the vector-ALU kernels: no planes)
         self._tapsum = any(n.endswith(".flow_head.conv2") for n in cout_packed)
         self._rows7 = bool(rows7)
         if self.gma:
@@ -328,6 +343,126 @@ class MOFNetHIP(_Holder):
 
     sk = False                 # (class defaults: engines that share this class's plumbing but have no such block)
     _sk_blocks = {}
+    twins = False
+
+    def _pack_twins(self, P, device, block_of, cblock_names, cout_packed):
+        """The Twins-SVT encoders' weights: every linear layer, and the patch and reduction convolutions (kernel = stride, so
+        a 1x1 over the space-to-depth rows [ky][kx][channel]), as [cout][K] matrices in the dense kernel's K order, into P
+        (split into planes by _pack).  Returns what stays f32 - LayerNorm (gamma, beta) and the depthwise position encodings
+        ([c][3][3], bias) - for _pack to add behind the planes."""
+        raw = {}
+        for name, kind, shape in self._twins_spec:
+            leaf = self._param(name)
+            w = leaf.weight.detach().to(device=device, dtype=torch.float32)
+            b = leaf.bias.detach().to(device=device, dtype=torch.float32).contiguous()
+            if kind == "ln":
+                raw[name] = (w.contiguous(), b)
+                continue
+            if kind == "dw":
+                raw[name] = (w.reshape(-1).contiguous(), b)
+                continue
+            if kind == "conv":
+                cout, cin, k, _ = shape
+                w = w.permute(0, 2, 3, 1)
+                if cin % 4:
+                    w = torch.nn.functional.pad(w, (0, 4 - cin % 4))      # (the frames are NHWC4)
+                w = w.reshape(cout, -1)
+            w = w.reshape(w.shape[0], w.shape[1], 1, 1)
+            cblock_names.add(name)
+            cout_packed[name] = w.shape[0]
+            P[name] = (pack_conv_weight(w, cblock=block_of(name, w.shape[1], w.shape[1], w.shape[0])), b)
+        return raw
+
+    def _twins_encoder(self, prefix, x, n, H, W, P, dev, out, ldo, out_off, epilogue, split, out_fmt=hip.FMT_F32):
+        """Twins-SVT encoder on NHWC4 input x [n,H,W,4]; writes [n,H/8,W/8,256] into `out` - the
+        contract of _encoder.  Token rows are split rows throughout; the dense layers run on vfml_conv2d_split (residuals
+        through VFML_EPI_ADD_AUX), q | k | v leave them as f32 rows for the two attention kernels.  The patch and reduction
+        convolutions do not overlap: a space-to-depth copy of the grid, then a 1x1."""
+        S, F32 = hip.FMT_S16, hip.FMT_F32
+        sv = f"{prefix}.svt"
+
+        def buf(name, numel):
+            return self._buf(f"tw_{name}", numel, dev)
+
+        def dense(name, src, k, rows, dst, co, ldo_=None, dst_off=0, aux=None, fmt=S):
+            wgt, b = P[name]
+            hip.conv2d(src, k, k, 1, 1, rows, wgt, b, co, 1, 1, dst, ldo_ or co, out_off=dst_off,
+                       epilogue=hip.EPI_ADD_AUX if aux is not None else hip.EPI_NONE, aux0=aux, ld_aux0=co if aux is not None else 0,
+                       in_fmt=S, out_fmt=fmt, aux_fmt=S, mfma=self._nm(name))
+
+        def norm(name, src, dst, rows, c):
+            g, b = P[name]
+            hip.layernorm_rows(src, c, dst, c, rows, c, g, b, in_fmt=S, out_fmt=S)
+
+        def patches(grid, hh, ww, c, p, ho, wo):
+            """[n][hh][ww][c] -> rows [n*ho*wo][p*p*c] of the p x p patches ([ky][kx][channel]; rows and columns behind
+            ho * p, wo * p are dropped).  Whole channel rows move: split rows stay split rows."""
+            g = grid[:n * hh * ww * c].view(n, hh, ww, c)[:, :ho * p, :wo * p]
+            return g.reshape(n, ho, p, wo, p, c).permute(0, 1, 3, 2, 4, 5).reshape(-1)
+
+        grid, hh, ww, cin = x, H, W, 4
+        last = len(TWINS_STAGES) - 1
+        for i, (p, _, c, heads, sr) in enumerate(TWINS_STAGES):
+            h, w = hh // p, ww // p
+            rows, k = n * h * w, p * p * cin
+            src = patches(grid, hh, ww, cin, p, h, w)
+            if i == 0:      # the frames are f32
+                src16 = buf("in", rows * k)
+                hip.to_s16(src, rows, k, k, src16, k)
+                src = src16
+            X, Y, T, A = (buf(f"{t}{i}", rows * c) for t in "xyta")
+            Hd = buf(f"hid{i}", rows * 4 * c)          # the MLP's hidden rows; q | k | v (3c) and q (c) as f32 before them
+            dense(f"{sv}.patch_embeds.{i}.proj", src, k, rows, X, c)
+            norm(f"{sv}.patch_embeds.{i}.norm", X, X, rows, c)
+
+            def mlp(b, src_, dst, final=False):
+                norm(f"{b}.norm2", src_, T, rows, c)
+                dense(f"{b}.mlp.fc1", T, c, rows, Hd, 4 * c)
+                hip.gelu_rows(Hd, 4 * c, Hd, 4 * c, rows, 4 * c, in_fmt=S, out_fmt=S)
+                if not final:
+                    dense(f"{b}.mlp.fc2", Hd, 4 * c, rows, dst, c, aux=src_)
+                elif epilogue == hip.EPI_NONE:
+                    dense(f"{b}.mlp.fc2", Hd, 4 * c, rows, out, c, ldo_=ldo, dst_off=out_off, aux=src_, fmt=out_fmt)
+                elif epilogue == hip.EPI_TANH_RELU:
+                    fin = buf("fin", rows * c)
+                    dense(f"{b}.mlp.fc2", Hd, 4 * c, rows, fin, c, aux=src_, fmt=F32)
+                    v = fin.view(rows, c)
+                    v[:, :split].tanh_()
+                    v[:, split:].relu_()
+                    if out_fmt == S:
+                        hip.to_s16(fin, rows, c, c, out, ldo, dst_off=out_off)
+                    else:
+                        torch.as_strided(out, (rows, c), (ldo, 1), out_off).copy_(v)
+                else:
+                    raise ValueError(f"_twins_encoder: epilogue {epilogue} is not one the encoders end in")
+
+            # blocks.i.0: locally-grouped attention over 7 x 7 windows, then the MLP
+            b = f"{sv}.blocks.{i}.0"
+            norm(f"{b}.norm1", X, T, rows, c)
+            dense(f"{b}.attn.qkv", T, c, rows, Hd, 3 * c, fmt=F32)
+            hip.window_attention(Hd, 3 * c, n, h, w, c, heads, TWINS_WS, P[f"{b}.attn.qkv"][1], A, c, out_fmt=S)
+            dense(f"{b}.attn.proj", A, c, rows, Y, c, aux=X)
+            mlp(b, Y, X)
+            # pos_block.i: x + depthwise 3 x 3
+            wgt, bias = P[f"{sv}.pos_block.{i}.proj.0"]
+            hip.dwconv2d(X, c, n, h, w, c, 3, wgt, bias, Y, c, in_fmt=S, out_fmt=S, residual=True)
+            # blocks.i.1: every query against the frame's sub-sampled keys and values, then the MLP
+            b = f"{sv}.blocks.{i}.1"
+            hr, wr = h // sr, w // sr
+            rk = n * hr * wr
+            if rk == 0:
+                raise ValueError(f"Twins-SVT encoder: a {h} x {w} token grid has no {sr} x {sr} patch to reduce (frame too small)")
+            norm(f"{b}.norm1", Y, T, rows, c)
+            dense(f"{b}.attn.q", T, c, rows, Hd, c, fmt=F32)
+            KR, KV = buf(f"r{i}", rk * c), buf(f"kv{i}", rk * 2 * c)
+            dense(f"{b}.attn.sr", patches(T, h, w, c, sr, hr, wr), sr * sr * c, rk, KR, c)
+            norm(f"{b}.attn.norm", KR, KR, rk, c)
+            dense(f"{b}.attn.kv", KR, c, rk, KV, 2 * c, fmt=F32)
+            hip.attention_shared_keys(Hd, c, KV, 2 * c, n, h * w, hr * wr, c, heads, A, c, out_fmt=S)
+            dense(f"{b}.attn.proj", A, c, rows, X, c, aux=Y)
+            mlp(b, X, Y, final=i == last)
+            grid, hh, ww, cin = Y, h, w, c
+        return hh, ww
 
     def _sk_padded(self, bname):
         """(positions of a PCBlock's channels in its padded rows, padded width, padded hidden width).  convc1 reads the
@@ -1065,7 +1200,7 @@ class MOFNetHIP(_Holder):
             hip.frames_to_nhwc4(take_frames(src, todo).contiguous(), m, H, W, float(self.cfg.input_scale), float(self.cfg.input_shift),
                                 frames)
             fmap = torch.empty(m * Pn * D, device=dev)          # owned by the cache entries (views)
-            self._encoder("fnet", frames, m, H, W, P, dev, fmap, D, 0, hip.EPI_NONE, 0)
+            (self._twins_encoder if self.twins else self._encoder)("fnet", frames, m, H, W, P, dev, fmap, D, 0, hip.EPI_NONE, 0)
             levels = [fmap]
             for l in range(1, L):
                 t = torch.empty(m * Sl[l] * D, device=dev)
@@ -1119,7 +1254,8 @@ class MOFNetHIP(_Holder):
                                 float(self.cfg.input_scale), float(self.cfg.input_shift), frames)
             ctx = torch.empty(m * Pn * 256, device=dev)
             AF = hip.FMT_S16 if self._split() else hip.FMT_F32
-            self._encoder("cnet", frames, m, H, W, P, dev, ctx, 256, 0, hip.EPI_TANH_RELU, self.hidden_dim, out_fmt=AF)
+            (self._twins_encoder if self.twins else self._encoder)("cnet", frames, m, H, W, P, dev, ctx, 256, 0, hip.EPI_TANH_RELU,
+                                                                   self.hidden_dim, out_fmt=AF)
             h8, w8 = H // 8, W // 8
             R, Mst = st["R"], st["M"]
             for i, j in enumerate(todo):

@@ -12,6 +12,9 @@ custom-op boundaries, other PyTorch code):
     vfml::convex_upsample(flow, mask)                                    -> Tensor     K8 8x convex upsampling
     vfml::text_draw(frame, plan)                                         -> Tensor     text labels on a composed frame
     vfml::dwconv2d_nhwc(x, weight, bias, residual, act)                  -> Tensor     K6 depthwise k x k (SK update block)
+    vfml::layernorm_rows(x, gamma, beta, eps)                            -> Tensor     LayerNorm over rows (Twins-SVT encoders)
+    vfml::window_attention(qkv, pad_row, heads)                          -> Tensor     7 x 7 locally-grouped attention
+    vfml::attention_shared_keys(q, kv, heads)                            -> Tensor     attention against a frame's shared keys
 
 Only the CUDA (= HIP on ROCm) dispatch key has an implementation: on CPU tensors the dispatcher raises
 NotImplementedError - there is no CPU fallback, as everywhere in the engine.  Importing this module registers the ops
@@ -110,6 +113,36 @@ def _dwconv2d_nhwc(x, weight, bias, residual, act):
     return out
 
 
+def _layernorm_rows(x, gamma, beta, eps):
+    """x [rows, c] f32 (c % 8 == 0), gamma / beta [c] -> LayerNorm over each row (biased variance), [rows, c] f32."""
+    rows, c = x.shape
+    x = x.contiguous().float()
+    out = torch.empty_like(x)
+    hip.layernorm_rows(x.reshape(-1), c, out.reshape(-1), c, rows, c, gamma.contiguous().float(), beta.contiguous().float(), eps=eps)
+    return out
+
+
+def _window_attention(qkv, pad_row, heads):
+    """qkv [n,h,w,3c] f32 (q | k | v, c = heads * 32), pad_row [3c] (the q | k | v of a position outside the grid: not masked)
+    -> [n,h,w,c] f32: softmax(q k^T / sqrt 32) v per head over 7 x 7 windows anchored at (0, 0)."""
+    n, h, w, c3 = qkv.shape
+    c = c3 // 3
+    qkv = qkv.contiguous().float()
+    out = torch.empty(n, h, w, c, device=qkv.device, dtype=torch.float32)
+    hip.window_attention(qkv.reshape(-1), c3, n, h, w, c, heads, 7, pad_row.contiguous().float(), out.reshape(-1), c)
+    return out
+
+
+def _attention_shared_keys(q, kv, heads):
+    """q [n,p,c] f32 (c = heads * 32), kv [n,pk,2c] (k | v) -> [n,p,c] f32: per frame and head softmax(q k^T / sqrt 32) v."""
+    n, p, c = q.shape
+    pk = kv.shape[1]
+    q, kv = q.contiguous().float(), kv.contiguous().float()
+    out = torch.empty_like(q)
+    hip.attention_shared_keys(q.reshape(-1), c, kv.reshape(-1), 2 * c, n, p, pk, c, heads, out.reshape(-1), c)
+    return out
+
+
 def register():
     global _LIB
     if _LIB is not None:
@@ -121,6 +154,12 @@ def register():
     lib.define("convex_upsample(Tensor flow, Tensor mask) -> Tensor")
     lib.define("text_draw(Tensor frame, Tensor plan) -> Tensor")
     lib.define("dwconv2d_nhwc(Tensor x, Tensor weight, Tensor bias, bool residual, bool act) -> Tensor")
+    lib.define("layernorm_rows(Tensor x, Tensor gamma, Tensor beta, float eps) -> Tensor")
+    lib.define("window_attention(Tensor qkv, Tensor pad_row, int heads) -> Tensor")
+    lib.define("attention_shared_keys(Tensor q, Tensor kv, int heads) -> Tensor")
+    lib.impl("layernorm_rows", _layernorm_rows, "CUDA")
+    lib.impl("window_attention", _window_attention, "CUDA")
+    lib.impl("attention_shared_keys", _attention_shared_keys, "CUDA")
     lib.impl("conv2d_nhwc", _conv2d_nhwc, "CUDA")
     lib.impl("corr_volume", _corr_volume, "CUDA")
     lib.impl("corr_lookup", _corr_lookup, "CUDA")

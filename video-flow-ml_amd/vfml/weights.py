@@ -80,7 +80,7 @@ def _sk_spec(cfg):
     hid = cfg.feat_dim // 2
     ub = "update_block"
     blocks = {n: _pcblock_spec(n, ci, co, k) for n, ci, co, k in sk_blocks(cfg)}
-    s = _encoder_spec("fnet", cfg.feat_dim) + _encoder_spec("cnet", cfg.feat_dim)
+    s = _encoders_spec(cfg)
     s += blocks[f"{ub}.encoder.convc1"] + blocks[f"{ub}.encoder.convc2"]
     s += [(f"{ub}.encoder.convf1", 128, 4, 1, 1)]
     s += blocks[f"{ub}.encoder.convf2"] + blocks[f"{ub}.encoder.conv"]
@@ -92,14 +92,60 @@ def _sk_spec(cfg):
     return s
 
 
+# The Twins-SVT encoders (cfg.twins; DESIGN.md section 17): timm's twins_svt_large cut to two stages, `<prefix>.svt.*`.  The
+# first patch embedding of fnet names the family in a checkpoint.
+TWINS_KEY = "fnet.svt.patch_embeds.0.proj.weight"
+TWINS_WS = 7                                      # window of the locally-grouped attention
+# per stage: (patch, channels in, channels, heads, reduction of the sub-sampled attention)
+TWINS_STAGES = ((4, 3, 128, 4, 8), (2, 128, 256, 8, 4))
+TWINS_FINAL_NORM = 1024                           # timm's final norm of the four-stage backbone: carried, loaded, unused
+TWINS_LN_SEEDED = ((0.75, 1.25), (-0.1, 0.1))     # seeded LayerNorm weight / bias ranges (PyTorch's 1 / 0 would test nothing)
+
+
+def twins_encoder_spec(prefix):
+    """[(name, kind, weight shape)] of one Twins-SVT encoder in state-dict order; every entry has a bias of shape[0] values.
+    kind: "conv" (Conv2d, kernel = stride), "linear", "dw" (depthwise 3 x 3) or "ln" (LayerNorm weight and bias)."""
+    sv = f"{prefix}.svt"
+    s = []
+    for i, (p, cin, c, _, _) in enumerate(TWINS_STAGES):
+        s += [(f"{sv}.patch_embeds.{i}.proj", "conv", (c, cin, p, p)), (f"{sv}.patch_embeds.{i}.norm", "ln", (c,))]
+    for i, (_, _, c, _, sr) in enumerate(TWINS_STAGES):
+        b = f"{sv}.blocks.{i}.0"
+        s += [(f"{b}.norm1", "ln", (c,)), (f"{b}.attn.qkv", "linear", (3 * c, c)), (f"{b}.attn.proj", "linear", (c, c)),
+              (f"{b}.norm2", "ln", (c,)), (f"{b}.mlp.fc1", "linear", (4 * c, c)), (f"{b}.mlp.fc2", "linear", (c, 4 * c))]
+        b = f"{sv}.blocks.{i}.1"
+        s += [(f"{b}.norm1", "ln", (c,)), (f"{b}.attn.q", "linear", (c, c)), (f"{b}.attn.kv", "linear", (2 * c, c)),
+              (f"{b}.attn.proj", "linear", (c, c)), (f"{b}.attn.sr", "conv", (c, c, sr, sr)), (f"{b}.attn.norm", "ln", (c,)),
+              (f"{b}.norm2", "ln", (c,)), (f"{b}.mlp.fc1", "linear", (4 * c, c)), (f"{b}.mlp.fc2", "linear", (c, 4 * c))]
+    for i, (_, _, c, _, _) in enumerate(TWINS_STAGES):
+        s.append((f"{sv}.pos_block.{i}.proj.0", "dw", (c, 1, 3, 3)))
+    s.append((f"{sv}.norm", "ln", (TWINS_FINAL_NORM,)))
+    return s
+
+
+def twins_spec(cfg):
+    """The non-BasicEncoder parameters of a cfg.twins network: both encoders' tables (empty without cfg.twins)."""
+    if not getattr(cfg, "twins", False):
+        return []
+    return twins_encoder_spec("fnet") + twins_encoder_spec("cnet")
+
+
+def _encoders_spec(cfg):
+    """The two BasicEncoders' convolutions - none with cfg.twins, whose encoders are twins_spec's."""
+    if getattr(cfg, "twins", False):
+        return []
+    return _encoder_spec("fnet", cfg.feat_dim) + _encoder_spec("cnet", cfg.feat_dim)
+
+
 def conv_spec(cfg):
     """[(name, cout, cin, kh, kw)] for every convolution, in state-dict order (checkpoint shapes: the
-    correlation input is always the base 4-level radius-4 lookup).  cfg.sk: the SK update block's table (_sk_spec)."""
+    correlation input is always the base 4-level radius-4 lookup).  cfg.sk: the SK update block's table (_sk_spec).
+    cfg.twins: without the encoders' convolutions - twins_spec lists the Twins-SVT encoders' parameters, which come first."""
     if getattr(cfg, "sk", False):
         return _sk_spec(cfg)
     cor = BASE_CORR_LEVELS * (2 * BASE_CORR_RADIUS + 1) ** 2
     hid = cfg.feat_dim // 2
-    s = _encoder_spec("fnet", cfg.feat_dim) + _encoder_spec("cnet", cfg.feat_dim)
+    s = _encoders_spec(cfg)
     ub = "update_block"
     s += [
         (f"{ub}.encoder.convc1", 256, 2 * cor, 1, 1),
@@ -137,6 +183,17 @@ def seeded_state_dict(cfg, seed=0):
     is k * k: its bound is 1 / k, PyTorch's default for a grouped convolution.)"""
     g = torch.Generator().manual_seed(seed)
     sd = {}
+    for name, kind, shape in twins_spec(cfg):
+        # Linear and convolution weights by the same rule (fan-in = the weight's other dimensions); LayerNorm weights and
+        # biases from TWINS_LN_SEEDED
+        if kind == "ln":
+            (w0, w1), (b0, b1) = TWINS_LN_SEEDED
+            sd[f"{name}.weight"] = w0 + (w1 - w0) * torch.rand(shape, generator=g)
+            sd[f"{name}.bias"] = b0 + (b1 - b0) * torch.rand(shape, generator=g)
+            continue
+        bound = 1.0 / math.sqrt(math.prod(shape[1:]))
+        sd[f"{name}.weight"] = (torch.rand(shape, generator=g) * 2 - 1) * bound
+        sd[f"{name}.bias"] = (torch.rand(shape[0], generator=g) * 2 - 1) * bound
     for name, cout, cin, kh, kw in conv_spec(cfg):
         bound = 1.0 / math.sqrt(cin * kh * kw)
         sd[f"{name}.weight"] = (torch.rand(cout, cin, kh, kw, generator=g) * 2 - 1) * bound
@@ -149,9 +206,10 @@ def seeded_state_dict(cfg, seed=0):
 
 def load_checked(model, state, what):
     """Strict `load_state_dict` (reference processing/videoflow_core.py:110) with an error that names what does not
-    fit: the engine hard-codes the RAFT BasicEncoder key layout (`fnet.conv1`, `fnet.layer1.0.conv1`, ...), while the
-    released MOF / BOF configurations select Twins-SVT encoders (`fnet.svt.*`) - such a checkpoint
-    is refused with its unexpected key FAMILIES listed instead of hundreds of raw keys.  The GMA aggregator's keys
+    fit, its unexpected key FAMILIES listed instead of hundreds of raw keys.  The encoders are the RAFT BasicEncoder
+    (`fnet.conv1`, `fnet.layer1.0.conv1`, ...) or, with cfg.twins - which VideoFlowCore.load_model sets from the checkpoint -
+    the Twins-SVT encoders cut to two stages that the released MOF / BOF configurations select (`fnet.svt.*`, SURVEY.md
+    App. A); a full four-stage backbone (`svt.patch_embeds.2`, ...) is refused.  The GMA aggregator's keys
     (`att.to_qk`, `update_block.aggregator.*`) belong to the network when cfg.gma is set, which VideoFlowCore.load_model
     does from the checkpoint: they are named as unexpected only for a network built without it; the SK update block's
     keys (`update_block.*.conv_list.*`, `.ffn1.*`, `.pw`, `.ffn2.*`) likewise with cfg.sk.  Numerical parity with the
@@ -167,10 +225,11 @@ def load_checked(model, state, what):
                 fam[f] = fam.get(f, 0) + 1
             return ", ".join(f"{f} ({n})" for f, n in sorted(fam.items())) or "none"
         raise RuntimeError(
-            f"{what}: checkpoint does not match the network this engine builds (CNN BasicEncoder fnet/cnet, "
+            f"{what}: checkpoint does not match the network this engine builds ({'Twins-SVT (two stages)' if TWINS_KEY in want else 'CNN BasicEncoder'} fnet/cnet, "
             f"{'SK' if SK_KEY in want else 'SepConvGRU'} update block{', GMA aggregator' if GMA_GAMMA in want else ''}).  Unexpected key families: {families(have - want)}.  Missing key families: "
-            f"{families(want - have)}.  Checkpoints of the upstream Twins-SVT configurations (fnet.svt.* / cnet.svt.*) "
-            f"are the one family that is not supported; the GMA aggregator (att.to_qk, update_block.aggregator.*) is, "
+            f"{families(want - have)}.  A full four-stage timm Twins-SVT backbone (svt.patch_embeds.2, svt.blocks.2, ...) "
+            f"is the one family that is not supported; Twins-SVT encoders cut to two stages (fnet.svt.* / cnet.svt.*) are, "
+            f"through cfg.twins; the GMA aggregator (att.to_qk, update_block.aggregator.*) is, "
             f"through cfg.gma, and the SK update block (update_block.*.conv_list.*) is, through cfg.sk.")
     bad = [f"{k}: checkpoint {tuple(state[k].shape)} vs network {tuple(v.shape)}"
            for k, v in model.state_dict().items() if tuple(state[k].shape) != tuple(v.shape)]
