@@ -33,7 +33,8 @@ extern "C" {
  * same way: additions only, and the four entry points they generalise forward to them with VFML_JPEG_420; and likewise
  * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well; and likewise
  * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows.  27 adds vfml_conv2d_split_variant_at; it also covers
- * vfml_layernorm_rows, vfml_window_attention and vfml_attention_shared_keys (the Twins-SVT encoders): additions only. */
+ * vfml_layernorm_rows, vfml_window_attention and vfml_attention_shared_keys (the Twins-SVT encoders): additions only;
+ * and vfml_attention_bank_planes_f16 and vfml_axpy_f32 (MemFlow's memory bank), additions as well. */
 #define VFML_ABI_VERSION 27
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -230,6 +231,26 @@ int vfml_softmax_rows_f16(const float* x, int64_t rows, int cols, int64_t ld_in,
 int64_t vfml_attention_plane_workspace_bytes(int p);
 int vfml_attention_plane_f16(const float* q, int64_t ld_q, const float* k, int64_t ld_k, int p, int d, float score_scale,
                              float prob_scale, void* plane, int64_t ld_plane, void* workspace, void* stream);
+
+/* The bank form of the call above (MemFlow's memory): the p queries of one frame against n_seg key
+ * sets of p rows each - the keys of earlier fields and the frame's own -, the softmax taken JOINTLY over all n_seg * p
+ * columns, written as n_seg planes:
+ *   planes[s][i][j] = RTN_f16(prob_scale * exp(t_isj) / sum_{s', j'} exp(t_is'j')),  t_isj = score_scale * q_i . keys[s]_j,
+ * columns p .. ld_plane-1 of every plane zero.  keys / planes: HOST arrays of n_seg device pointers (copied into the
+ * launch: they may be freed when the call returns); every key set f32 rows [p][d] of the common row stride ld_k
+ * (ld_k % 4 == 0, 16-byte aligned), every plane [p][ld_plane] f16 (ld_plane % 64 == 0, p <= ld_plane <= 32768, 16-byte
+ * aligned; offsets into a plane are computed in 64 bits).  1 <= n_seg <= 9.  Arithmetic, operand domain (|x| < 4094), d = 128,
+ * prob_scale and the workspace (vfml_attention_plane_workspace_bytes(p): every row's joint maximum and sum) as above; a
+ * set's last key tile is partial whenever p % 64 != 0 and its dead keys count as -inf.  With n_seg = 1 the plane is the one
+ * vfml_attention_plane_f16 writes, bit for bit (tests/test_gpu_memflow_memory.py).  Stream-ordered, no host
+ * synchronisation; a bad argument returns non-zero with vfml_last_error set and launches nothing. */
+int vfml_attention_bank_planes_f16(const float* q, int64_t ld_q, const float* const* keys, int64_t ld_k, int n_seg, int p, int d,
+                                   float score_scale, float prob_scale, void* const* planes, int64_t ld_plane, void* workspace,
+                                   void* stream);
+
+/* y += scale * x over n floats (n % 4 == 0, both 16-byte aligned, no overlap): the memory part of MemFlow's read-out is
+ * summed over the bank's planes, and added to every iteration's own, with it. */
+int vfml_axpy_f32(const float* x, float* y, int64_t n, float scale, void* stream);
 
 /* src f32 [rows][c] (row stride ld) -> SPLIT ROWS of its transpose times scale: dst[c][ld_dst] (VFML_FMT_S16, ld_dst =
  * rows rounded up to 32, pad channels zero): the activation operand of out^T = V^T . A^T. */

@@ -42,7 +42,7 @@ from processing.flow_inference import VideoFlowInference
 from processing.memflow_inference import MemFlowInference
 from storage import AsyncFlowCacheWriter, FlowCacheManager
 from vfml import dist as vdist
-from vfml.runner import ClipFeeder, run_sharded
+from vfml.runner import ClipFeeder, check_memory_job, run_sharded
 from video.frame_extractor import fast_mode_dimensions, resize_frame
 from video.video_info import (SYNTHETIC_FPS, own_avi_reader, probe_video, read_frames, time_to_frame,
                               validate_frame_range)
@@ -379,6 +379,22 @@ def mjpg_sampling():
     return value
 
 
+# Fields of earlier frames whose keys and values a MemFlow field reads: 0, every field with an empty
+# memory bank, as the reference runs it; 1..8, a job walks its frames in order through one stream with a bank of that many
+# entries (one GPU, whole frames; the cache directory carries _mem{N}).  The environment variable VFML_MEMFLOW_MEMORY
+# overrides it.  No command-line flag: the parser stays the reference's.
+MEMFLOW_MEMORY = 0
+
+
+def memflow_memory():
+    """MEMFLOW_MEMORY, or VFML_MEMFLOW_MEMORY when it is set: an integer 0..8; anything else is refused."""
+    from vfml.memflow_net import check_memory_frames
+    env = os.environ.get("VFML_MEMFLOW_MEMORY")
+    if env:
+        return check_memory_frames(env, "VFML_MEMFLOW_MEMORY")
+    return check_memory_frames(MEMFLOW_MEMORY, "flow_processor.MEMFLOW_MEMORY")
+
+
 # True: the output video carries the reference's text labels, drawn with the project's own text (DESIGN.md section 9,
 # "Text"): vfml_text_draw behind the composer on the device path, visualization/text.py under --device cpu.  The
 # environment variable VFML_LABELS=1|0 overrides it.  Off: the fixtures cut from the reference and the render tests pin
@@ -634,6 +650,14 @@ def main(argv=None):
         check_flow_input(args)
     mjpg_sampling()             # a setting that is not built is refused before anything is computed or rendered
     draw_labels()               # (likewise VFML_LABELS)
+    memory = memflow_memory()   # (likewise VFML_MEMFLOW_MEMORY)
+    if args.model != 'memflow':
+        memory = 0
+    try:
+        check_memory_job(memory, bool(args.tile), world)
+    except ValueError as e:
+        log(f"Error: {e}")
+        return 1
     if not (args.input.startswith('synthetic:') or os.path.exists(args.input)):
         log(f"Error: Input video not found: {args.input}")
         return 1
@@ -664,7 +688,7 @@ def main(argv=None):
     memflow = args.model == 'memflow'
     cache_dir = args.use_flow_cache or mgr.generate_cache_path(
         cache_src, start, n, args.sequence_length, args.fast, args.tile, args.model,
-        args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant)
+        args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant, memory_frames=memory)
     complete, fmt, missing = mgr.check_cache_exists(cache_dir, n)
     if complete and not args.force_recompute:
         if args.interactive:
@@ -677,7 +701,7 @@ def main(argv=None):
 
     if memflow:     # reference flow_processor.py:64-75: model path defaults to MemFlow_ckpt/MemFlowNet_{stage}.pth
         eng = MemFlowInference(device, args.model_path or f"MemFlow_ckpt/MemFlowNet_{args.stage}.pth", args.stage,
-                               args.sequence_length)
+                               args.sequence_length, memory_frames=memory)
     else:
         eng = VideoFlowInference(device, args.fast, args.tile, args.sequence_length, args.vf_dataset,
                                  args.vf_architecture, args.vf_variant)

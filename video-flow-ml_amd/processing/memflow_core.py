@@ -14,12 +14,14 @@ from typing import Dict
 import torch
 
 from vfml import InputPadder
-from vfml.memflow_net import build_memflow_network, memflow_cfg
+from vfml.memflow_net import build_memflow_network, check_memory_frames, memflow_cfg
 from vfml.weights import load_checked
 
 
 class MemFlowCore:
-    def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel'):
+    def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel', memory_frames=0):
+        self.memory_frames = check_memory_frames(memory_frames)      # bank capacity of step_stream (an extension)
+        self._stream = None
         self.device = self._validate_device(device)
         self.model_path = model_path
         self.stage = stage
@@ -118,6 +120,42 @@ class MemFlowCore:
                 keys = [(k, mode, tuple(x.shape[-2:])) for k in frame_keys]
             _, flows = self.model.forward_pairs(x, None, frame_keys=keys)
             return padder.unpad(flows)
+
+    @property
+    def stream(self):
+        """The open stream (None before the first open_stream / step_stream): its bank and planes, for callers that report."""
+        return self._stream
+
+    def open_stream(self):
+        """A fresh stream of fields in frame order with a bank of `memory_frames` entries (vfml.memflow_net.MemFlowStream;
+        upstream's InferenceCore): the fields of step_stream read the keys and values of the fields before them.  The
+        padder is fixed by the stream's first pair."""
+        if self.model is None:
+            raise RuntimeError("Model not loaded. Call load_model() first.")
+        self._stream = self.model.stream(self.memory_frames)
+        self._stream_padder = None
+        return self._stream
+
+    def step_stream(self, frames_tensor, mode, frame_keys=None, end=False):
+        """[1,2,3,H,W] raw frame values on the device (previous, current), normalised by branch `mode` of the range heuristic:
+        the next field of the open stream -> flow [2,H,W] on the device.  Normalised and padded as compute_pair_flows does."""
+        if self._stream is None:
+            self.open_stream()
+        with torch.no_grad():
+            x = self.normalise_as(frames_tensor.to(self.device).float(), mode)
+            size = tuple(x.shape[-2:])
+            if self._stream_padder is None:
+                self._stream_padder = (size, InputPadder(x.shape))
+            if self._stream_padder[0] != size:
+                raise ValueError(f"the stream was opened on {self._stream_padder[0]} frames, this pair is {size}: "
+                                 f"open a new stream for a clip of another size")
+            padder = self._stream_padder[1]
+            x = padder.pad(x)
+            keys = None
+            if frame_keys is not None:
+                keys = [(k, mode, tuple(x.shape[-2:])) for k in frame_keys]
+            _, flow = self._stream.step(x, end=end, frame_keys=keys)
+            return padder.unpad(flow)[0]
 
     def compute_flow_from_tensor(self, frames_tensor: torch.Tensor, keep_on_device: bool = False,
                                  frame_keys=None) -> torch.Tensor:

@@ -14,12 +14,14 @@ from .memflow_core import MemFlowCore
 
 class MemFlowProcessor:
     def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel',
-                 sequence_length=3):
+                 sequence_length=3, memory_frames=0):
         self.device = device
         self.model_path = model_path
         self.stage = stage
         self.sequence_length = max(2, sequence_length)
-        self.core_engine = MemFlowCore(device=device, model_path=model_path, stage=stage)
+        self.core_engine = MemFlowCore(device=device, model_path=model_path, stage=stage, memory_frames=memory_frames)
+        self.memory_frames = self.core_engine.memory_frames     # above 0: job loops walk one stream (an extension)
+        self._stream_at = None           # (clip token, frame) of the stream's last field
         print("MemFlow Processor initialized:")
         print(f"  Sequence length: {self.sequence_length} frames")
         print("  Note: MemFlow processes frame pairs (last 2 frames of sequence)")
@@ -63,6 +65,8 @@ class MemFlowProcessor:
         return torch.stack(planes, dim=0).unsqueeze(0)
 
     def compute_optical_flow(self, frames: List[np.ndarray], frame_idx: int) -> np.ndarray:
+        """Random access (the visualiser's call): one field with an empty memory bank, whatever `memory_frames` is - the bank
+        belongs to a job that walks the frames in order (compute_optical_flow_stream)."""
         flow = self.core_engine.compute_flow_from_tensor(self.prepare_frame_sequence(frames, frame_idx))
         return flow.permute(1, 2, 0).numpy()
 
@@ -137,6 +141,33 @@ class MemFlowProcessor:
                 flows = self.core_engine.compute_pair_flows(x, mode_of(i), frame_keys=keys)
                 out.extend(flows[j].permute(1, 2, 0) for j in range(flows.shape[0]))
             k = e + 1
+        return out
+
+    def begin_stream_job(self):
+        """A job starts with an empty bank at its first frame."""
+        self._stream_at = None
+
+    def compute_optical_flow_stream(self, clip, frame_idxs):
+        """Fields of frames of a resident clip IN FRAME ORDER through one stream with a bank of `memory_frames` entries ->
+        list of device tensors [H,W,2].  Field i is the pair (i-1, i) - frame 0 the pair (0, 0) - and reads the keys and
+        values of the fields before it, so fields are not batched (field t needs field t-1's value map).  The stream carries
+        over from one call to the next while the frames stay consecutive in one clip; anything else - begin_stream_job(),
+        another clip, a gap, a step back - starts from an empty bank."""
+        from vfml.clip_id import clip_token
+        from vfml.network import take_frames
+        core = self.core_engine
+        mx = self._frame_maxima(clip)
+        tok = clip_token(clip)
+        out = []
+        for i in frame_idxs:
+            if self._stream_at != (tok, i - 1) or core._stream is None:
+                core.open_stream()
+            ids = [max(0, i - 1), i]
+            m = max(mx[j] for j in self.window_indices(i))
+            mode = 0 if m > 2.0 else (1 if m > 1.0 else 2)
+            x = take_frames(clip, ids).permute(0, 3, 1, 2).float().unsqueeze(0)
+            out.append(core.step_stream(x, mode, frame_keys=[(tok, j) for j in ids]).permute(1, 2, 0))
+            self._stream_at = (tok, i)
         return out
 
     def compute_optical_flow_with_progress(self, frames, frame_idx, tile_pbar=None) -> np.ndarray:

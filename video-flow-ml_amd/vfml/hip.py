@@ -137,6 +137,9 @@ def lib():
     L.vfml_attention_plane_workspace_bytes.argtypes = [c_int]
     L.vfml_attention_plane_f16.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_float, c_float, c_void_p, c_int64,
                                            c_void_p, c_void_p]
+    L.vfml_attention_bank_planes_f16.argtypes = [c_void_p, c_int64, POINTER(c_void_p), c_int64, c_int, c_int, c_int, c_float, c_float,
+                                                 POINTER(c_void_p), c_int64, c_void_p, c_void_p]
+    L.vfml_axpy_f32.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p]
     L.vfml_dwconv2d.argtypes = [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int,
                                 c_int, c_void_p]
     L.vfml_gelu_rows.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p]
@@ -244,7 +247,7 @@ def lib():
 
 
 EXPORTS = [
-    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
+    "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_attention_bank_planes_f16", "vfml_axpy_f32", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
@@ -579,6 +582,40 @@ def attention_plane(q, k, p, plane, score_scale=None, d=128, ld_q=None, ld_k=Non
                                           float(score_scale if score_scale is not None else 1.0 / d ** 0.5), plane.scale,
                                           c_void_p(plane.hi.data_ptr()), plane.kp, c_void_p(workspace.data_ptr()), _stream()),
            "vfml_attention_plane_f16")
+
+
+ATT_BANK_MAX = 9        # key sets of one vfml_attention_bank_planes_f16 call
+
+
+def attention_bank_planes(q, keys, p, planes, score_scale=None, d=128, ld_q=None, ld_k=None, q_off=0, k_offs=None,
+                          workspace=None):
+    """planes[s] (PlainWeights [p][kp] of one kp and one scale) = scale * the columns of key set s of the softmax taken JOINTLY
+    over all len(keys) * p scores of every query: q f32 rows [p][d] against keys[s], f32 rows [p][d] of the common stride ld_k
+    (float offsets q_off / k_offs[s]), in one call (vfml_attention_bank_planes_f16; the scores never reach memory).
+    score_scale: 1 / sqrt(d) unless given.  workspace: a float32 device tensor of at least 2 p elements."""
+    n = len(keys)
+    if len(planes) != n or not all(isinstance(a, PlainWeight) for a in planes):
+        raise ValueError("attention_bank_planes: one PlainWeight per key set")
+    if n and any(a.kp != planes[0].kp or a.scale != planes[0].scale or a.rows < p for a in planes):
+        raise ValueError("attention_bank_planes: planes of one row stride and one scale, at least p rows each")
+    dev = planes[0].hi.device if n else q.device
+    if workspace is None:
+        workspace = torch.empty(max(1, attention_plane_workspace_bytes(p) // 4), dtype=torch.float32, device=dev)
+    if workspace.dtype != torch.float32 or workspace.numel() * 4 < attention_plane_workspace_bytes(p):
+        raise ValueError("attention_bank_planes: workspace of 2 p floats")
+    k_offs = k_offs or [0] * n
+    kptr = (c_void_p * max(1, n))(*[_dev(k).data_ptr() + 4 * o for k, o in zip(keys, k_offs)])
+    pptr = (c_void_p * max(1, n))(*[a.hi.data_ptr() for a in planes])
+    _check(lib().vfml_attention_bank_planes_f16(_ptr(_dev(q), q_off), ld_q or d, kptr, ld_k or d, n, p, d,
+                                                float(score_scale if score_scale is not None else 1.0 / d ** 0.5),
+                                                planes[0].scale if n else 1.0, pptr, planes[0].kp if n else 0,
+                                                c_void_p(workspace.data_ptr()), _stream()),
+           "vfml_attention_bank_planes_f16")
+
+
+def axpy_f32(x, y, n, scale=1.0, x_off=0, y_off=0):
+    """y += scale * x over n floats (vfml_axpy_f32)."""
+    _check(lib().vfml_axpy_f32(_ptr(_dev(x), x_off), _ptr(_dev(y), y_off), n, float(scale), _stream()), "vfml_axpy_f32")
 
 
 DW_RESIDUAL, DW_GELU = 1, 2      # flags of vfml_dwconv2d (include/vfml.h)

@@ -11,7 +11,12 @@ MI355X shape of the read-out: q and k come from the context features and do not 
 iterations, so the P x P attention matrix is computed ONCE per field, kept resident in HBM as
 split-row halves (4.2 GB at 1080p; no flash-style re-computation needed with 288 GB), and every
 iteration is one long-K GEMM  attn[P,P] . v[P,128]  on the MFMA kernel with the residual add fused.
+
+MemFlowStream (below) is the bank that is not empty: fields in frame order, each reading the keys and
+values of up to `memory_frames` fields before it; with none held a step is forward() launch for launch.
 """
+import weakref
+
 import torch
 import torch.nn as nn
 
@@ -84,10 +89,13 @@ class MemFlowNetHIP(MOFNetHIP):
         self._pyr_free = []
         self._att_planes = {}            # attention matrices as plain f16 planes (hip.PlainWeight), per pair of a pass
         self._feat_cache = collections.OrderedDict()
+        self._streams = weakref.WeakSet()    # the MemFlowStreams on this network: release_workspace drops their planes
 
     def release_workspace(self):
         super().release_workspace()
         self._att_planes.clear()
+        for st in list(self._streams):
+            st._planes.clear()
 
     # ------------------------------------------------------------------ weights
     def _pack(self, device):
@@ -140,6 +148,15 @@ class MemFlowNetHIP(MOFNetHIP):
         fields of a job in one pass (every pair its own fresh-memory step, exactly as B separate calls; at
         1080p one pair leaves most tiles of the update-block convolutions' last round empty).
         Returns (flow_low [B,2,h,w], flow [B,2,H,W])."""
+        return self._run_pairs(frames, frame_keys, None)
+
+    def stream(self, memory_frames=0):
+        """A stream of fields in frame order that carries the memory bank (MemFlowStream)."""
+        return MemFlowStream(self, memory_frames)
+
+    def _run_pairs(self, frames, frame_keys, mem):
+        """forward_pairs; mem: the MemFlowStream whose bank this (single) pair reads and, after its last iteration, joins -
+        with no entry held the launches are forward_pairs' own."""
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise RuntimeError("MemFlowNetHIP runs on an MI355X (HIP) device only; got "
                                f"{getattr(frames, 'device', type(frames))}. There is no CPU fallback in the shipped engine.")
@@ -158,6 +175,14 @@ class MemFlowNetHIP(MOFNetHIP):
         dev = src.device
         Pn = h * w
         MP = B * Pn
+        P8, ldA, plain = self._attention_geometry(Pn)
+        if mem is not None and mem.memory_frames and not (ATT_PLAIN and plain):       # before anything is launched
+            if not ATT_PLAIN:
+                raise ValueError("the memory bank needs the plane form of the attention, which memflow_net.ATT_PLAIN = False "
+                                 "switches off")
+            raise ValueError(f"the memory bank needs the plane form of the attention (P >= 1024 cells, P % 4 == 0, a plane "
+                             f"below 2 GiB, row stride <= 32768): {H}x{W} has P = {Pn}")
+        plain = ATT_PLAIN and plain
         P = self._pack(dev)
         if self._precision() != "f16x3":
             raise ValueError("the MemFlow path is built on the split-f16 kernels: cfg.precision must be 'f16x3'")
@@ -206,25 +231,37 @@ class MemFlowNetHIP(MOFNetHIP):
             # memory read-out operator: attn = softmax(q k^T / sqrt(d)), P x P per pair, once per field
             qmap = self._buf("att_q", MP * AD, dev)
             kmap = self._buf("att_k", MP * AD, dev)
+            bank = mem.entries if mem is not None else ()
             wgt, b = P["query"]
-            hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, qmap, AD, in0_off=INP, in_fmt=AF, out_fmt=AF)
+            if bank:       # the bank form takes q as f32 rows (csrc/attention.hip)
+                hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, qmap, AD, in0_off=INP, in_fmt=AF)
+            else:
+                hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, qmap, AD, in0_off=INP, in_fmt=AF, out_fmt=AF)
             wgt, b = P["key"]
             hip.conv2d(G, 128, GLD, B, h, w, wgt, b, AD, 1, 1, kmap, AD, in0_off=INP, in_fmt=AF)
             # probabilities as ONE f16 each (round to nearest, times ATT_SCALE): 2^-12 relative per probability, unbiased -
             # the 1080p EPE does not move (tests/test_gpu_memflow.py); else - small or odd frames - as split rows
             # (update_block.attention_readout has the two forms of the read-out)
-            P8, ldA, plain = self._attention_geometry(Pn)
-            plain = ATT_PLAIN and plain
-            scores = self._buf("att_scores", Pn * ldA, dev)
-            attn = []
-            for k in range(B):
+            attn, r_mem = [], None
+            if bank:
+                # [bank keys ..., k_t]: one joint softmax, one plane per key set (the stream's, kept across fields)
+                planes = mem._planes_for(len(bank) + 1, Pn, ldA, dev)
+                hip.attention_bank_planes(qmap, [e[0] for e in bank] + [kmap], Pn, planes, score_scale=1.0 / float(AD) ** 0.5,
+                                          d=AD, workspace=self._buf("att_stats", 2 * Pn, dev))
+                attn.append(planes[-1])
+            else:
+                scores = self._buf("att_scores", Pn * ldA, dev)
+            for k in range(0 if bank else B):
                 kw_ = hip.SplitWeight(Pn, AD, dev).fill(kmap, src_off=k * Pn * AD, scale=16.0)
                 hip.conv2d(qmap, AD, AD, 1, 1, Pn, kw_, None, Pn, 1, 1, scores, ldA, in0_off=k * Pn * AD,
                            out_scale=1.0 / float(AD) ** 0.5, in_fmt=AF)
                 if plain:
-                    a = self._att_planes.get(k)
-                    if a is None or a.rows != Pn or a.kp != ldA or a.hi.device != dev:
-                        a = self._att_planes[k] = hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE)
+                    if mem is not None and mem.memory_frames:
+                        a = mem._planes_for(1, Pn, ldA, dev)[0]  # a stream's memory-free field: into the stream's first plane
+                    else:
+                        a = self._att_planes.get(k)
+                        if a is None or a.rows != Pn or a.kp != ldA or a.hi.device != dev:
+                            a = self._att_planes[k] = hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE)
                     hip.softmax_rows_f16(scores, Pn, Pn, ldA, a)
                 else:
                     a = self._buf(f"att_probs{k}", Pn * ldA, dev)
@@ -233,6 +270,15 @@ class MemFlowNetHIP(MOFNetHIP):
             ro = update_block.readout_scratch(self._buf, dev, MP, Pn, AD, ldA, plain,
                                               None if plain else hip.SplitWeight(AD, P8, dev))
             gate_off = dict.fromkeys(gate_add, 0)
+            if bank:
+                # the bank's part of the read-out, sum_j A_j . V_j: the same for every iteration of the field
+                r_mem = self._buf("att_rmem", Pn * AD, dev)
+                for j, (_, vj) in enumerate(bank):
+                    update_block.plane_readout(s, planes[j], ldA, ro, vj)
+                    if j == 0:
+                        r_mem.copy_(ro.out_t)
+                    else:
+                        hip.axpy_f32(ro.out_t, r_mem, Pn * AD)
 
             update_block.init_coords(s, B)
             for it in range(cfg.decoder_depth):
@@ -243,10 +289,12 @@ class MemFlowNetHIP(MOFNetHIP):
                 update_block.encoder_conv(s, B, 0)
                 # value map and memory read-out  m_global = m + gamma * attn . v  (per pair: its own attention)
                 update_block.attention_readout(s, "update_block.value", attn, plain, ldA, P8, self._gamma, ATT_SCALE,
-                                               s.MF, s.MT, ro)
+                                               s.MF, s.MT, ro, addend=r_mem)
                 update_block.sep_conv_gru(s, B, gate_add, gate_off)
                 update_block.flow_head(s, B, cout=2)
 
+            if mem is not None and mem.memory_frames:
+                mem._take(kmap, ro.val, Pn * AD, (H, W))      # (k_t, the last iteration's value map) joins the bank
             mask = self._buf("mmask", MP * 576, dev)
             update_block.mask_head(s, B, mask, 576)
             up = torch.empty(B, H, W, 2, device=dev, dtype=torch.float32)
@@ -263,6 +311,86 @@ class MemFlowNetHIP(MOFNetHIP):
         ctx = torch.empty(B * Pn * 256, device=dev)
         self._encoder("cnet", frames, B, H, W, P, dev, ctx, 256, 0, hip.EPI_TANH_RELU, self.hidden_dim, out_fmt=AF)
         return ctx
+
+
+MEMORY_FRAMES_MAX = hip.ATT_BANK_MAX - 1       # bank entries: with the frame's own keys one hip.attention_bank_planes call
+
+
+def check_memory_frames(value, source="memory_frames"):
+    """The bank capacity as an integer 0..MEMORY_FRAMES_MAX; anything else is refused."""
+    text = str(value).strip() if isinstance(value, (int, str)) and not isinstance(value, bool) else ""
+    if not (text.isdigit() and int(text) <= MEMORY_FRAMES_MAX):
+        raise ValueError(f"{source} = {value!r}: the memory bank holds an integer 0..{MEMORY_FRAMES_MAX} of earlier fields")
+    return int(text)
+
+
+class MemFlowStream:
+    """The fields of a video in frame order, each reading the keys and values of the fields before it (DESIGN.md section
+    18; upstream's InferenceCore.step).  The bank holds up to `memory_frames` pairs (k_j, v_j), oldest first: a field's keys
+    as f32 rows and the value map of its last iteration, on the device.  With entries held the attention rows are the softmax
+    JOINTLY over the bank's keys and the frame's own, as one resident f16 plane per key set; the bank's part of the read-out
+    is computed once per field.  With none - the first field, memory_frames = 0, after end=True or reset() - a step is
+    net.forward on the pair, launch for launch."""
+
+    def __init__(self, net, memory_frames=0):
+        self.net = net
+        self.memory_frames = check_memory_frames(memory_frames)
+        self.entries = []            # [(k [Pn*AD] f32, v [Pn*AD] f32)], oldest first
+        self.size = None             # (H, W) of the entries
+        self.planes_in_use = 0       # planes the last step read: entries held before it + 1
+        self._planes = []            # hip.PlainWeight [Pn][ldA], kept across fields
+        self._spare = []             # an evicted entry's tensors, taken again by the next one
+        net._streams.add(self)
+
+    def reset(self):
+        self._spare += self.entries
+        self.entries = []
+        self.size = None
+
+    @property
+    def planes_held(self):
+        return len(self._planes)
+
+    @property
+    def plane_bytes(self):
+        return sum(a.hi.numel() * 2 for a in self._planes)
+
+    def _planes_for(self, n, Pn, ldA, dev):
+        ps = self._planes
+        if ps and (ps[0].rows != Pn or ps[0].kp != ldA or ps[0].hi.device != dev):
+            ps.clear()
+        while len(ps) < n:
+            ps.append(hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE))
+        return ps[:n]
+
+    def _take(self, k, v, n, size):
+        if self.entries and self.size != size:
+            raise ValueError(f"the bank holds fields of {self.size[0]}x{self.size[1]}, this one is {size[0]}x{size[1]}")
+        if len(self.entries) == self.memory_frames:
+            self._spare.append(self.entries.pop(0))
+        self._spare = [e for e in self._spare if e[0].numel() == n and e[0].device == k.device]
+        kk, vv = self._spare.pop() if self._spare else (torch.empty_like(k[:n]), torch.empty_like(v[:n]))
+        kk.copy_(k[:n])
+        vv.copy_(v[:n])
+        self.entries.append((kk, vv))
+        self.size = size
+
+    @torch.no_grad()
+    def step(self, pair, end=False, frame_keys=None):
+        """pair: float [1, 2, 3, H, W] in [-1, 1] on the GPU (previous, current), the next field of the stream.
+        Returns (flow_low [1,2,h,w], flow [1,2,H,W]).  end=True: the bank is cleared after the step."""
+        if not isinstance(pair, torch.Tensor) or pair.dim() != 5 or pair.shape[1] != 2:
+            raise ValueError(f"pair must be [1,2,3,H,W], got {tuple(getattr(pair, 'shape', ()))}")
+        size = (int(pair.shape[3]), int(pair.shape[4]))
+        if self.entries and self.size != size:
+            raise ValueError(f"the bank holds fields of {self.size[0]}x{self.size[1]}, this pair is {size[0]}x{size[1]}: "
+                             f"reset() the stream before a clip of another size")
+        n = len(self.entries)
+        out = self.net._run_pairs(pair, frame_keys, self)
+        self.planes_in_use = n + 1
+        if end:
+            self.reset()
+        return out
 
 
 def build_memflow_network(cfg):

@@ -214,11 +214,30 @@ class ClipFeeder:
         torch.cuda.current_stream(self.device).wait_event(last)    # (copies on one stream complete in order)
 
 
+def memory_frames(proc):
+    """Capacity of the processor's memory bank in job loops (MemFlowProcessor.memory_frames); 0: every field on its own."""
+    return int(getattr(proc, "memory_frames", 0) or 0)
+
+
+def check_memory_job(memory, tile_mode, world):
+    """What a job with a memory bank cannot be: tiled (the bank is a whole frame's), or whole frames over several ranks (each
+    rank's shard would start from an empty bank, and the fields would depend on the number of ranks)."""
+    if memory and tile_mode:
+        raise ValueError(f"MemFlow's memory bank (memory of {memory} fields) works on whole frames: --tile is not available "
+                         f"with it (MemFlow never tiles anyway)")
+    if memory and world > 1:
+        raise ValueError(f"MemFlow's memory bank (memory of {memory} fields) carries from field to field: a job over "
+                         f"{world} ranks would start every rank's shard from an empty bank; run it on one GPU")
+
+
 def _fields_in_order(proc, clip, frame_indices, before=None):
     """(position, field) for every frame, whole frames: a few fields per pass where the processor can batch
     them (the tri-frame network, compute_optical_flow_resident_batch), else one call per field."""
     batch = getattr(proc, "compute_optical_flow_resident_batch", None)
     step = (getattr(proc, "TRI_BATCH", None) or getattr(proc, "PAIR_BATCH", 1)) if batch is not None else 1
+    if memory_frames(proc):
+        # MemFlow with its memory bank: one stream in frame order, a field per pass (field t reads field t-1's value map)
+        batch, step = proc.compute_optical_flow_stream, 1
     for k0 in range(0, len(frame_indices), step):
         chunk = frame_indices[k0:k0 + step]
         if before is not None:
@@ -323,7 +342,7 @@ class _Unpacker(threading.Thread):
 
 def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, group=None, on_field=None,
                 collect=True, num_lods=0, chunk=None, feeder=None, prepare_only=False, local_sink=None, out=None,
-                device_npz=None):
+                device_npz=None, continue_stream=False):
     """Compute the flow field of every frame in `frame_indices` of the device-resident uint8 clip [F,H,W,3]
     (`clip` may be None when a ClipFeeder is given: its clip is used and fed as the job advances).
     Returns on rank 0 a float32 numpy array [len(frame_indices), H, W, 2] (None with collect=False, when the
@@ -342,7 +361,10 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     prepare_only: allocate the job's staging buffers (kept for later jobs of the same geometry) and return.
     out: optional result array (rank 0, with collect): float32 [len(frame_indices), H, W, 2], filled and returned instead of a
     fresh one - a caller that times the job hands in memory it has already touched (at 8 ranks x 41 fields/s the result
-    grows by 5 GB/s; first-touch page faults of a fresh array would be part of what is measured)."""
+    grows by 5 GB/s; first-touch page faults of a fresh array would be part of what is measured).
+    continue_stream (MemFlow with a memory bank): the job goes on where the processor's last one ended - its bank is kept while
+    the frames follow on in the same clip (MemFlowProcessor.compute_optical_flow_stream); otherwise a job starts with an
+    empty bank at its first frame."""
     frame_indices = list(frame_indices)
     if feeder is not None:
         clip = feeder.clip
@@ -350,6 +372,7 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     tiles = _tiles(proc, W, H, tile_mode)
     whole = len(tiles) == 1
     on_gpu = clip.is_cuda
+    check_memory_job(memory_frames(proc), not whole, world)
     local = local_sink is not None or device_npz is not None
     if local and (not whole or collect or on_field is not None):
         raise ValueError("local_sink applies to whole-frame jobs and replaces collect / on_field")
@@ -392,6 +415,8 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
             if on_gpu:
                 torch.cuda.synchronize(dev)
         return None
+    if memory_frames(proc) and not continue_stream:
+        proc.begin_stream_job()                             # (not before: preparing buffers leaves the bank alone)
     side = torch.cuda.Stream(device=dev) if on_gpu and sink_here else None
     seq = getattr(proc, "sequence_length", 1)
 

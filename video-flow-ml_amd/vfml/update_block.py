@@ -108,10 +108,21 @@ def readout_scratch(buf, dev, rows, Pn, AD, ldA, plain, vt=None):
     return ro
 
 
-def attention_readout(s, layer, planes, plain, ldA, P8, gamma, att_scale, src, dst, ro):
+def plane_readout(s, a, ldA, ro, val, val_off=0):
+    """ro.out_t [Pn][AD] = plane a . rows `val` (f32 [Pn][AD] from float offset val_off): the plain form's long-K GEMM."""
+    hip.transpose_to_s16(val, s.Pn, ro.AD, ro.AD, ro.vrows, ldA, scale=16.0, src_off=val_off)
+    hip.conv2d(ro.vrows, ldA, ldA, ro.AD, 1, 1, a, None, s.Pn, 1, 1, ro.out, ldA, out_scale=1.0 / 16.0,
+               in_fmt=s.AF, out_t=ro.out_t, ld_out_t=ro.AD, mfma=1, ksplit_ws=ro.ws)
+
+
+def attention_readout(s, layer, planes, plain, ldA, P8, gamma, att_scale, src, dst, ro, addend=None):
     """columns dst = columns src + gamma * attn . v,  v = `layer`(columns src), per frame with its own attention: planes[k]
     is frame k's P x P matrix of probabilities times att_scale, resident in HBM (4.2 GB at 1080p as split rows, 2.1 GB as a
-    plane), and every iteration is one long-K GEMM over it on the MFMA kernel."""
+    plane), and every iteration is one long-K GEMM over it on the MFMA kernel.
+    addend (plain form, one frame): f32 rows [Pn][AD] added to attn . v before the scaling - the part of a read-out that
+    does not change over the iterations (MemFlow's memory bank); None: no launch is added."""
+    if addend is not None and not (plain and len(planes) == 1):
+        raise ValueError("attention_readout: an addend needs the plane form and a single frame")
     # plain: the probabilities as ONE f16 each, the WEIGHT plane (hip.PlainWeight) of the GEMM  out^T = V^T . A^T  (V as plain
     # f16 too: one MFMA per product, 64-channel steps of hi halves); the read-out streams the matrix once per iteration and
     # is bound by its bytes.  Else split rows [Pn][ldA] of P8 columns, with the residual add fused.
@@ -120,9 +131,9 @@ def attention_readout(s, layer, planes, plain, ldA, P8, gamma, att_scale, src, d
     hip.conv2d(G, 128, GLD, n, s.h, s.w, wgt, b, AD, 1, 1, ro.val, AD, in0_off=src, in_fmt=AF, mfma=s.nm(layer))
     for k, a in enumerate(planes):
         if plain:
-            hip.transpose_to_s16(ro.val, Pn, AD, AD, ro.vrows, ldA, scale=16.0, src_off=k * Pn * AD)
-            hip.conv2d(ro.vrows, ldA, ldA, AD, 1, 1, a, None, Pn, 1, 1, ro.out, ldA, out_scale=1.0 / 16.0,
-                       in_fmt=AF, out_t=ro.out_t, ld_out_t=AD, mfma=1, ksplit_ws=ro.ws)
+            plane_readout(s, a, ldA, ro, ro.val, k * Pn * AD)
+            if addend is not None:
+                hip.axpy_f32(addend, ro.out_t, Pn * AD)
             hip.add_to_s16(ro.out_t, AD, G, GLD, G, GLD, Pn, AD, scale=gamma, aux_off=k * Pn * GLD + src,
                            out_off=k * Pn * GLD + dst)
         else:
