@@ -20,9 +20,10 @@ from oracle.memflow_oracle import CorrBlock, MemFlowNetOracle, coords_grid, upsa
 
 
 @torch.no_grad()
-def step(net, pair, bank, M):
+def step(net, pair, bank, M, alter=None):
     """One field.  net: a MemFlowNetOracle; pair [1, 2, 3, H, W] in [-1, 1]; bank: the list of (k [1,d,P], v [1,P,d]) this
-    field reads - and joins: it is updated in place.  Returns (flow_low [1,2,h,w], flow [1,2,H,W])."""
+    field reads - and joins: it is updated in place.  Returns (flow_low [1,2,h,w], flow [1,2,H,W]).  alter: a function
+    applied to the attention rows [1, P, (n + 1) P] before they are used (the mutants of tests/test_memflow_noise_cpu.py)."""
     cfg, ub = net.cfg, net.update_block
     B, _, _, H, W = pair.shape
     h, w = H // 8, W // 8
@@ -36,6 +37,8 @@ def step(net, pair, bank, M):
     held = list(bank) if M > 0 else []
     keys = torch.cat([e[0] for e in held] + [k], dim=2) if held else k
     attn = torch.softmax(torch.matmul(q, keys) / math.sqrt(cfg.att_dim), dim=-1)
+    if alter is not None:
+        attn = alter(attn)
     coords0 = coords_grid(B, h, w, pair.dtype)
     coords1 = coords0.clone()
     v = None
@@ -60,11 +63,11 @@ def step(net, pair, bank, M):
 class Stream:
     """The interface of vfml.memflow_net.MemFlowStream over step()."""
 
-    def __init__(self, net, memory_frames):
-        self.net, self.memory_frames, self.bank = net, memory_frames, []
+    def __init__(self, net, memory_frames, alter=None):
+        self.net, self.memory_frames, self.bank, self.alter = net, memory_frames, [], alter
 
     def step(self, pair, end=False):
-        out = step(self.net, pair, self.bank, self.memory_frames)
+        out = step(self.net, pair, self.bank, self.memory_frames, self.alter)
         if end:
             self.reset()
         return out

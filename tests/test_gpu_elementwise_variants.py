@@ -1,14 +1,16 @@
-"""Elementwise parity of the GMA, SK and BOF engines: tests/test_gpu_elementwise.py's scheme on the variants' own oracles.
+"""Elementwise parity of the GMA, SK, BOF and Twins engines: tests/test_gpu_elementwise.py's scheme on the variants' own
+oracles.
 
 The older field tests of these engines bound the MEAN end-point error alone (test_gpu_gma.py and the BOF test of
 test_gpu_e2e.py by 1e-3 px, test_gpu_sk.py by 8 N), and never look at the 1/8-resolution flows.  An aggregator that drops the
 last 8 keys of every attention row moves the 256 x 264 field by 6.5e-4 px in the mean - 246 N, and below 1e-3
 (tests/test_noise_floor.py::test_a_mean_bound_is_blind_to_eight_dropped_keys).  Here the engine's field and its 1/8-resolution
 flows are compared with the variant's oracle in float64 - tests/mof_gma_oracle.py, tests/mof_sk_oracle.py, oracle.mof_oracle
-for the plain update block on the BOF network - and every statistic of tests_support.error_stats / low_stats must stay within
-K times N, the same oracle's float32-against-float64 noise for the same input, weights and depth.  K is
-tests_support.K_OF's: 8 for 'f16x3', 4 for 'f32' (which only the plain update block accepts).  Nothing in a bound comes from
-the engine.
+for the plain update block on the BOF network, tests/mof_twins_oracle.py for a checkpoint with the Twins-SVT encoders (whose
+own field test in tests/test_gpu_twins.py holds three of its four cases by the mean alone) - and every statistic of
+tests_support.error_stats / low_stats must stay within K times N, the same oracle's float32-against-float64 noise for the same
+input, weights and depth.  K is tests_support.K_OF's: 8 for 'f16x3', 4 for 'f32' (which only the plain update block on the
+residual encoders accepts).  Nothing in a bound comes from the engine.
 
 The attention store's resident f16 plane rounds the probabilities to f16 at 2^14 on purpose; in float64 that rounding moves
 the 256 x 264 field by less than 0.1 N (test_noise_floor.py::test_plane_rounding_costs_less_than_the_noise_floor, which caps
@@ -37,6 +39,9 @@ def _builder(name):
     if name == "sk":
         import mof_sk_oracle as so
         return so
+    if name == "twins":
+        import mof_twins_oracle as to
+        return to
     from oracle import mof_oracle as mo
     return mo
 
@@ -49,8 +54,12 @@ VARIANTS = {
     "sk+bof": ({"sk": True, "network": "BOFNet"}, "sk", ts.DRIFT_KEY_SK),
     "sk+gma": ({"sk": True, "gma": True}, "sk", ts.DRIFT_KEY_SK),
     "bof": ({"network": "BOFNet"}, "plain", ts.DRIFT_KEY),
+    # the Twins-SVT encoders; mof_twins_oracle builds the update block the other switches name
+    "twins": ({"twins": True}, "twins", ts.DRIFT_KEY),
+    "twins+bof": ({"twins": True, "network": "BOFNet"}, "twins", ts.DRIFT_KEY),
+    "twins+sk+gma": ({"twins": True, "sk": True, "gma": True}, "twins", ts.DRIFT_KEY_SK),
 }
-PRECISIONS = {v: ("f16x3", "f32") if v == "bof" else ("f16x3",) for v in VARIANTS}     # GMA and SK refuse 'f32'
+PRECISIONS = {v: ("f16x3", "f32") if v == "bof" else ("f16x3",) for v in VARIANTS}     # GMA, SK and Twins refuse 'f32'
 
 # (variant, input kind, T, H, W, plain-f16 attention plane expected? (None: no attention)).  Cells per frame:
 #   256 x 264 = 32 x 33 = 1056: the resident f16 plane, row stride 1088, a ragged last key tile
@@ -65,11 +74,16 @@ FIELDS = [("gma", "randf", 5, 256, 264, True), ("gma", "randf", 3, 264, 264, Fal
           ("bof", "randf", 5, 128, 192, None), ("bof", "randf", 4, 136, 160, None),
           # uint8 frames of the synthetic clip through forward_u8, at each variant's smallest size
           ("gma", "clip", 3, 136, 152, False), ("gma+bof", "clip", 5, 256, 264, True), ("sk", "clip", 3, 136, 152, None),
-          ("sk+bof", "clip", 5, 136, 152, None), ("sk+gma", "clip", 3, 136, 152, False), ("bof", "clip", 4, 136, 160, None)]
+          ("sk+bof", "clip", 5, 136, 152, None), ("sk+gma", "clip", 3, 136, 152, False), ("bof", "clip", 4, 136, 160, None),
+          # Twins checkpoints at test_gpu_twins.py's own size (17 x 19 cells: ragged 7 x 7 windows both ways)
+          ("twins", "randf", 3, 136, 152, None), ("twins", "randf", 5, 136, 152, None),
+          ("twins+bof", "randf", 5, 136, 152, None), ("twins+sk+gma", "randf", 3, 136, 152, False),
+          ("twins", "clip", 3, 136, 152, None)]
 CASES = [f + (p,) for f in FIELDS for p in PRECISIONS[f[0]]]
 # large flow: (variant, T, H, W, plane?) x drift c; about 4 and 8 cells at depth 4 (test_noise_floor.py asserts it)
 LARGE = [f + (c, p) for f in (("gma", "randf", 5, 256, 264, True), ("sk", "randf", 3, 136, 152, None),
-                              ("bof", "randf", 5, 128, 192, None)) for c in (1, 2) for p in PRECISIONS[f[0]]]
+                              ("bof", "randf", 5, 128, 192, None), ("twins", "randf", 3, 136, 152, None))
+         for c in (1, 2) for p in PRECISIONS[f[0]]]
 
 
 def _id(case):

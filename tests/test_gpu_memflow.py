@@ -1,5 +1,8 @@
 """MemFlow pair path (BASELINE config C4) against its CPU oracle, and the new
-entry points it needs (row softmax into split rows, transposed split planes, residual-add epilogue)."""
+entry points it needs (row softmax into split rows, transposed split planes, residual-add epilogue).
+
+The field tests here bound the MEAN end-point error against the float32 oracle; every statistic of the field and of the
+1/8-resolution flow, against the float64 oracle and at the oracle's own noise level, is tests/test_gpu_elementwise_memflow.py's."""
 import math
 import os
 
@@ -29,6 +32,8 @@ def _pair(seed=0, **over):
 
 @pytest.mark.parametrize("precision", ["f16x3"])
 def test_memflow_forward_matches_oracle(gpu, precision):
+    """Depth 12, 128 x 192: the mean within the contract, the 1/8-resolution flow by its maximum.  Elementwise, per statistic and
+    at every attention form: tests/test_gpu_elementwise_memflow.py::test_forward_within_k_times_the_oracles_own_noise."""
     net, ora = _pair(precision=precision)
     x = torch.rand(1, 2, 3, 128, 192, generator=torch.Generator().manual_seed(3)) * 2 - 1
     low_ref, ref = ora(x)
@@ -42,7 +47,8 @@ def test_memflow_forward_matches_oracle(gpu, precision):
 
 def test_memflow_plain_attention_plane_at_a_small_size(gpu, monkeypatch):
     """256 x 320: 1280 keys, the smallest size class that takes the one-f16-per-probability read-out; both read-out
-    paths against the oracle, and against each other."""
+    paths against the oracle, and against each other.  (Both forms at the smallest plane size, 256 x 264, held to 8 N in every
+    statistic: tests/test_gpu_elementwise_memflow.py.)"""
     from vfml import memflow_net
     net, ora = _pair()
     x = torch.rand(1, 2, 3, 256, 320, generator=torch.Generator().manual_seed(11)) * 2 - 1
@@ -59,7 +65,8 @@ def test_memflow_plain_attention_plane_at_a_small_size(gpu, monkeypatch):
 
 def test_memflow_1080p_matches_oracle(gpu):
     """One pair at the size of BASELINE config C4: 32400 keys per attention row - the probabilities average 3e-5,
-    which is where their storage scale (memflow_net.ATT_SCALE) matters."""
+    which is where their storage scale (memflow_net.ATT_SCALE) matters.  The mean alone, at the one size the elementwise
+    module (tests/test_gpu_elementwise_memflow.py) leaves out."""
     import time
     net, ora = _pair()
     torch.set_num_threads(min(16, os.cpu_count() or 1))

@@ -197,7 +197,8 @@ def _epe(a, b):
 
 @pytest.mark.parametrize("M", [1, 2])
 def test_stream_matches_memory_oracle(gpu, M):
-    """Depth 12, four fields: every field within the contract of its oracle."""
+    """Depth 12, four fields: every field within the contract of its oracle - in the mean.  Every statistic of every field and
+    of its 1/8-resolution flow, at 8 times the oracle's own noise: tests/test_gpu_elementwise_memflow.py's stream cases."""
     s = _shared()
     for f in range(4):
         e = _epe(s["got"][M][f], s["ref"][M][f])

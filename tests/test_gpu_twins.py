@@ -57,26 +57,38 @@ def _ln_case(rows, c, in_fmt, out_fmt, ld=None, off=0, inplace=False, x=None):
 
 
 @pytest.mark.parametrize("in_fmt,out_fmt", FMTS)
-@pytest.mark.parametrize("rows,c", [(37, 128), (5, 256), (1000, 128)])
+@pytest.mark.parametrize("rows,c", [(37, 128), (5, 256), (1000, 128),
+                                    # what the entry point accepts beyond the encoders' own widths: a row is held by G = 16,
+                                    # 32 or 64 lanes (c / 8 units up to 16, up to 32, above), in up to four passes of G units
+                                    (37, 8),        # G = 16 with one lane live
+                                    (37, 136),      # 17 units: G = 32, half of it without channels
+                                    (37, 264),      # 33 units: G = 64 in one pass, ragged
+                                    (21, 520),      # 65 units: G = 64, a second pass with one live lane
+                                    (9, 2048)])     # LN_MAX_C: all four passes full
 def test_layernorm_rows_against_float64(gpu, rows, c, in_fmt, out_fmt):
     _ln_case(rows, c, in_fmt, out_fmt)
 
 
 @pytest.mark.parametrize("fmt", [0, 1])
 def test_layernorm_rows_in_place_and_in_a_slice(gpu, fmt):
-    """In place; and 128 channels at offset 8 of rows 16 wider than c, the columns around them keeping their pattern."""
+    """In place; and 128 channels at offset 8 of rows 16 wider than c, the columns around them keeping their pattern.  The
+    same at c = 520 (G = 64, a second pass with one live lane: the last lane's store is the one next to the pattern)."""
     _ln_case(37, 128, fmt, fmt, inplace=True)
     _ln_case(37, 128, fmt, fmt, ld=144, off=8)
     _ln_case(37, 128, fmt, fmt, ld=144, off=8, inplace=True)
+    _ln_case(21, 520, fmt, fmt, ld=536, off=8)
+    _ln_case(21, 520, fmt, fmt, ld=536, off=8, inplace=True)
 
 
 @pytest.mark.parametrize("fmt", [0, 1])
 def test_layernorm_rows_far_from_zero(gpu, fmt):
-    """Rows whose |mean| is 100 times their spread: E[x^2] - E[x]^2 in f32 would lose the variance's leading digits."""
-    g = torch.Generator().manual_seed(5)
-    x = 100.0 * (torch.rand(37, 1, generator=g) + 0.5) * torch.tensor([1.0, -1.0])[torch.arange(37) % 2].view(37, 1) \
-        + torch.randn(37, 256, generator=g)
-    _ln_case(37, 256, fmt, fmt, x=x)
+    """Rows whose |mean| is 100 times their spread: E[x^2] - E[x]^2 in f32 would lose the variance's leading digits.  At
+    c = 256 (G = 32, every lane full) and at c = 520 (G = 64, two passes, the mean folded over lanes without channels)."""
+    for c in (256, 520):
+        g = torch.Generator().manual_seed(5)
+        x = 100.0 * (torch.rand(37, 1, generator=g) + 0.5) * torch.tensor([1.0, -1.0])[torch.arange(37) % 2].view(37, 1) \
+            + torch.randn(37, c, generator=g)
+        _ln_case(37, c, fmt, fmt, x=x)
 
 
 # ----------------------------------------------------------------------------- window_attention
@@ -378,7 +390,9 @@ CASES = [(3, 136, 152, {}), (5, 136, 152, {}), (5, 136, 152, {"network": "BOFNet
 @pytest.mark.parametrize("T,H,W,over", CASES, ids=["mof3", "mof5", "bof5", "twins+sk+gma3"])
 def test_twins_forward_matches_oracle(gpu, T, H, W, over):
     """f16x3, depth 4, seed 0, against the float64 oracle: mean EPE <= 8 N, N = the float32 oracle's own mean EPE against
-    float64 on that input, and < EPE_TOL; for mof3 all five statistics within 8 times the oracle's noise floor."""
+    float64 on that input, and < EPE_TOL; for mof3 all five statistics within 8 times the oracle's noise floor.  All five
+    statistics of every one of these cases, of the 1/8-resolution flows, of uint8 input and of flows above one cell are held
+    to 8 N by the `twins` cases of tests/test_gpu_elementwise_variants.py."""
     import mof_twins_oracle as to
     from vfml.weights import seeded_state_dict
     cfg, ocfg = _cfgs(**over)

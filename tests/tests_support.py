@@ -189,10 +189,14 @@ def drift_state_dict(sd, c, key=DRIFT_KEY):
     """A copy of state dict `sd` whose flow head adds c * DRIFT_DIRECTION cells to the flow in every iteration: the seeded
     weights' own flow stays near one cell, with this the 1/8-resolution flow reaches about depth * c cells (forward and
     backward, x and y each another way).  `key` names the bias of the flow head's last convolution (DRIFT_KEY_SK for an SK
-    checkpoint).  Every other entry is the same tensor's clone; oracle and engine load the same dict."""
+    checkpoint).  A bias of two entries (MemFlow's flow head: one flow) takes the first two components.  Every other entry is
+    the same tensor's clone; oracle and engine load the same dict."""
     out = {k: v.clone() for k, v in sd.items()}
     b = out[key]
-    out[key] = b + float(c) * torch.tensor(DRIFT_DIRECTION, dtype=b.dtype, device=b.device)
+    if b.numel() not in (2, 4):
+        raise ValueError(f"drift_state_dict: {key} has {b.numel()} entries, a flow head has 2 (one flow) or 4")
+    # (MemFlow's flow head gives one flow: the forward components)
+    out[key] = b + float(c) * torch.tensor(DRIFT_DIRECTION[:b.numel()], dtype=b.dtype, device=b.device)
     return out
 
 
@@ -220,6 +224,63 @@ def plan_deviation(x, cfg, state_dict, plan, corr_volume="f32"):
     ref, low = oracle_f64_fields(x, cfg, state_dict)
     got, _ = oracle_f64_fields(x, cfg, state_dict, plan, corr_volume)
     return error_stats(got, ref), float(low.abs().max())
+
+
+# ----------------------------------------------------------------------------- the MemFlow oracles
+# Another call shape than the MOF oracles': forward(pair) -> (low, flow), frames already in [-1, 1], a stream of fields
+# through tests/memflow_memory_oracle.py.
+_MEMFLOW = {}
+
+
+def memflow_oracle_net(depth, state_dict, double=False):
+    """oracle.memflow_oracle's network at `depth` iterations with `state_dict` loaded, eval mode; `double`: the same modules
+    in float64 (parameters converted exactly; feed it float64 frames)."""
+    from oracle import memflow_oracle as mm
+    cfg = mm.get_cfg()
+    cfg.decoder_depth = depth
+    net = mm.build_network(cfg)
+    net.load_state_dict(state_dict)
+    net.eval()
+    return net.double() if double else net
+
+
+def memflow_stack(fields):
+    """[(low [1, 2, h, w], flow [1, 2, H, W]) per field] -> (flow [1, F, 2, H, W], low [1, F, 2, h, w]): the layout of
+    error_stats / low_stats, in oracle_pair's order."""
+    return torch.stack([f[1][0] for f in fields])[None], torch.stack([f[0][0] for f in fields])[None]
+
+
+def memflow_stream_fields(net, clip, M, alter=None):
+    """The fields (i, i+1) of clip [1, F+1, 3, H, W] (in [-1, 1], the network's dtype) through ONE
+    memflow_memory_oracle.Stream of capacity M (M = 0: MemFlowNetOracle.forward on every pair), stacked by memflow_stack.
+    `alter`: applied to every field's attention rows [1, P, (n + 1) P] - the mutants of tests/test_memflow_noise_cpu.py."""
+    import memflow_memory_oracle as mo
+    st = mo.Stream(net, M, alter)
+    return memflow_stack([st.step(clip[:, i:i + 2]) for i in range(clip.shape[1] - 1)])
+
+
+def memflow_oracle_fields(clip, depth, state_dict, M):
+    """The MemFlow oracle's fields of clip [1, F+1, 3, H, W] (float32, in [-1, 1]) through one stream of capacity M, in
+    float32 and in float64 (the same modules and state dict, .double()), computed once per session and (clip, depth, weights,
+    M): {"f32": (flow [1, F, 2, H, W], low [1, F, 2, h, w]), "f64": (flow, low), "seconds": (t32, t64)}."""
+    key = (_digest(clip), int(depth), _digest(*state_dict.values()), int(M))
+    ent = _MEMFLOW.get(key)
+    if ent is None:
+        torch.set_num_threads(min(16, torch.get_num_threads()))
+        ent, secs = {}, []
+        for name, double in (("f32", False), ("f64", True)):
+            net = memflow_oracle_net(depth, state_dict, double)
+            t0 = time.time()
+            ent[name] = memflow_stream_fields(net, clip.double() if double else clip.float(), M)
+            secs.append(time.time() - t0)
+        ent["seconds"] = tuple(secs)
+        _MEMFLOW[key] = ent
+    return ent
+
+
+def field_of(t, f):
+    """Field f of a stack [1, F, 2, H, W], as a stack of one."""
+    return t[:, f:f + 1]
 
 
 # ----------------------------------------------------------------------------- input kinds
