@@ -34,7 +34,8 @@ extern "C" {
  * the three vfml_jpeg_*_sampled entry points of the encoder; and vfml_text_draw, an addition as well; and likewise
  * vfml_attention_plane_f16, vfml_dwconv2d and vfml_gelu_rows.  27 adds vfml_conv2d_split_variant_at; it also covers
  * vfml_layernorm_rows, vfml_window_attention and vfml_attention_shared_keys (the Twins-SVT encoders): additions only;
- * and vfml_attention_bank_planes_f16 and vfml_axpy_f32 (MemFlow's memory bank), additions as well. */
+ * and vfml_attention_bank_planes_f16 and vfml_axpy_f32 (MemFlow's memory bank), additions as well; and likewise
+ * vfml_flow_forward_interpolate with its workspace size (the warm start of a MemFlow stream). */
 #define VFML_ABI_VERSION 27
 
 /* Epilogue selector of vfml_conv2d.  v = out_scale * (acc + addend[p][c] + bias[c]). */
@@ -451,6 +452,23 @@ int vfml_coords_update(float* coords1, const float* delta, int n, int h, int w,
                        float* flow_a, int ld_a, float* flow_b, int ld_b, int fmt_b, void* stream);
 /* fmt_b VFML_FMT_S16: flow_b points at channel 4 of a split-row unit (16-byte aligned + 8): the four
  * flow values become the second quad of that unit (hi at +0..7, lo at +16..23 of the quad slot). */
+
+/* forward_interpolate: a 1/8-resolution flow projected forward along itself, what the next field of a
+ * video starts its recurrence from.  flow: n independent maps of [h][w] rows of ld_in floats (ld_in >= 2), channels 0..1 =
+ * (x, y) in cells; flow4 of the update block has ld_in = 4.  Source cell s = (xs, ys) lands at x1 = f32(xs) + f.x,
+ * y1 = f32(ys) + f.y (one f32 addition each) and is VALID iff 0 < x1 < w and 0 < y1 < h (strict; NaN and infinities fail).
+ * Target cell (x, y) takes flow[s*] of the valid source of least d2 = (x1 - x)*(x1 - x) + (y1 - y)*(y1 - y) - every
+ * operation a single f32 one rounded to nearest, nothing contracted -, ties to the LOWEST row-major source index; with no
+ * valid source the map is zero.  out: rows of ld_out floats (ld_out >= 2), channels 0..1 written, and with ld_out >= 4
+ * channels 2..3 written as zero - with ld_out = 4 the `delta` operand of vfml_coords_update; out may not overlap flow.
+ * index: NULL, or int32 [n][h*w] that receives s* per cell (-1: no valid source).  An exact brute-force search, h*w <= 2^24:
+ * (h*w)^2 distance evaluations per map; partial minima of 2048-source chunks go through `workspace`
+ * (vfml_flow_forward_interpolate_workspace_bytes(n, h, w) bytes, 8-byte aligned; 0 for sizes that are refused) as 64-bit
+ * keys and are combined by an integer minimum: results are bit-identical from run to run.  Two launches, stream-ordered, no
+ * host synchronisation (capturable); a bad argument returns non-zero with vfml_last_error set and launches nothing. */
+int64_t vfml_flow_forward_interpolate_workspace_bytes(int n, int h, int w);
+int vfml_flow_forward_interpolate(const float* flow, int ld_in, int n, int h, int w, float* out, int ld_out, int32_t* index,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 /* coords1[p] = (x, y, x, y) */
 int vfml_coords_init(float* coords1, int n, int h, int w, void* stream);
 

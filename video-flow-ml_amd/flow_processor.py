@@ -395,6 +395,22 @@ def memflow_memory():
     return check_memory_frames(MEMFLOW_MEMORY, "flow_processor.MEMFLOW_MEMORY")
 
 
+# True: in a MemFlow job every field's recurrence starts from the previous field's 1/8-resolution flow projected forward along
+# itself (upstream's flow_init) instead of from zero: the job walks its frames in order through one
+# stream, as with a memory bank (one GPU, whole frames; the cache directory carries _warm).  The environment variable
+# VFML_MEMFLOW_WARM_START (0 or 1) overrides it.  No command-line flag: the parser stays the reference's.
+MEMFLOW_WARM_START = False
+
+
+def memflow_warm_start():
+    """MEMFLOW_WARM_START, or VFML_MEMFLOW_WARM_START when it is set: 0 or 1; anything else is refused."""
+    from vfml.memflow_net import check_warm_start
+    env = os.environ.get("VFML_MEMFLOW_WARM_START")
+    if env:
+        return check_warm_start(env, "VFML_MEMFLOW_WARM_START")
+    return check_warm_start(MEMFLOW_WARM_START, "flow_processor.MEMFLOW_WARM_START")
+
+
 # True: the output video carries the reference's text labels, drawn with the project's own text (DESIGN.md section 9,
 # "Text"): vfml_text_draw behind the composer on the device path, visualization/text.py under --device cpu.  The
 # environment variable VFML_LABELS=1|0 overrides it.  Off: the fixtures cut from the reference and the render tests pin
@@ -651,10 +667,11 @@ def main(argv=None):
     mjpg_sampling()             # a setting that is not built is refused before anything is computed or rendered
     draw_labels()               # (likewise VFML_LABELS)
     memory = memflow_memory()   # (likewise VFML_MEMFLOW_MEMORY)
+    warm = memflow_warm_start()  # (likewise VFML_MEMFLOW_WARM_START)
     if args.model != 'memflow':
-        memory = 0
+        memory, warm = 0, False
     try:
-        check_memory_job(memory, bool(args.tile), world)
+        check_memory_job(memory, bool(args.tile), world, warm)
     except ValueError as e:
         log(f"Error: {e}")
         return 1
@@ -688,7 +705,8 @@ def main(argv=None):
     memflow = args.model == 'memflow'
     cache_dir = args.use_flow_cache or mgr.generate_cache_path(
         cache_src, start, n, args.sequence_length, args.fast, args.tile, args.model,
-        args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant, memory_frames=memory)
+        args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant, memory_frames=memory,
+        warm_start=warm)
     complete, fmt, missing = mgr.check_cache_exists(cache_dir, n)
     if complete and not args.force_recompute:
         if args.interactive:
@@ -701,7 +719,7 @@ def main(argv=None):
 
     if memflow:     # reference flow_processor.py:64-75: model path defaults to MemFlow_ckpt/MemFlowNet_{stage}.pth
         eng = MemFlowInference(device, args.model_path or f"MemFlow_ckpt/MemFlowNet_{args.stage}.pth", args.stage,
-                               args.sequence_length, memory_frames=memory)
+                               args.sequence_length, memory_frames=memory, warm_start=warm)
     else:
         eng = VideoFlowInference(device, args.fast, args.tile, args.sequence_length, args.vf_dataset,
                                  args.vf_architecture, args.vf_variant)

@@ -14,13 +14,15 @@ from typing import Dict
 import torch
 
 from vfml import InputPadder
-from vfml.memflow_net import build_memflow_network, check_memory_frames, memflow_cfg
+from vfml.memflow_net import build_memflow_network, check_memory_frames, check_warm_start, memflow_cfg
 from vfml.weights import load_checked
 
 
 class MemFlowCore:
-    def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel', memory_frames=0):
+    def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel', memory_frames=0,
+                 warm_start=False):
         self.memory_frames = check_memory_frames(memory_frames)      # bank capacity of step_stream (an extension)
+        self.warm_start = check_warm_start(warm_start)               # step_stream's fields start from the projected last flow
         self._stream = None
         self.device = self._validate_device(device)
         self.model_path = model_path
@@ -128,11 +130,11 @@ class MemFlowCore:
 
     def open_stream(self):
         """A fresh stream of fields in frame order with a bank of `memory_frames` entries (vfml.memflow_net.MemFlowStream;
-        upstream's InferenceCore): the fields of step_stream read the keys and values of the fields before them.  The
-        padder is fixed by the stream's first pair."""
+        upstream's InferenceCore): the fields of step_stream read the keys and values of the fields before them and, with
+        `warm_start`, start from the previous field's flow projected forward.  The padder is fixed by the stream's first pair."""
         if self.model is None:
             raise RuntimeError("Model not loaded. Call load_model() first.")
-        self._stream = self.model.stream(self.memory_frames)
+        self._stream = self.model.stream(self.memory_frames, warm_start=self.warm_start)
         self._stream_padder = None
         return self._stream
 

@@ -8,10 +8,11 @@ _FORWARDED = ("prepare_frame_sequence", "compute_optical_flow", "compute_optical
 
 class MemFlowInference:
     def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel',
-                 sequence_length=3, memory_frames=0):
+                 sequence_length=3, memory_frames=0, warm_start=False):
         self.device, self.model_path, self.stage, self.sequence_length = device, model_path, stage, sequence_length
         self.processor = MemFlowProcessor(device=device, model_path=model_path, stage=stage,
-                                          sequence_length=sequence_length, memory_frames=memory_frames)
+                                          sequence_length=sequence_length, memory_frames=memory_frames,
+                                          warm_start=warm_start)
         self.model = None
         self.cfg = None
 

@@ -14,13 +14,15 @@ from .memflow_core import MemFlowCore
 
 class MemFlowProcessor:
     def __init__(self, device='cuda', model_path='MemFlow_ckpt/MemFlowNet_sintel.pth', stage='sintel',
-                 sequence_length=3, memory_frames=0):
+                 sequence_length=3, memory_frames=0, warm_start=False):
         self.device = device
         self.model_path = model_path
         self.stage = stage
         self.sequence_length = max(2, sequence_length)
-        self.core_engine = MemFlowCore(device=device, model_path=model_path, stage=stage, memory_frames=memory_frames)
+        self.core_engine = MemFlowCore(device=device, model_path=model_path, stage=stage, memory_frames=memory_frames,
+                                       warm_start=warm_start)
         self.memory_frames = self.core_engine.memory_frames     # above 0: job loops walk one stream (an extension)
+        self.warm_start = self.core_engine.warm_start           # True: job loops walk one stream too, whatever the bank
         self._stream_at = None           # (clip token, frame) of the stream's last field
         print("MemFlow Processor initialized:")
         print(f"  Sequence length: {self.sequence_length} frames")
@@ -65,8 +67,9 @@ class MemFlowProcessor:
         return torch.stack(planes, dim=0).unsqueeze(0)
 
     def compute_optical_flow(self, frames: List[np.ndarray], frame_idx: int) -> np.ndarray:
-        """Random access (the visualiser's call): one field with an empty memory bank, whatever `memory_frames` is - the bank
-        belongs to a job that walks the frames in order (compute_optical_flow_stream)."""
+        """Random access (the visualiser's call): one field with an empty memory bank and a cold start, whatever `memory_frames`
+        and `warm_start` are - the bank and the kept flow belong to a job that walks the frames in order
+        (compute_optical_flow_stream)."""
         flow = self.core_engine.compute_flow_from_tensor(self.prepare_frame_sequence(frames, frame_idx))
         return flow.permute(1, 2, 0).numpy()
 
@@ -144,15 +147,16 @@ class MemFlowProcessor:
         return out
 
     def begin_stream_job(self):
-        """A job starts with an empty bank at its first frame."""
+        """A job starts with an empty bank, and cold, at its first frame."""
         self._stream_at = None
 
     def compute_optical_flow_stream(self, clip, frame_idxs):
         """Fields of frames of a resident clip IN FRAME ORDER through one stream with a bank of `memory_frames` entries ->
         list of device tensors [H,W,2].  Field i is the pair (i-1, i) - frame 0 the pair (0, 0) - and reads the keys and
-        values of the fields before it, so fields are not batched (field t needs field t-1's value map).  The stream carries
-        over from one call to the next while the frames stay consecutive in one clip; anything else - begin_stream_job(),
-        another clip, a gap, a step back - starts from an empty bank."""
+        values of the fields before it, so fields are not batched (field t needs field t-1's value map).  With `warm_start`
+        field i also starts from field i-1's flow projected forward (with memory_frames = 0 that is all the stream carries).
+        The stream carries over from one call to the next while the frames stay consecutive in one clip; anything else -
+        begin_stream_job(), another clip, a gap, a step back - starts from an empty bank and a zero flow."""
         from vfml.clip_id import clip_token
         from vfml.network import take_frames
         core = self.core_engine

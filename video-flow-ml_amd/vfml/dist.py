@@ -1,7 +1,8 @@
 """Multi-GPU sharding of flow-field work items (one process per GPU, torch.distributed).
 
 Every flow field depends only on its own T-frame window (no warm start: the reference never passes
-flow_init, processing/videoflow_core.py:188), and in --tile mode every tile only on its own crop
+flow_init, processing/videoflow_core.py:188; MemFlow's opt-in warm start and memory bank carry state from field to field and
+are refused over several ranks, vfml.runner.check_memory_job), and in --tile mode every tile only on its own crop
 (processing/videoflow_processor.py:258-277).  So the job is a list of independent work items
 (frame i) or (frame i, tile j); ranks take contiguous blocks of that list, compute them with no
 data-path communication, and one gather collects the finished fields on rank 0 — RCCL over xGMI on

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip", "warm_start.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -179,6 +179,10 @@ def lib():
     L.vfml_tapsum3x3.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, ctypes.c_int64, c_void_p]
     L.vfml_coords_update.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                      c_int, c_void_p]
+    L.vfml_flow_forward_interpolate_workspace_bytes.restype = c_int64
+    L.vfml_flow_forward_interpolate_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.vfml_flow_forward_interpolate.argtypes = [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                                c_void_p]
     L.vfml_flow_lod.argtypes = [c_void_p, c_int, c_int, c_void_p, c_void_p]
     L.vfml_flow_encode.argtypes = [c_void_p, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, c_void_p,
                                    c_void_p]
@@ -251,6 +255,7 @@ EXPORTS = [
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
     "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
+    "vfml_flow_forward_interpolate_workspace_bytes", "vfml_flow_forward_interpolate",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay", "vfml_text_draw",
     "vfml_flow_turbulence_workspace_bytes", "vfml_flow_turbulence_map", "vfml_resize_u8",
@@ -831,6 +836,51 @@ def coords_update(coords1, delta, n, h, w, flow_a=None, ld_a=0, flow_a_off=0, fl
     _check(lib().vfml_coords_update(_ptr(_dev(coords1)), _ptr(delta), n, h, w,
                                     _ptr(flow_a, flow_a_off), ld_a, _ptr(flow_b, flow_b_off), ld_b, fmt_b, _stream()),
            "vfml_coords_update")
+
+
+def flow_forward_interpolate_workspace(n, h, w, device):
+    """The workspace of flow_forward_interpolate for n maps of h x w cells (vfml_flow_forward_interpolate_workspace_bytes)."""
+    nbytes = lib().vfml_flow_forward_interpolate_workspace_bytes(n, h, w)
+    return torch.empty(max(1, nbytes // 8), dtype=torch.int64, device=device)
+
+
+def flow_forward_interpolate(flow, h=None, w=None, n=1, ld_in=None, out=None, ld_out=None, index=None, workspace=None):
+    """A 1/8-resolution flow projected forward along itself (vfml_flow_forward_interpolate): every
+    source cell moves by its own flow, every target cell takes the flow of the nearest landing point inside the frame, ties to
+    the lowest source index, zero when no source stays inside.
+    flow: float32 device tensor, [h, w, 2] (or [n, h, w, c], c = 2 or 4: then h, w, n and ld_in come from its shape) or flat
+    rows of ld_in floats with h, w, n given.  out: rows of ld_out floats (default: flow's own layout, a new tensor); with
+    ld_out = 4 channels 2..3 are written as zero: the `delta` operand of coords_update.  index: optional int32 tensor of
+    n * h * w entries that receives the chosen source per cell (-1: none valid).  workspace: from
+    flow_forward_interpolate_workspace, or allocated here.  Stream-ordered, no host synchronisation.  Returns out."""
+    _dev(flow)
+    shape = None
+    if h is None or w is None:
+        if flow.dim() not in (3, 4) or flow.shape[-1] not in (2, 4):
+            raise ValueError(f"flow_forward_interpolate: flow [h, w, 2] or [n, h, w, c] expected (or flat rows with h, w), "
+                             f"got {tuple(flow.shape)}")
+        shape = tuple(flow.shape)
+        h, w, ld_in = shape[-3], shape[-2], shape[-1]
+        n = shape[0] if flow.dim() == 4 else 1
+    ld_in = ld_in or 2
+    ld_out = ld_out or ld_in
+    if flow.numel() < n * h * w * ld_in:
+        raise ValueError(f"flow_forward_interpolate: flow holds {flow.numel()} floats, {n} x {h} x {w} x {ld_in} expected")
+    if out is None:
+        out = torch.empty(shape[:-1] + (ld_out,) if shape else (n * h * w * ld_out,), dtype=torch.float32, device=flow.device)
+    if _dev(out).device != flow.device or out.numel() < n * h * w * ld_out:
+        raise ValueError(f"flow_forward_interpolate: out of {n} x {h} x {w} x {ld_out} floats on {flow.device} expected")
+    if index is not None and (_dev(index, torch.int32).device != flow.device or index.numel() < n * h * w):
+        raise ValueError(f"flow_forward_interpolate: index of {n} x {h} x {w} int32 on {flow.device} expected")
+    if workspace is None:
+        workspace = flow_forward_interpolate_workspace(n, h, w, flow.device)
+    if _dev(workspace, torch.int64).device != flow.device:
+        raise ValueError(f"flow_forward_interpolate: workspace on {flow.device} expected")
+    _check(lib().vfml_flow_forward_interpolate(_ptr(flow), ld_in, n, h, w, _ptr(out), ld_out,
+                                               None if index is None else c_void_p(index.data_ptr()),
+                                               c_void_p(workspace.data_ptr()), workspace.numel() * 8, _stream()),
+           "vfml_flow_forward_interpolate")
+    return out
 
 
 def flow_lods(flow, num_lods=5):

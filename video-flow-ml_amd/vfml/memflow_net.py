@@ -13,7 +13,9 @@ split-row halves (4.2 GB at 1080p; no flash-style re-computation needed with 288
 iteration is one long-K GEMM  attn[P,P] . v[P,128]  on the MFMA kernel with the residual add fused.
 
 MemFlowStream (below) is the bank that is not empty: fields in frame order, each reading the keys and
-values of up to `memory_frames` fields before it; with none held a step is forward() launch for launch.
+values of up to `memory_frames` fields before it; with none held a step is forward() launch for launch.  With
+warm_start=True a field's recurrence also starts from the previous field's 1/8-resolution flow projected
+forward along itself (hip.flow_forward_interpolate), upstream's `flow_init`.
 """
 import weakref
 
@@ -96,6 +98,7 @@ class MemFlowNetHIP(MOFNetHIP):
         self._att_planes.clear()
         for st in list(self._streams):
             st._planes.clear()
+            st._scratch.clear()          # (the kept flow stays, as the bank does)
 
     # ------------------------------------------------------------------ weights
     def _pack(self, device):
@@ -132,36 +135,54 @@ class MemFlowNetHIP(MOFNetHIP):
 
     # ------------------------------------------------------------------ forward
     @torch.no_grad()
-    def forward(self, pair, data=None, frame_keys=None):
+    def forward(self, pair, data=None, frame_keys=None, flow_init=None):
         """pair: float [1, 2, 3, H, W] in [-1, 1] on the GPU (previous, current).
         Returns (flow_low [1,2,h,w], flow [1,2,H,W]) like InferenceCore.step(..., end=True).
         frame_keys: optional pair of hashable ids of the two frames (same id = same normalised pixels): the
         feature encoder output of a frame is then kept, so a frame that is "current" in one call and
-        "previous" in the next is encoded once (results bit-identical)."""
+        "previous" in the next is encoded once (results bit-identical).
+        flow_init: optional 1/8-resolution flow the recurrence starts from, in cells, float32 on the pair's device:
+        [1, 2, h, w] or [h, w, 2] (or the rows [h * w, 4] = (x, y, 0, 0) a stream hands over); None: zero, today's launches."""
         if isinstance(pair, torch.Tensor) and pair.dim() == 5 and pair.shape[1] != 2:
             raise ValueError(f"pair must be [1,2,3,H,W], got {tuple(pair.shape)}")
-        return self.forward_pairs(pair, data, frame_keys)
+        return self._run_pairs(pair, frame_keys, None, flow_init)
 
     @torch.no_grad()
-    def forward_pairs(self, frames, data=None, frame_keys=None):
+    def forward_pairs(self, frames, data=None, frame_keys=None, flow_init=None):
         """frames: float [1, B+1, 3, H, W] in [-1, 1] on the GPU: B overlapping pairs (k, k+1) - B consecutive
         fields of a job in one pass (every pair its own fresh-memory step, exactly as B separate calls; at
         1080p one pair leaves most tiles of the update-block convolutions' last round empty).
-        Returns (flow_low [B,2,h,w], flow [B,2,H,W])."""
-        return self._run_pairs(frames, frame_keys, None)
+        Returns (flow_low [B,2,h,w], flow [B,2,H,W]).  flow_init: None, or a single pair's (forward): a starting flow belongs
+        to one field."""
+        return self._run_pairs(frames, frame_keys, None, flow_init)
 
-    def stream(self, memory_frames=0):
-        """A stream of fields in frame order that carries the memory bank (MemFlowStream)."""
-        return MemFlowStream(self, memory_frames)
+    def stream(self, memory_frames=0, warm_start=False):
+        """A stream of fields in frame order that carries the memory bank and, with warm_start, the flow (MemFlowStream)."""
+        return MemFlowStream(self, memory_frames, warm_start)
 
-    def _run_pairs(self, frames, frame_keys, mem):
+    @staticmethod
+    def _check_flow_init(flow_init, B, h, w, dev):
+        """The form of a starting flow (forward's docstring); raises before anything is launched."""
+        if B != 1:
+            raise ValueError(f"flow_init starts ONE field's recurrence: it is refused with {B} pairs in a pass")
+        if not isinstance(flow_init, torch.Tensor) or flow_init.dtype != torch.float32:
+            raise ValueError(f"flow_init must be a float32 tensor, got {getattr(flow_init, 'dtype', type(flow_init))}")
+        if flow_init.device != dev:
+            raise ValueError(f"flow_init is on {flow_init.device}, the pair on {dev}")
+        if tuple(flow_init.shape) not in ((1, 2, h, w), (h, w, 2), (h * w, 4)):
+            raise ValueError(f"flow_init must be [1,2,{h},{w}] or [{h},{w},2] (the 1/8-resolution grid of the pair, in cells), "
+                             f"got {tuple(flow_init.shape)}")
+
+    def _run_pairs(self, frames, frame_keys, mem, flow_init=None):
         """forward_pairs; mem: the MemFlowStream whose bank this (single) pair reads and, after its last iteration, joins -
-        with no entry held the launches are forward_pairs' own."""
+        with no entry held the launches are forward_pairs' own.  flow_init: forward's."""
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
             raise RuntimeError("MemFlowNetHIP runs on an MI355X (HIP) device only; got "
                                f"{getattr(frames, 'device', type(frames))}. There is no CPU fallback in the shipped engine.")
         if frames.dim() != 5 or frames.shape[0] != 1 or frames.shape[1] < 2 or frames.shape[2] != 3:
             raise ValueError(f"frames must be [1,B+1,3,H,W], got {tuple(frames.shape)}")
+        if flow_init is not None:
+            self._check_flow_init(flow_init, frames.shape[1] - 1, frames.shape[3] // 8, frames.shape[4] // 8, frames.device)
         cfg = self.cfg
         src = frames[0].float().contiguous()
         B = src.shape[0] - 1
@@ -280,7 +301,11 @@ class MemFlowNetHIP(MOFNetHIP):
                     else:
                         hip.axpy_f32(ro.out_t, r_mem, Pn * AD)
 
-            update_block.init_coords(s, B)
+            if flow_init is not None and tuple(flow_init.shape) != (Pn, 4):
+                xy = flow_init[0].permute(1, 2, 0) if flow_init.dim() == 4 else flow_init
+                flow_init = self._buf("flow_init", Pn * 4, dev, zero=True).view(Pn, 4)      # channels 2,3 stay zero
+                flow_init[:, :2].copy_(xy.reshape(Pn, 2))
+            update_block.init_coords(s, B, None if flow_init is None else flow_init.contiguous())
             for it in range(cfg.decoder_depth):
                 update_block.lookup(s, B, 0, pyrs=pyrs)
                 update_block.convc1(s, B, 0)
@@ -295,6 +320,8 @@ class MemFlowNetHIP(MOFNetHIP):
 
             if mem is not None and mem.memory_frames:
                 mem._take(kmap, ro.val, Pn * AD, (H, W))      # (k_t, the last iteration's value map) joins the bank
+            if mem is not None and mem.warm_start:
+                mem._keep_flow(s.flow4, Pn, (H, W))           # the next field's recurrence starts from its projection
             mask = self._buf("mmask", MP * 576, dev)
             update_block.mask_head(s, B, mask, 576)
             up = torch.empty(B, H, W, 2, device=dev, dtype=torch.float32)
@@ -324,17 +351,38 @@ def check_memory_frames(value, source="memory_frames"):
     return int(text)
 
 
+def check_warm_start(value, source="warm_start"):
+    """The warm-start switch as a bool: False / True, 0 / 1, "0" / "1"; anything else is refused."""
+    if isinstance(value, bool):
+        return value
+    text = str(value).strip() if isinstance(value, (int, str)) else ""
+    if text not in ("0", "1"):
+        raise ValueError(f"{source} = {value!r}: the warm start of a MemFlow stream is switched with 0 or 1")
+    return text == "1"
+
+
 class MemFlowStream:
     """The fields of a video in frame order, each reading the keys and values of the fields before it (DESIGN.md section
     18; upstream's InferenceCore.step).  The bank holds up to `memory_frames` pairs (k_j, v_j), oldest first: a field's keys
     as f32 rows and the value map of its last iteration, on the device.  With entries held the attention rows are the softmax
     JOINTLY over the bank's keys and the frame's own, as one resident f16 plane per key set; the bank's part of the read-out
     is computed once per field.  With none - the first field, memory_frames = 0, after end=True or reset() - a step is
-    net.forward on the pair, launch for launch."""
+    net.forward on the pair, launch for launch.
 
-    def __init__(self, net, memory_frames=0):
+    warm_start=True (upstream's flow_init): the stream also keeps the last field's final 1/8-resolution
+    flow (flow4, in a buffer of its own: the network's workspace is reused) and starts the next field's recurrence from
+    hip.flow_forward_interpolate of it, coords1 = coords0 + that.  The stream's first field and the first after end=True or
+    reset() start from zero.  It needs no attention plane: with memory_frames = 0 it runs at every size forward takes.  With
+    warm_start=False nothing of this is allocated or launched."""
+
+    def __init__(self, net, memory_frames=0, warm_start=False):
         self.net = net
         self.memory_frames = check_memory_frames(memory_frames)
+        self.warm_start = check_warm_start(warm_start)
+        self.flow_size = None        # (H, W) of the kept flow; None: the next field starts cold
+        self.flow_index = None       # int32 [Pn]: the source cell every cell of the last warm field started from (-1: none)
+        self._flow = None            # f32 [Pn * 4]: the last field's flow4
+        self._scratch = {}           # the projection's delta rows, index map and workspace
         self.entries = []            # [(k [Pn*AD] f32, v [Pn*AD] f32)], oldest first
         self.size = None             # (H, W) of the entries
         self.planes_in_use = 0       # planes the last step read: entries held before it + 1
@@ -346,6 +394,7 @@ class MemFlowStream:
         self._spare += self.entries
         self.entries = []
         self.size = None
+        self.flow_size = None
 
     @property
     def planes_held(self):
@@ -375,18 +424,43 @@ class MemFlowStream:
         self.entries.append((kk, vv))
         self.size = size
 
+    def _keep_flow(self, flow4, Pn, size):
+        if self._flow is None or self._flow.numel() != Pn * 4 or self._flow.device != flow4.device:
+            self._flow = torch.empty(Pn * 4, device=flow4.device)
+        self._flow.copy_(flow4[:Pn * 4])
+        self.flow_size = size
+
+    def _projected_flow(self, h, w):
+        """hip.flow_forward_interpolate of the kept flow as delta rows [Pn][4]; the chosen sources go to flow_index."""
+        dev, Pn, sc = self._flow.device, h * w, self._scratch
+        if "delta" not in sc or sc["delta"].numel() != Pn * 4 or sc["delta"].device != dev:
+            sc.update(delta=torch.empty(Pn * 4, device=dev), index=torch.empty(Pn, dtype=torch.int32, device=dev),
+                      ws=hip.flow_forward_interpolate_workspace(1, h, w, dev))
+        hip.flow_forward_interpolate(self._flow, h, w, ld_in=4, out=sc["delta"], ld_out=4, index=sc["index"], workspace=sc["ws"])
+        self.flow_index = sc["index"]
+        return sc["delta"].view(Pn, 4)
+
     @torch.no_grad()
-    def step(self, pair, end=False, frame_keys=None):
+    def step(self, pair, end=False, frame_keys=None, flow_init=None):
         """pair: float [1, 2, 3, H, W] in [-1, 1] on the GPU (previous, current), the next field of the stream.
-        Returns (flow_low [1,2,h,w], flow [1,2,H,W]).  end=True: the bank is cleared after the step."""
+        Returns (flow_low [1,2,h,w], flow [1,2,H,W]).  end=True: the bank and the kept flow are cleared after the step.
+        flow_init (warm_start=False only): the field's starting flow as net.forward takes it."""
         if not isinstance(pair, torch.Tensor) or pair.dim() != 5 or pair.shape[1] != 2:
             raise ValueError(f"pair must be [1,2,3,H,W], got {tuple(getattr(pair, 'shape', ()))}")
         size = (int(pair.shape[3]), int(pair.shape[4]))
         if self.entries and self.size != size:
             raise ValueError(f"the bank holds fields of {self.size[0]}x{self.size[1]}, this pair is {size[0]}x{size[1]}: "
                              f"reset() the stream before a clip of another size")
+        if self.flow_size is not None and self.flow_size != size:
+            raise ValueError(f"the stream holds the flow of a {self.flow_size[0]}x{self.flow_size[1]} field, this pair is "
+                             f"{size[0]}x{size[1]}: reset() the stream before a clip of another size")
+        if flow_init is not None and self.warm_start:
+            raise ValueError("a warm_start stream projects its own starting flow: flow_init is for warm_start=False")
         n = len(self.entries)
-        out = self.net._run_pairs(pair, frame_keys, self)
+        self.flow_index = None
+        if self.warm_start and self.flow_size is not None:       # (a field of this size has run: H, W are multiples of 8)
+            flow_init = self._projected_flow(size[0] // 8, size[1] // 8)
+        out = self.net._run_pairs(pair, frame_keys, self, flow_init)
         self.planes_in_use = n + 1
         if end:
             self.reset()

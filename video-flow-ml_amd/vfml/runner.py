@@ -219,15 +219,33 @@ def memory_frames(proc):
     return int(getattr(proc, "memory_frames", 0) or 0)
 
 
-def check_memory_job(memory, tile_mode, world):
+def warm_start(proc):
+    """Whether the processor's job loops start every field from the previous field's projected flow (MemFlowProcessor.warm_start)."""
+    return bool(getattr(proc, "warm_start", False))
+
+
+def streams(proc):
+    """Whether a job of this processor walks ONE stream in frame order (MemFlowProcessor.compute_optical_flow_stream): with a
+    memory bank above 0, or with the warm start on."""
+    return bool(memory_frames(proc) or warm_start(proc))
+
+
+def check_memory_job(memory, tile_mode, world, warm=False):
     """What a job with a memory bank cannot be: tiled (the bank is a whole frame's), or whole frames over several ranks (each
-    rank's shard would start from an empty bank, and the fields would depend on the number of ranks)."""
+    rank's shard would start from an empty bank, and the fields would depend on the number of ranks).  warm: the same two for
+    a job with the warm start - the projected flow is a whole frame's, and every rank's shard would start cold."""
     if memory and tile_mode:
         raise ValueError(f"MemFlow's memory bank (memory of {memory} fields) works on whole frames: --tile is not available "
                          f"with it (MemFlow never tiles anyway)")
     if memory and world > 1:
         raise ValueError(f"MemFlow's memory bank (memory of {memory} fields) carries from field to field: a job over "
                          f"{world} ranks would start every rank's shard from an empty bank; run it on one GPU")
+    if warm and tile_mode:
+        raise ValueError("MemFlow's warm start (a field starts from the previous field's projected flow) works on whole "
+                         "frames: --tile is not available with it (MemFlow never tiles anyway)")
+    if warm and world > 1:
+        raise ValueError(f"MemFlow's warm start carries the flow from field to field: a job over {world} ranks would start "
+                         f"every rank's shard cold, and the fields would depend on the number of ranks; run it on one GPU")
 
 
 def _fields_in_order(proc, clip, frame_indices, before=None):
@@ -235,8 +253,9 @@ def _fields_in_order(proc, clip, frame_indices, before=None):
     them (the tri-frame network, compute_optical_flow_resident_batch), else one call per field."""
     batch = getattr(proc, "compute_optical_flow_resident_batch", None)
     step = (getattr(proc, "TRI_BATCH", None) or getattr(proc, "PAIR_BATCH", 1)) if batch is not None else 1
-    if memory_frames(proc):
-        # MemFlow with its memory bank: one stream in frame order, a field per pass (field t reads field t-1's value map)
+    if streams(proc):
+        # MemFlow with its memory bank or the warm start: one stream in frame order, a field per pass (field t reads field
+        # t-1's value map, or starts from its flow)
         batch, step = proc.compute_optical_flow_stream, 1
     for k0 in range(0, len(frame_indices), step):
         chunk = frame_indices[k0:k0 + step]
@@ -362,9 +381,9 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     out: optional result array (rank 0, with collect): float32 [len(frame_indices), H, W, 2], filled and returned instead of a
     fresh one - a caller that times the job hands in memory it has already touched (at 8 ranks x 41 fields/s the result
     grows by 5 GB/s; first-touch page faults of a fresh array would be part of what is measured).
-    continue_stream (MemFlow with a memory bank): the job goes on where the processor's last one ended - its bank is kept while
-    the frames follow on in the same clip (MemFlowProcessor.compute_optical_flow_stream); otherwise a job starts with an
-    empty bank at its first frame."""
+    continue_stream (MemFlow with a memory bank or the warm start): the job goes on where the processor's last one ended - its
+    bank and kept flow stay while the frames follow on in the same clip (MemFlowProcessor.compute_optical_flow_stream);
+    otherwise a job starts with an empty bank, and cold, at its first frame."""
     frame_indices = list(frame_indices)
     if feeder is not None:
         clip = feeder.clip
@@ -372,7 +391,7 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     tiles = _tiles(proc, W, H, tile_mode)
     whole = len(tiles) == 1
     on_gpu = clip.is_cuda
-    check_memory_job(memory_frames(proc), not whole, world)
+    check_memory_job(memory_frames(proc), not whole, world, warm_start(proc))
     local = local_sink is not None or device_npz is not None
     if local and (not whole or collect or on_field is not None):
         raise ValueError("local_sink applies to whole-frame jobs and replaces collect / on_field")
@@ -415,8 +434,8 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
             if on_gpu:
                 torch.cuda.synchronize(dev)
         return None
-    if memory_frames(proc) and not continue_stream:
-        proc.begin_stream_job()                             # (not before: preparing buffers leaves the bank alone)
+    if streams(proc) and not continue_stream:
+        proc.begin_stream_job()                             # (not before: preparing buffers leaves the bank and the flow alone)
     side = torch.cuda.Stream(device=dev) if on_gpu and sink_here else None
     seq = getattr(proc, "sequence_length", 1)
 

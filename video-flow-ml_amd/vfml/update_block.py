@@ -32,9 +32,11 @@ def _put_flow(s):
     return dict(flow_a=s.flow4, ld_a=4, flow_b=s.G, ld_b=s.GLD, flow_b_off=s.MF + 124, fmt_b=s.AF)
 
 
-def init_coords(s, n):
+def init_coords(s, n, flow_init=None):
+    """coords1 = the grid, flow = 0; flow_init: f32 rows [n * Pn][4] (x, y, 0, 0) in cells that the recurrence starts from
+    instead (coords1 = grid + flow_init: the warm start of a MemFlow stream) - the same two launches, the second with a delta."""
     hip.coords_init(s.coords1, n, s.h, s.w)
-    hip.coords_update(s.coords1, None, n, s.h, s.w, **_put_flow(s))
+    hip.coords_update(s.coords1, flow_init, n, s.h, s.w, **_put_flow(s))
 
 
 def lookup(s, n, r0, tables=(), bidir=None, pyrs=None):
