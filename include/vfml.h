@@ -385,6 +385,25 @@ int vfml_corr_lookup_indirect_bidir(const float* const* table, const int32_t* hl
                                     int vol_tile, void* stream);
 int vfml_ptr_table_set(void* table, const void* const* ptrs, int n, void* stream);
 
+/* Level 0 of correlation pyramids on demand: in front of a lookup, compute the 128 x 64 tiles of the level-0 volumes that
+ * the lookup's windows will read and that are not there yet - instead of the dense level-0 GEMM of every frame pair, most
+ * of whose values no lookup ever reads.  The values are the ones that GEMM writes, bit for bit.
+ *   d, w_hi .. k_order : the dense level-0 call (vfml_conv2d_split's arguments: query rows of one frame as split rows,
+ *                     target planes of the other, out = the level-0 buffer, no out_t) of ANY one of the pyramids - it gives
+ *                     the shapes and the arithmetic, and must be a call the library runs on the resident-A walk of its GEMM
+ *                     form (one MFMA per product, f32 volume, at most 256 channels).  Its three pointers are not used:
+ *   cells           : DEVICE table read when the kernel runs (vfml_ptr_table_set), four 8-byte cells per (direction,
+ *                     centre), direction 1 starting dir_cells centres behind direction 0:
+ *                       [0] query frame's split rows   [1] target frame's hi plane (level 0)
+ *                       [2] the pyramid's level-0 buffer   [3] its bitmap: (rows / 128) x ceil(cout / 64 / 32) uint32,
+ *                     bit t of row tile m set = tile (m, t) is computed.  A new pair's bitmap is all zero.
+ *   coords .. vol_tile : as vfml_corr_lookup_indirect_bidir's, for `centres` query maps of h x w cells.
+ *   counter         : optional device cell: the number of tiles computed is added to it (tests, profiles). */
+int vfml_corr_level0_ensure(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale, int in_fmt,
+                            int out_fmt, int k_order, const void* const* cells, int centres, int dirs, int dir_cells,
+                            const float* coords, int ld_coords, int dir_coords, int h, int w, int radius, int vol_tile,
+                            uint32_t* counter, void* stream);
+
 /* Window set-up of the recurrent state, one launch: state is [ncentres * rows][ld_state] floats, centre frame c owns rows
  * c * rows .. (c + 1) * rows - 1.  `cells` is a DEVICE table of three 8-byte cells per centre frame, read when the kernel
  * runs (vfml_ptr_table_set writes them; a captured launch follows what they hold at replay):

@@ -94,7 +94,7 @@ class VideoFlowProcessor:
         if not self.core.is_model_loaded():
             raise RuntimeError("Model not loaded. Call load_model() first.")
 
-    def _flow_from_host_u8(self, frames, frame_idx):
+    def _flow_from_host_u8(self, frames, frame_idx, tile_crop=False):
         """The reference's host-array call (list of numpy frames in, numpy field out) without its per-call
         cost: the reference converts, stacks and uploads T float32 frames (124 MB at 1080p) for every
         field and T-1 of them are the frames of the previous call (:150-161).  Here every uint8 frame of
@@ -102,7 +102,9 @@ class VideoFlowProcessor:
         edit of a frame changes its key), uploaded once as uint8, and the engine's per-frame / per-pair
         caches are keyed on the same hash - so a sliding loop over host frames runs at the resident
         rate.  Same pixels, same /255, same network: bit-identical to the float path (tests).  Returns
-        None when the fast path does not apply (float frames, sizes that need padding, CPU)."""
+        None when the fast path does not apply (float frames, sizes that need padding, CPU).
+        tile_crop: the frames are the crops of one tile of a tiled job (they keep the dense level-0 build of their
+        correlation pyramids, like the resident path's tiles)."""
         model = self.core.model
         if not (str(self.device).startswith('cuda') and hasattr(model, "forward_u8")):
             return None
@@ -126,7 +128,8 @@ class VideoFlowProcessor:
                 while len(self._dev_frames) > HOST_FRAME_CACHE:
                     self._dev_frames.popitem(last=False)
         win = torch.stack([self._dev_frames[keys[i]] for i in ids])
-        flows, _ = model.forward_u8(win, return_lowres=False, frame_keys=[keys[i] for i in ids], pick_only=self.PICK_ONLY)
+        flows, _ = model.forward_u8(win, return_lowres=False, frame_keys=[keys[i] for i in ids], pick_only=self.PICK_ONLY,
+                                    dense_corr=tile_crop)
         return flows[0, flows.shape[1] // 2].permute(1, 2, 0).cpu().numpy()
 
     def compute_optical_flow(self, frames, frame_idx):
@@ -138,7 +141,7 @@ class VideoFlowProcessor:
         flow = self.core.compute_flow_from_tensor(self.prepare_frame_sequence(frames, frame_idx))
         return flow.permute(1, 2, 0).cpu().numpy()
 
-    def compute_optical_flow_with_progress(self, frames, frame_idx, tile_pbar=None):
+    def compute_optical_flow_with_progress(self, frames, frame_idx, tile_pbar=None, tile_crop=False):
         self._require_model()
 
         def step(desc, n=0, reset=False):
@@ -150,7 +153,7 @@ class VideoFlowProcessor:
                     tile_pbar.update(n)
 
         step("Preparing frames", reset=True)
-        fast = self._flow_from_host_u8(frames, frame_idx)
+        fast = self._flow_from_host_u8(frames, frame_idx, tile_crop)
         if fast is not None:
             step("Completed", 4)
             return fast
@@ -173,7 +176,7 @@ class VideoFlowProcessor:
                 overall_pbar.set_description(f"Tile {k + 1}/{len(tiles)} ({t['width']}x{t['height']})")
             crops = [self.extract_tile(f, t) for f in frames]
             full[t['y']:t['y'] + t['height'], t['x']:t['x'] + t['width']] = \
-                self.compute_optical_flow_with_progress(crops, frame_idx, tile_pbar)
+                self.compute_optical_flow_with_progress(crops, frame_idx, tile_pbar, tile_crop=True)
             if overall_pbar is not None:
                 overall_pbar.update(1)
         return full
@@ -212,7 +215,9 @@ class VideoFlowProcessor:
             # let the engine reuse its per-frame encoder outputs across the sliding windows
             tok = clip_token(clip)
             keys = [(tok, i, rect) for i in frame_ids]
-            flows, _ = model.forward_u8(win, return_lowres=False, frame_keys=keys, pick_only=self.PICK_ONLY)
+            # (a tiled job's crops keep the dense level-0 build of their correlation pyramids)
+            flows, _ = model.forward_u8(win, return_lowres=False, frame_keys=keys, pick_only=self.PICK_ONLY,
+                                        dense_corr=tile is not None)
             # the frame after this one is what a job asks for next: its window's new frame goes through the encoders
             # now, on a side stream beside this field's update iterations (vfml/network.py prefetch_frames)
             # (whole frames, or a tile when the caller walks a tile's frames before the next tile - vfml/runner.py sets

@@ -91,6 +91,9 @@ const SplitVariant* find_variant(const SplitVariant* rows, size_t n, const Split
 int variant_name(const SplitPlan& key, char* buf, int len);     // the kernel's name as rocprofv3 prints it
 const SplitVariant* tapx_variant(const SplitPlan& plan);        // conv_gemm_tapx.hip's table
 const SplitVariant* tapx_variant_at(int index);                 // its rows in order, null past the last
+// conv_gemm_split.hip: the arguments of a call planned on the resident-A walk (gemm_resident_walk.h), for corr_ensure.hip
+int prepare_resident_gemm(const vfml_conv_desc* d, const void* w_hi, const void* w_lo, int kp, float w_scale, int in_fmt,
+                          int out_fmt, int k_order, const char* who, SplitArgs* a);
 }  // namespace vfml_detail
 using vfml_detail::SplitArgs;
 using vfml_detail::SplitPlan;

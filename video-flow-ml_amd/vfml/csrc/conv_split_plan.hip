@@ -79,7 +79,7 @@ int plan_split(const SplitArgs& a, bool in16, int flags, int forced_tile, SplitP
     const bool reduced = a.fastk && !a.cswap && (a.nm == 1 || a.nm == 2 || a.nm == 5);
     *plan = dma_plan(2, 2, 2, 2, true, a.fastk, a.cswap, reduced ? a.nm : 3, false, a.out_h16);
     plan->add_rows = a.ksplit == 2;    // (two work items per tile, one per half of K: the halves are added afterwards)
-    // The 64-channel-step instantiations hold a second walk of the tile space (conv_gemm_split.hip, "resident-A walk"):
+    // The 64-channel-step instantiations hold a second walk of the tile space (gemm_resident_walk.h, "resident-A walk"):
     // taken by a 1x1 over ONE source whose 128-row tile can be staged whole and held in registers - the correlation
     // GEMMs.  Longer K (the MemFlow read-out), a split K axis, two sources and every other product keep the streaming walk.
     plan->resident = plan->nm == 5 && plan->fastk && !plan->cswap && a.pointwise && a.ksplit == 1 && a.c1 == 0 &&

@@ -3,6 +3,7 @@
 // (upsample), patches staged through LDS, results written as contiguous runs.
 #include <stdlib.h>
 #include "vfml_common.h"
+#include "corr_window.h"
 
 namespace {
 
@@ -45,13 +46,7 @@ __device__ __forceinline__ void lookup_rows(const LookupArgs& a, int q, int& map
   orow = qd * a.ld_out + (dir ? a.dir_out : 0);
 }
 
-// Position of texel (y, x) of a w-wide image stored as (1<<tws) x (1<<ths) tiles, tile after tile, each tile row-major
-// (tws = ths = 0: plain row-major).  A (2r+2)^2 lookup window then lies in ~8 128-byte lines instead of ~13 (ten 40-byte row
-// segments): the lookup is bound by the lines it drags in, not by the texels it uses (tools/exp/lookup_tiled.py).
-__device__ __forceinline__ int tiled_at(int y, int x, int w, int tws, int ths) {
-  const int tpr = (w + (1 << tws) - 1) >> tws;
-  return ((((y >> ths) * tpr + (x >> tws)) << (tws + ths)) + ((y & ((1 << ths) - 1)) << tws) + (x & ((1 << tws) - 1)));
-}
+// (tiled_at and window_origin: corr_window.h, shared with the on-demand level-0 pass)
 
 // grid_sample's bilinear mix nw*(1-fx)(1-fy) + ne*fx(1-fy) + sw*(1-fx)fy + se*fx*fy as ONE explicit chain of fused
 // multiply-adds, shared by both lookup kernels so that they agree bit for bit whatever hipcc would contract on its own.
@@ -97,9 +92,8 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_kernel(const Lo
       const float inv = 1.0f / (float)(1 << l);
       const float x = cx * inv, y = cy * inv;  // exact: power-of-two scale
       const float fx0 = floorf(x), fy0 = floorf(y);
-      // clamp before the int conversion so that wild coordinates cannot overflow
-      const int x0 = (int)fminf(fmaxf(fx0, -65536.f), 65536.f) - a.radius;
-      const int y0 = (int)fminf(fmaxf(fy0, -65536.f), 65536.f) - a.radius;
+      const int x0 = window_origin(x, a.radius);
+      const int y0 = window_origin(y, a.radius);
       const int xx = x0 + px, yy = y0 + py;
       float v = 0.f;
       if (xx >= 0 && xx < a.wl[l] && yy >= 0 && yy < a.hl[l])
@@ -217,8 +211,8 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_kernel(co
     const int wl = a.wl[ll], hl = a.hl[ll];
     const float inv = __builtin_bit_cast(float, (127 - l) << 23);      // 2^-l, exactly what 1.0f / (1 << l) is
     const float x = cx * inv, y = cy * inv;                            // exact: power-of-two scale
-    const int x0 = (int)fminf(fmaxf(floorf(x), -65536.f), 65536.f) - R;   // (clamped before the conversion: wild coordinates)
-    const int y0 = (int)fminf(fmaxf(floorf(y), -65536.f), 65536.f) - R;
+    const int x0 = window_origin(x, R);
+    const int y0 = window_origin(y, R);
     auto texel = [&](int px, int py, bool in, float& out, bool& ok) {
       const int xx = x0 + px, yy = y0 + py;
       ok = have && in && xx >= 0 && xx < wl && yy >= 0 && yy < hl;

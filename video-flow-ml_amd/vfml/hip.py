@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip", "warm_start.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "corr_ensure.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip", "warm_start.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -73,6 +73,7 @@ def build(force=False, verbose=False):
     """Compile the HIP sources for gfx950 into libvfml_hip.so (in-tree). Cross-compiles without a GPU."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     hdrs = [os.path.join(CSRC, "vfml_common.h"), os.path.join(CSRC, "conv_split_common.h"),
+            os.path.join(CSRC, "gemm_resident_walk.h"), os.path.join(CSRC, "corr_window.h"),
             os.path.join(CSRC, "jet_table.inc"), os.path.join(CSRC, "jpeg_tables.inc"), os.path.join(CSRC, "jpeg_decode_common.h"),
             os.path.join(CSRC, "jpeg_sync_steps.h"), os.path.join(CSRC, "deflate_code.h"), os.path.join(_HERE, "..", "..", "include", "vfml.h")]
     deps = srcs + hdrs
@@ -167,6 +168,8 @@ def lib():
                                                   c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                   c_int, c_int, c_int, c_int, c_void_p]
     L.vfml_ptr_table_set.argtypes = [c_void_p, POINTER(c_void_p), c_int, c_void_p]
+    L.vfml_corr_level0_ensure.argtypes = L.vfml_conv2d_split.argtypes[:5] + [c_int, c_int, c_int] + [
+        c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     L.vfml_window_seed.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     L.vfml_tapsum3x3_update.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p,
                                         c_int, c_void_p, c_int, c_int, c_void_p]
@@ -254,7 +257,7 @@ EXPORTS = [
     "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_attention_bank_planes_f16", "vfml_axpy_f32", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
-    "vfml_ptr_table_set", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
+    "vfml_ptr_table_set", "vfml_corr_level0_ensure", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_flow_forward_interpolate_workspace_bytes", "vfml_flow_forward_interpolate",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay", "vfml_text_draw",
@@ -692,6 +695,39 @@ def ptr_table_set(table, tensors):
         raise ValueError("ptr_table_set: table must be an int64 device tensor with room for the pointers")
     ptrs = (c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in tensors])     # (an int: the cell's value itself)
     _check(lib().vfml_ptr_table_set(c_void_p(table.data_ptr()), ptrs, n, _stream()), "vfml_ptr_table_set")
+
+
+def corr_bitmap_words(rows, cols):
+    """uint32 words of a level-0 bitmap (vfml_corr_level0_ensure): one bit per 128-row x 64-column tile, whole words per row tile."""
+    return ((rows + 127) // 128) * (((cols + 63) // 64 + 31) // 32)
+
+
+def corr_level0_ensure(rows, c, weight, level0, n_rows, n_cols, ldo, out_scale, cells, centres, dirs, dir_cells, coords,
+                       coords_off, ld_coords, dir_coords, h, w, radius, vol_tile, counter=None, in_fmt=FMT_S16, mfma=1):
+    """The level-0 tiles the next lookup reads and the pyramids do not hold yet (include/vfml.h vfml_corr_level0_ensure).
+    rows / weight / level0 (with c channels, n_rows x n_cols, ldo, out_scale, in_fmt, mfma): the dense level-0 call
+    `conv2d(rows, c, c, 1, 1, n_rows, weight, None, n_cols, 1, 1, level0, ldo, ...)` of any one of the pyramids; cells: an
+    int64 device tensor, four per (direction, centre) - query rows, target hi plane, level 0, bitmap (ptr_table_set);
+    coords .. vol_tile: as corr_lookup's; counter: an int32 device cell the number of computed tiles is added to."""
+    if not isinstance(weight, SplitWeight) or weight.lo is None:
+        raise ValueError("corr_level0_ensure: the target operand is a SplitWeight")
+    ndirs = 2 if dirs == 2 else 1
+    if not (cells.is_cuda and cells.dtype == torch.int64 and cells.numel() >= 4 * ((ndirs - 1) * dir_cells + centres)):
+        raise ValueError("corr_level0_ensure: cells must be an int64 device tensor, four per direction and centre frame")
+    if counter is not None and not (counter.is_cuda and counter.dtype == torch.int32):
+        raise ValueError("corr_level0_ensure: the counter is an int32 device tensor")
+    d = ConvDesc()
+    d.in0, d.c0, d.ld0 = _ptr(_dev(rows)), c, c
+    d.n, d.h, d.w = 1, 1, n_rows
+    d.cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w = n_cols, 1, 1, 1, 0, 0
+    d.out, d.ldo = _ptr(_dev(level0)), ldo
+    d.epilogue, d.split, d.out_scale = EPI_NONE, 0, out_scale
+    d.flags = {3: 0, 2: CONV_MFMA2, 1: CONV_MFMA1}[mfma]
+    _check(lib().vfml_corr_level0_ensure(ctypes.byref(d), c_void_p(weight.hi.data_ptr()), c_void_p(weight.lo.data_ptr()),
+                                         weight.kp, weight.scale, in_fmt, FMT_F32, weight.order, c_void_p(cells.data_ptr()),
+                                         centres, ndirs, dir_cells, _ptr(_dev(coords), coords_off), ld_coords, dir_coords, h, w,
+                                         radius, vol_tile, c_void_p(counter.data_ptr()) if counter is not None else None,
+                                         _stream()), "vfml_corr_level0_ensure")
 
 
 SEED_NONE, SEED_LOAD, SEED_STORE = 0, 1, 2

@@ -956,7 +956,7 @@ class MOFNetHIP(_Holder):
         return self._run(src.contiguous(), src.shape[0], src.shape[2], src.shape[3], return_lowres)
 
     @torch.no_grad()
-    def forward_u8(self, frames, return_lowres=True, frame_keys=None, tri_batch=False, pick_only=False):
+    def forward_u8(self, frames, return_lowres=True, frame_keys=None, tri_batch=False, pick_only=False, dense_corr=False):
         """frames: uint8 [N, H, W, 3] RGB on the GPU; /255 happens in the K1 kernel (same fp32 ops
         as the reference's host-side conversion), saving the 4x larger float upload.
 
@@ -973,7 +973,10 @@ class MOFNetHIP(_Holder):
 
         pick_only (with return_lowres=False): return only the flow the reference takes from the output,
         `[0, shape[1]//2]` = the backward flow of the first centre frame, as [1, 1, 2, H, W]; the last
-        iterations then skip the centre frames that can no longer influence it (same bits for that flow)."""
+        iterations then skip the centre frames that can no longer influence it (same bits for that flow).
+
+        dense_corr: build every correlation pyramid's level 0 whole, whatever `corr_on_demand` says (the crops of a tiled
+        job; same bits)."""
         if not (isinstance(frames, torch.Tensor) and frames.is_cuda and frames.dtype == torch.uint8
                 and frames.dim() == 4 and frames.shape[3] == 3):
             raise ValueError("forward_u8 expects a uint8 [N,H,W,3] device tensor")
@@ -982,7 +985,7 @@ class MOFNetHIP(_Holder):
         if tri_batch and not self.tri_frame:
             raise ValueError("tri_batch applies to tri-frame (BOF) networks")
         return self._run(frames.contiguous(), frames.shape[0], frames.shape[1], frames.shape[2], return_lowres,
-                         frame_keys, tri_batch, pick_only and not return_lowres)
+                         frame_keys, tri_batch, pick_only and not return_lowres, dense_corr)
 
     # ------------------------------------------------------------------ per-frame encoder cache
     FEATURE_CACHE_FRAMES = 12
@@ -1119,21 +1122,59 @@ class MOFNetHIP(_Holder):
         return types.SimpleNamespace(L=L, AF=AF, hl=hl, wl=wl, Sl=Sl, VT=VT, Nl=Nl, Pv=Pv, TILE=TILE, vol16=mask, VF=VF,
                                      VFl=VFl, ldl=ldl, psz=psz)
 
-    def _window_pyramids(self, feats, keys, N, geo, dev):
+    corr_on_demand = True    # False: every pyramid's level 0 is built whole by the dense GEMM (tests, A/B runs)
+
+    def _corr_scale(self, AF):
+        scale = 1.0 / float(self.cfg.feat_dim) ** 0.5
+        if AF == hip.FMT_S16:
+            scale /= self.FMAP_ROW_SCALE       # the split-row query features carry a factor 16
+        return scale
+
+    def _level0_on_demand(self, keys, N, geo, dense_corr=False):
+        """Whether a window's pyramids get their level 0 tile by tile, in front of the lookups that read it
+        (vfml_corr_level0_ensure), instead of whole: keyed MOF windows of the mixed plan's arithmetic - the GEMM form with one
+        MFMA per product and an f32 level 0, the lookups of both directions as one launch."""
+        return (self.corr_on_demand and not dense_corr and keys is not None and self._split() and not self.tri_frame
+                and not self.gma and not self.sk and geo.AF == hip.FMT_S16 and geo.Pv % 4 == 0 and geo.Nl[0] >= 1024
+                and geo.VT is not None and geo.Pv == geo.Nl[0] and geo.VFl[0] == hip.FMT_F32 and self._nm("corr") == 1
+                and self.cfg.feat_dim <= 256 and 2 * (N - 2) <= 8 and (geo.Nl[0] + 63) // 64 <= 2048)
+
+    @staticmethod
+    def _pyramid_bitmap(pyr, L):
+        """The bitmap of an on-demand pyramid's level 0 (which 128 x 64 tiles are computed): one more buffer of the pyramid's
+        entry behind its L levels (hip.corr_bitmap_words words), so it is recycled and freed with them; it is cleared
+        whenever the buffers are handed to a new pair."""
+        return pyr[L].view(torch.int32)
+
+    def corr_tiles_computed(self, reset=True):
+        """Level-0 tiles the on-demand passes computed since the last reset (tests, profiles: this synchronises)."""
+        count = self._ws.get("ensure_count")
+        if count is None:
+            return 0
+        n = int(count.item())
+        if reset:
+            count.zero_()
+        return n
+
+    def _window_pyramids(self, feats, keys, N, geo, dev, on_demand=False):
         """K3/K4: the correlation pyramids of a window, one per problem (query frame -> target frame): level l is one GEMM of
         the query frame's features against the 2^l-pooled features of the target frame.  A pyramid depends on its two frames
         only, so with frame keys it is kept across windows: consecutive sliding windows share 2(N-3) of their 2(N-2)
-        problems.  Returns {"f": [...], "b": [...]} (per centre frame, a list of level buffers)."""
+        problems.  Returns {"f": [...], "b": [...]} (per centre frame, a list of level buffers).
+        on_demand (_level0_on_demand): level 0 is not built here - neither the GEMM nor its transposed twin is launched; the
+        pyramid gets an empty bitmap and the iterations fill the tiles their lookups read (update_block.ensure_level0)."""
         D, L = self.cfg.feat_dim, geo.L
         AF, VFl, Nl, Pv, ldl, psz = geo.AF, geo.VFl, geo.Nl, geo.Pv, geo.ldl, geo.psz
-        scale = 1.0 / float(D) ** 0.5
-        if AF == hip.FMT_S16:
-            scale /= self.FMAP_ROW_SCALE       # the split-row query features carry a factor 16
+        scale = self._corr_scale(AF)
         lim = 2 * (N - 2) + 2
         pyrs = {"f": [], "b": []}
+        od = ("od",) if on_demand else ()      # (a pyramid without its level 0 is not the dense one: its own cache entry)
+        if on_demand:
+            psz = psz + [hip.corr_bitmap_words(Pv, Nl[0])]      # (the bitmap travels with the level buffers)
+        first = 1 if on_demand else 0
         for c in range(1, N - 1):
             for d, tgt in (("f", c + 1), ("b", c - 1)):
-                pk = ("p", keys[c], keys[tgt]) if keys is not None else None
+                pk = ("p", keys[c], keys[tgt]) + od if keys is not None else None
                 if pk is not None and self.gma and d == "b" and keys[c] == keys[tgt]:
                     # a frame against ITSELF (a window clamped at an end of the clip repeats a frame): the backward problem's
                     # level 0 adds its cross terms in the order of a transposed forward volume (VFML_CONV_SWAP_CROSS below),
@@ -1158,7 +1199,7 @@ class MOFNetHIP(_Holder):
                     # builds its two new pyramids with one 32400 x 32400 GEMM instead of two.
                     # (a backward problem's level 0 computed directly uses VFML_CONV_SWAP_CROSS, the addition
                     # order of a transposed forward volume: both routes give the same bits)
-                    rk = ("p", keys[tgt], keys[c]) if pk is not None else None
+                    rk = ("p", keys[tgt], keys[c]) + od if pk is not None else None
                     gemm_form = AF == hip.FMT_S16 and Pv % 4 == 0 and Nl[0] >= 1024
                     dual = rk is not None and d == "f" and gemm_form and ("p", rk) not in self._feat_cache
                     rev = None
@@ -1166,7 +1207,7 @@ class MOFNetHIP(_Holder):
                         rev = self._pyramid_buffers(psz, dev, limit=lim)
                         self._cache_put("p", rk, rev, limit=lim)
                     cnm = self._nm("corr") if self._split() else 3
-                    for l in range(L):
+                    for l in range(first, L):
                         # (one MFMA per product is symmetric in its operands: no swapped cross terms to order)
                         hip.conv2d(feats[c][0], D, D, 1, 1, Pv, feats[tgt][1][l], None, Nl[l], 1, 1, pyr[l],
                                    ldl[l], out_scale=scale, in_fmt=AF, out_fmt=VFl[l],
@@ -1177,8 +1218,27 @@ class MOFNetHIP(_Holder):
                         for l in range(1, L):
                             hip.conv2d(feats[tgt][0], D, D, 1, 1, Pv, feats[c][1][l], None, Nl[l], 1, 1, rev[l],
                                        ldl[l], out_scale=scale, in_fmt=AF, out_fmt=VFl[l], mfma=cnm)
+                    if on_demand:
+                        # (on the stream that builds the pooled levels, behind whatever read these buffers' last pair)
+                        for p in (pyr, rev) if dual else (pyr,):
+                            self._pyramid_bitmap(p, L).zero_()
                 pyrs[d].append(pyr)
         return pyrs
+
+    def _ensure_plan(self, pyrs, feats, N, geo, dev):
+        """What the on-demand level-0 passes of a window need (update_block.ensure_level0): the device cells that name, per
+        direction and centre, the query frame's rows, the target frame's level-0 hi plane, the level-0 buffer and its bitmap."""
+        M = N - 2
+        cells = self._buf("ensure_cells", 64, dev, torch.int64)
+        ptrs = []
+        for d, step in (("f", 1), ("b", -1)):
+            for i, c in enumerate(range(1, N - 1)):
+                pyr = pyrs[d][i]
+                ptrs += [feats[c][0], feats[c + step][1][0].hi, pyr[0], self._pyramid_bitmap(pyr, geo.L)]
+        hip.ptr_table_set(cells, ptrs)
+        count = self._buf("ensure_count", 1, dev, torch.int32, zero=True)     # (through _buf: captured launches hold its address)
+        return types.SimpleNamespace(cells=cells, M=M, rows=feats[1][0], weight=feats[2][1][0], level0=pyrs["f"][0][0],
+                                     D=self.cfg.feat_dim, scale=self._corr_scale(geo.AF), counter=count)
 
     def _frame_features(self, src, sel, keys, H, W, P, dev, L, hl, wl, Sl, vt=None):
         """Feature map + target pyramid of frames `sel` of the window.
@@ -1372,12 +1432,12 @@ class MOFNetHIP(_Holder):
         # (at most 8 maps)
         if 2 * M <= 8 and 2 * M * L <= 48:
             tab_fb = self._buf("pyr_table_fb", 64, dev, torch.int64)
-            hip.ptr_table_set(tab_fb, [p for d in ("f", "b") for m in pyrs[d] for p in m])
+            hip.ptr_table_set(tab_fb, [p for d in ("f", "b") for m in pyrs[d] for p in m[:L]])
             return (tab_fb,), (2, cor_p, M)
         tab_f = self._buf("pyr_table_f", 64, dev, torch.int64)
         tab_b = self._buf("pyr_table_b", 64, dev, torch.int64)
-        hip.ptr_table_set(tab_f, [p for m in pyrs["f"] for p in m])
-        hip.ptr_table_set(tab_b, [p for m in pyrs["b"] for p in m])
+        hip.ptr_table_set(tab_f, [p for m in pyrs["f"] for p in m[:L]])
+        hip.ptr_table_set(tab_b, [p for m in pyrs["b"] for p in m[:L]])
         return (tab_f, tab_b), None
 
     def _gma_readout(self, s, win, ng):
@@ -1405,6 +1465,8 @@ class MOFNetHIP(_Holder):
                 ub.flow_half(s, ne, r0)
                 join = torch.cuda.Event()
                 join.record()
+        if win.ensure is not None:
+            ub.ensure_level0(s, ne, r0, win.ensure)     # the level-0 tiles this lookup reads and the pyramids lack
         ub.lookup(s, ne, r0, win.tables, win.bidir)
         ub.convc1(s, ne, r0)
         ub.convc2(s, ne, r0)
@@ -1442,7 +1504,7 @@ class MOFNetHIP(_Holder):
         blk(f"{ub}.flow_head", P, G, GLD, s.HH, ng, h, w, s.delta, 4, 0, ws, out_fmt=hip.FMT_F32)
         update_block.update_coords(s, ng)
 
-    def _run(self, src, N, H, W, return_lowres, frame_keys=None, tri_batch=False, pick_only=False):
+    def _run(self, src, N, H, W, return_lowres, frame_keys=None, tri_batch=False, pick_only=False, dense_corr=False):
         cfg = self.cfg
         if N < 3:
             raise ValueError(f"need at least 3 frames, got {N}")
@@ -1479,7 +1541,8 @@ class MOFNetHIP(_Holder):
             # K1 + K2: feature maps and pooled target pyramids, per frame (cached across windows)
             feats = self._frame_features(src, list(range(N)), keys, H, W, P, dev, L, geo.hl, geo.wl, geo.Sl, vt=geo.VT)
             # K3/K4 correlation pyramids, one per problem (query frame -> target frame)
-            pyrs = self._window_pyramids(feats, keys, N, geo, dev)
+            on_demand = self._level0_on_demand(keys, N, geo, dense_corr)
+            pyrs = self._window_pyramids(feats, keys, N, geo, dev, on_demand)
             s = self._window_state(P, dev, M, h, w, geo, R, AF, cor_p)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
@@ -1494,6 +1557,7 @@ class MOFNetHIP(_Holder):
             win.gates = self._gate_addends(ctx, dev, Pn, M)
             win.sk_ws = self._sk_workspace(MP, dev) if self.sk else None
             win.tables, win.bidir = self._pyramid_tables(pyrs, dev, M, L, cor_p)
+            win.ensure = self._ensure_plan(pyrs, feats, N, geo, dev) if on_demand else None
             no, nflows = (1, 1) if short else (M, 2 * M)
             up_fixed = self._buf("up_out", nflows * H * W * 2, dev)
             mask = self._buf("mask", MP * 1152, dev)
@@ -1539,7 +1603,7 @@ class MOFNetHIP(_Holder):
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), geo.vol16,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), win.warm, win.att_slots)
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), win.warm, win.att_slots, on_demand)
             if self.sk:
                 gkey += ("sk",)
             self._pre_body = torch.cuda.Event()

@@ -55,6 +55,17 @@ def lookup(s, n, r0, tables=(), bidir=None, pyrs=None):
                         s.ld_corr, out_fmt=s.AF, table=tab[t0:], nmaps=n, vol_fmt=g.VF, vol_tile=g.TILE, bidir=bidir)
 
 
+def ensure_level0(s, n, r0, en):
+    """In front of `lookup` on the same n query maps from row r0 on, both directions: compute the level-0 tiles of their
+    pyramids that the lookup's windows read and that are not there yet (hip.corr_level0_ensure).  en: the window's record -
+    cells (four per direction and centre, the second direction M centres behind the first), the dense level-0 call of one
+    of the pyramids (rows, weight, level0, D, scale) and the counter."""
+    g = s.geo
+    c0 = r0 // s.Pn
+    hip.corr_level0_ensure(en.rows, en.D, en.weight, en.level0, g.Pv, g.Nl[0], g.ldl[0], en.scale, en.cells[4 * c0:], n, 2,
+                           en.M, s.coords1, r0 * 4, 4, 2, g.hl[0], g.wl[0], s.R, g.TILE, counter=en.counter, in_fmt=s.AF)
+
+
 # ---------------------------------------------------------------------- motion encoder
 def convc1(s, n, r0):
     wgt, b = s.P[f"{UB}.encoder.convc1"]
