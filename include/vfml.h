@@ -404,6 +404,34 @@ int vfml_corr_level0_ensure(const vfml_conv_desc* d, const void* w_hi, const voi
                             const float* coords, int ld_coords, int dir_coords, int h, int w, int radius, int vol_tile,
                             uint32_t* counter, void* stream);
 
+/* The same for a list of levels of the pyramids, in ONE launch: level 0 and / or pooled levels whose dense GEMM stores far
+ * more than the lookups read (1080p: 6 % of level 1 and 16 % of level 2 are read).  A work unit - (direction, centre, row
+ * tile) - goes through the listed levels in ascending order; per level the window of a query lies around its coordinate
+ * times 2^-level in the level image, exactly as the lookup places it.
+ *   levels[i]       : d, w_hi, w_lo, kp, w_scale, out_fmt - the dense call of that level of ANY one of the pyramids, under
+ *                     the conditions of vfml_corr_level0_ensure (a level stored as f16, with fewer than 1024 columns or more
+ *                     than 2048 column tiles is refused, never run some other way); level - its number in the pyramid;
+ *                     h, w - its image.  Every level has the query map's rows.  At most three levels.
+ *   cells           : 1 + 3 * nlevels cells per (direction, centre): [0] the query frame's split rows, then per listed level
+ *                     [1 + 3i] the target frame's hi plane of that level  [2 + 3i] the pyramid's buffer of that level
+ *                     [3 + 3i] that level's bitmap (rows / 128) x ceil(cout / 64 / 32) uint32.  One level: the layout above.
+ *   h, w            : the query map (the level-0 image), which orders the volumes' rows, listed or not.
+ *   counters        : optional device array with one cell per pyramid level: the tiles computed at level l are added to
+ *                     counters[l].
+ * Everything else as vfml_corr_level0_ensure, which is this call with the one level 0. */
+typedef struct vfml_corr_level_desc {
+  const vfml_conv_desc* d;
+  const void* w_hi;
+  const void* w_lo;
+  int32_t kp;
+  float w_scale;
+  int32_t out_fmt, level, h, w;
+} vfml_corr_level_desc;
+int vfml_corr_levels_ensure(const vfml_corr_level_desc* levels, int nlevels, int in_fmt, int k_order,
+                            const void* const* cells, int centres, int dirs, int dir_cells, const float* coords,
+                            int ld_coords, int dir_coords, int h, int w, int radius, int vol_tile, uint32_t* counters,
+                            void* stream);
+
 /* Window set-up of the recurrent state, one launch: state is [ncentres * rows][ld_state] floats, centre frame c owns rows
  * c * rows .. (c + 1) * rows - 1.  `cells` is a DEVICE table of three 8-byte cells per centre frame, read when the kernel
  * runs (vfml_ptr_table_set writes them; a captured launch follows what they hold at replay):

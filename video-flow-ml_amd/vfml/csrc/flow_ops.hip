@@ -46,7 +46,7 @@ __device__ __forceinline__ void lookup_rows(const LookupArgs& a, int q, int& map
   orow = qd * a.ld_out + (dir ? a.dir_out : 0);
 }
 
-// (tiled_at and window_origin: corr_window.h, shared with the on-demand level-0 pass)
+// (tiled_at, level_coord and window_origin: corr_window.h, shared with the on-demand pass)
 
 // grid_sample's bilinear mix nw*(1-fx)(1-fy) + ne*fx(1-fy) + sw*(1-fx)fy + se*fx*fy as ONE explicit chain of fused
 // multiply-adds, shared by both lookup kernels so that they agree bit for bit whatever hipcc would contract on its own.
@@ -89,8 +89,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_kernel(const Lo
       const int l = e / psz;
       const int idx = e - l * psz;
       const int py = idx / side, px = idx - py * side;
-      const float inv = 1.0f / (float)(1 << l);
-      const float x = cx * inv, y = cy * inv;  // exact: power-of-two scale
+      const float x = level_coord(cx, l), y = level_coord(cy, l);  // exact: power-of-two scale
       const float fx0 = floorf(x), fy0 = floorf(y);
       const int x0 = window_origin(x, a.radius);
       const int y0 = window_origin(y, a.radius);
@@ -209,8 +208,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_kernel(co
     const int ES = v16 ? 2 : 4;              // bytes per texel of this level
     const char* base = reinterpret_cast<const char*>(pl[l]) + (int64_t)qrow * a.ld[ll] * ES;
     const int wl = a.wl[ll], hl = a.hl[ll];
-    const float inv = __builtin_bit_cast(float, (127 - l) << 23);      // 2^-l, exactly what 1.0f / (1 << l) is
-    const float x = cx * inv, y = cy * inv;                            // exact: power-of-two scale
+    const float x = level_coord(cx, l), y = level_coord(cy, l);        // exact: power-of-two scale (a constant here)
     const int x0 = window_origin(x, R);
     const int y0 = window_origin(y, R);
     auto texel = [&](int px, int py, bool in, float& out, bool& ok) {
@@ -243,8 +241,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_kernel(co
   wave_lds_sync();
   if (lane < a.levels * WIN) {
     const int l = lane / WIN, i = lane - l * WIN;          // i: x offset index; the lane walks j, the y offset index
-    const float inv = __builtin_bit_cast(float, (127 - l) << 23);
-    const float x = cx * inv, y = cy * inv;
+    const float x = level_coord(cx, l), y = level_coord(cy, l);
     const float fx = x - floorf(x), fy = y - floorf(y);
     const float wx0 = 1.f - fx, wy0 = 1.f - fy;
     const float w00 = wx0 * wy0, w10 = fx * wy0, w01 = wx0 * fy, w11 = fx * fy;

@@ -57,6 +57,12 @@ class ConvDesc(ctypes.Structure):
     ]
 
 
+class CorrLevelDesc(ctypes.Structure):
+    """Mirror of `vfml_corr_level_desc` (include/vfml.h): one level of vfml_corr_levels_ensure."""
+    _fields_ = [("d", POINTER(ConvDesc)), ("w_hi", c_void_p), ("w_lo", c_void_p), ("kp", c_int32), ("w_scale", c_float),
+                ("out_fmt", c_int32), ("level", c_int32), ("h", c_int32), ("w", c_int32)]
+
+
 # Every source is built without the SLP vectoriser.  Left on, it pairs adjacent scalar f32 multiplies / adds into
 # v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32; where such a packed op was the FIRST reader of a ds_read result, straight behind
 # the s_waitcnt that covers it, the correlation lookup read a stale register in lanes 48-63 whenever one of this library's
@@ -170,6 +176,8 @@ def lib():
     L.vfml_ptr_table_set.argtypes = [c_void_p, POINTER(c_void_p), c_int, c_void_p]
     L.vfml_corr_level0_ensure.argtypes = L.vfml_conv2d_split.argtypes[:5] + [c_int, c_int, c_int] + [
         c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.vfml_corr_levels_ensure.argtypes = [POINTER(CorrLevelDesc), c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     L.vfml_window_seed.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
     L.vfml_tapsum3x3_update.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, ctypes.c_int64, c_void_p, c_void_p,
                                         c_int, c_void_p, c_int, c_int, c_void_p]
@@ -257,7 +265,7 @@ EXPORTS = [
     "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_attention_bank_planes_f16", "vfml_axpy_f32", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
-    "vfml_ptr_table_set", "vfml_corr_level0_ensure", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
+    "vfml_ptr_table_set", "vfml_corr_level0_ensure", "vfml_corr_levels_ensure", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_flow_forward_interpolate_workspace_bytes", "vfml_flow_forward_interpolate",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
     "vfml_flow_colorize", "vfml_compose_frame", "vfml_flow_decode", "vfml_flow_diff_overlay", "vfml_text_draw",
@@ -688,17 +696,24 @@ def to_s16(src, rows, c, ld_src, dst, ld_dst, src_off=0, dst_off=0, scale=1.0):
                              _stream()), "vfml_to_s16")
 
 
+PTR_TABLE_MAX = 48      # pointers per vfml_ptr_table_set launch
+
+
 def ptr_table_set(table, tensors):
     """Write the device pointers of `tensors` into `table` (an int64 device tensor), asynchronously on the current stream."""
     n = len(tensors)
     if not (table.is_cuda and table.dtype == torch.int64 and table.numel() >= n):
         raise ValueError("ptr_table_set: table must be an int64 device tensor with room for the pointers")
-    ptrs = (c_void_p * n)(*[t if isinstance(t, int) else t.data_ptr() for t in tensors])     # (an int: the cell's value itself)
-    _check(lib().vfml_ptr_table_set(c_void_p(table.data_ptr()), ptrs, n, _stream()), "vfml_ptr_table_set")
+    vals = [t if isinstance(t, int) else t.data_ptr() for t in tensors]     # (an int: the cell's value itself)
+    for at in range(0, n, PTR_TABLE_MAX):       # (a launch carries the values as its arguments: 48 of them)
+        part = vals[at:at + PTR_TABLE_MAX]
+        _check(lib().vfml_ptr_table_set(c_void_p(table.data_ptr() + 8 * at), (c_void_p * len(part))(*part), len(part), _stream()),
+               "vfml_ptr_table_set")
 
 
 def corr_bitmap_words(rows, cols):
-    """uint32 words of a level-0 bitmap (vfml_corr_level0_ensure): one bit per 128-row x 64-column tile, whole words per row tile."""
+    """uint32 words of a level's bitmap (vfml_corr_level0_ensure, vfml_corr_levels_ensure): one bit per 128-row x 64-column
+    tile, whole words per row tile."""
     return ((rows + 127) // 128) * (((cols + 63) // 64 + 31) // 32)
 
 
@@ -728,6 +743,46 @@ def corr_level0_ensure(rows, c, weight, level0, n_rows, n_cols, ldo, out_scale, 
                                          centres, ndirs, dir_cells, _ptr(_dev(coords), coords_off), ld_coords, dir_coords, h, w,
                                          radius, vol_tile, c_void_p(counter.data_ptr()) if counter is not None else None,
                                          _stream()), "vfml_corr_level0_ensure")
+
+
+def corr_levels_ensure(rows, c, n_rows, levels, out_scale, cells, centres, dirs, dir_cells, coords, coords_off, ld_coords,
+                       dir_coords, h, w, radius, vol_tile, counters=None, in_fmt=FMT_S16, mfma=1):
+    """The tiles of several pyramid levels that the next lookup reads and the pyramids do not hold yet, in one launch
+    (include/vfml.h vfml_corr_levels_ensure).  rows (c channels, n_rows of them): the query rows of any one of the pyramids;
+    levels: a list of (level, weight, volume, n_cols, ldo, h_l, w_l) in ascending order of level - the dense call
+    `conv2d(rows, c, c, 1, 1, n_rows, weight, None, n_cols, 1, 1, volume, ldo, ...)` of that level and its image; cells: an
+    int64 device tensor, 1 + 3 * len(levels) per (direction, centre) - query rows, then per level target hi plane, level
+    buffer, bitmap (corr_bitmap_words(n_rows, n_cols) words); h, w: the query map; counters: an int32 device tensor, cell l
+    counts the tiles computed at level l.  Everything else as corr_level0_ensure."""
+    ndirs = 2 if dirs == 2 else 1
+    per = 1 + 3 * len(levels)
+    if not levels or any(not isinstance(lv[1], SplitWeight) or lv[1].lo is None for lv in levels):
+        raise ValueError("corr_levels_ensure: every level's target operand is a SplitWeight")
+    if not (cells.is_cuda and cells.dtype == torch.int64 and cells.numel() >= per * ((ndirs - 1) * dir_cells + centres)):
+        raise ValueError("corr_levels_ensure: cells must be an int64 device tensor, 1 + 3 per level for each direction and "
+                         "centre frame")
+    if counters is not None and not (counters.is_cuda and counters.dtype == torch.int32
+                                     and counters.numel() > max(lv[0] for lv in levels)):
+        raise ValueError("corr_levels_ensure: the counters are an int32 device tensor with a cell per pyramid level")
+    descs = (ConvDesc * len(levels))()
+    lvs = (CorrLevelDesc * len(levels))()
+    for i, (level, weight, volume, n_cols, ldo, hl, wl) in enumerate(levels):
+        d = descs[i]
+        d.in0, d.c0, d.ld0 = _ptr(_dev(rows)), c, c
+        d.n, d.h, d.w = 1, 1, n_rows
+        d.cout, d.kh, d.kw, d.stride, d.pad_h, d.pad_w = n_cols, 1, 1, 1, 0, 0
+        d.out, d.ldo = _ptr(_dev(volume)), ldo
+        d.epilogue, d.split, d.out_scale = EPI_NONE, 0, out_scale
+        d.flags = {3: 0, 2: CONV_MFMA2, 1: CONV_MFMA1}[mfma]
+        lv = lvs[i]
+        lv.d = ctypes.pointer(d)
+        lv.w_hi, lv.w_lo, lv.kp, lv.w_scale = weight.hi.data_ptr(), weight.lo.data_ptr(), weight.kp, weight.scale
+        lv.out_fmt, lv.level, lv.h, lv.w = FMT_F32, level, hl, wl
+    order = levels[0][1].order
+    _check(lib().vfml_corr_levels_ensure(lvs, len(levels), in_fmt, order, c_void_p(cells.data_ptr()), centres, ndirs, dir_cells,
+                                         _ptr(_dev(coords), coords_off), ld_coords, dir_coords, h, w, radius, vol_tile,
+                                         c_void_p(counters.data_ptr()) if counters is not None else None, _stream()),
+           "vfml_corr_levels_ensure")
 
 
 SEED_NONE, SEED_LOAD, SEED_STORE = 0, 1, 2

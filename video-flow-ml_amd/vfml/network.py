@@ -1122,7 +1122,10 @@ class MOFNetHIP(_Holder):
         return types.SimpleNamespace(L=L, AF=AF, hl=hl, wl=wl, Sl=Sl, VT=VT, Nl=Nl, Pv=Pv, TILE=TILE, vol16=mask, VF=VF,
                                      VFl=VFl, ldl=ldl, psz=psz)
 
-    corr_on_demand = True    # False: every pyramid's level 0 is built whole by the dense GEMM (tests, A/B runs)
+    corr_on_demand = True    # False: every level of every pyramid is built whole by the dense GEMMs (tests, A/B runs)
+    # Pooled levels that are computed on demand too, where level 0 is and the level qualifies (_on_demand_levels).  Level 2
+    # works the same way ((1, 2)) but its gain at 1080p stayed inside the run-to-run noise: off.
+    corr_on_demand_levels = (1,)
 
     def _corr_scale(self, AF):
         scale = 1.0 / float(self.cfg.feat_dim) ** 0.5
@@ -1139,39 +1142,65 @@ class MOFNetHIP(_Holder):
                 and geo.VT is not None and geo.Pv == geo.Nl[0] and geo.VFl[0] == hip.FMT_F32 and self._nm("corr") == 1
                 and self.cfg.feat_dim <= 256 and 2 * (N - 2) <= 8 and (geo.Nl[0] + 63) // 64 <= 2048)
 
+    def _on_demand_levels(self, on_demand, geo):
+        """The levels of a window's pyramids that are not built but filled tile by tile (vfml_corr_levels_ensure), ascending:
+        none, or level 0 and those of corr_on_demand_levels whose dense GEMM runs on the same walk - an f32 level of at
+        least 1024 columns (and at most 2048 column tiles); at most three in all."""
+        if not on_demand:
+            return ()
+        more = [l for l in range(1, geo.L) if l in self.corr_on_demand_levels and geo.VFl[l] == hip.FMT_F32
+                and geo.Nl[l] >= 1024 and (geo.Nl[l] + 63) // 64 <= 2048]
+        return (0,) + tuple(more[:2])
+
+    @staticmethod
+    def _bitmap_sections(geo, levels):
+        """Where each on-demand level's bitmap starts in the pyramid's one bitmap buffer (level 0's first), and the total."""
+        at, n = {}, 0
+        for l in levels:
+            at[l] = n
+            n += hip.corr_bitmap_words(geo.Pv, geo.Nl[l])
+        return at, n
+
     @staticmethod
     def _pyramid_bitmap(pyr, L):
-        """The bitmap of an on-demand pyramid's level 0 (which 128 x 64 tiles are computed): one more buffer of the pyramid's
-        entry behind its L levels (hip.corr_bitmap_words words), so it is recycled and freed with them; it is cleared
-        whenever the buffers are handed to a new pair."""
+        """The bitmaps of an on-demand pyramid (which 128 x 64 tiles of its on-demand levels are computed, a section per
+        level: _bitmap_sections): one more buffer of the pyramid's entry behind its L levels, so it is recycled and freed
+        with them; it is cleared whenever the buffers are handed to a new pair."""
         return pyr[L].view(torch.int32)
 
-    def corr_tiles_computed(self, reset=True):
-        """Level-0 tiles the on-demand passes computed since the last reset (tests, profiles: this synchronises)."""
+    def corr_level_tiles_computed(self, reset=True):
+        """Tiles the on-demand passes computed since the last reset, per pyramid level (tests, profiles: this synchronises)."""
         count = self._ws.get("ensure_count")
         if count is None:
-            return 0
-        n = int(count.item())
+            return [0, 0, 0, 0]
+        n = [int(v) for v in count.tolist()]
         if reset:
             count.zero_()
         return n
 
-    def _window_pyramids(self, feats, keys, N, geo, dev, on_demand=False):
+    def corr_tiles_computed(self, reset=True):
+        """Level-0 tiles the on-demand passes computed since the last reset (tests, profiles: this synchronises)."""
+        return self.corr_level_tiles_computed(reset)[0]
+
+    def _window_pyramids(self, feats, keys, N, geo, dev, od_levels=()):
         """K3/K4: the correlation pyramids of a window, one per problem (query frame -> target frame): level l is one GEMM of
         the query frame's features against the 2^l-pooled features of the target frame.  A pyramid depends on its two frames
         only, so with frame keys it is kept across windows: consecutive sliding windows share 2(N-3) of their 2(N-2)
         problems.  Returns {"f": [...], "b": [...]} (per centre frame, a list of level buffers).
-        on_demand (_level0_on_demand): level 0 is not built here - neither the GEMM nor its transposed twin is launched; the
-        pyramid gets an empty bitmap and the iterations fill the tiles their lookups read (update_block.ensure_level0)."""
+        od_levels (_on_demand_levels): these levels are not built here - for level 0 neither the GEMM nor its transposed twin
+        is launched; the pyramid gets empty bitmaps and the iterations fill the tiles their lookups read
+        (update_block.ensure_level0)."""
         D, L = self.cfg.feat_dim, geo.L
         AF, VFl, Nl, Pv, ldl, psz = geo.AF, geo.VFl, geo.Nl, geo.Pv, geo.ldl, geo.psz
         scale = self._corr_scale(AF)
         lim = 2 * (N - 2) + 2
         pyrs = {"f": [], "b": []}
-        od = ("od",) if on_demand else ()      # (a pyramid without its level 0 is not the dense one: its own cache entry)
+        on_demand = bool(od_levels)
+        # (a pyramid without some of its levels is not the dense one, nor one that lacks other levels: its own cache entry)
+        od = (tuple(od_levels), "od") if on_demand else ()
         if on_demand:
-            psz = psz + [hip.corr_bitmap_words(Pv, Nl[0])]      # (the bitmap travels with the level buffers)
-        first = 1 if on_demand else 0
+            psz = psz + [self._bitmap_sections(geo, od_levels)[1]]      # (the bitmaps travel with the level buffers)
+        built = [l for l in range(L) if l not in od_levels]
         for c in range(1, N - 1):
             for d, tgt in (("f", c + 1), ("b", c - 1)):
                 pk = ("p", keys[c], keys[tgt]) + od if keys is not None else None
@@ -1207,7 +1236,7 @@ class MOFNetHIP(_Holder):
                         rev = self._pyramid_buffers(psz, dev, limit=lim)
                         self._cache_put("p", rk, rev, limit=lim)
                     cnm = self._nm("corr") if self._split() else 3
-                    for l in range(first, L):
+                    for l in built:
                         # (one MFMA per product is symmetric in its operands: no swapped cross terms to order)
                         hip.conv2d(feats[c][0], D, D, 1, 1, Pv, feats[tgt][1][l], None, Nl[l], 1, 1, pyr[l],
                                    ldl[l], out_scale=scale, in_fmt=AF, out_fmt=VFl[l],
@@ -1215,7 +1244,7 @@ class MOFNetHIP(_Holder):
                                    out_t=rev[0] if dual and l == 0 else None, ld_out_t=ldl[0] if dual and l == 0 else 0,
                                    mfma=cnm)
                     if dual:
-                        for l in range(1, L):
+                        for l in built if on_demand else range(1, L):
                             hip.conv2d(feats[tgt][0], D, D, 1, 1, Pv, feats[c][1][l], None, Nl[l], 1, 1, rev[l],
                                        ldl[l], out_scale=scale, in_fmt=AF, out_fmt=VFl[l], mfma=cnm)
                     if on_demand:
@@ -1225,19 +1254,25 @@ class MOFNetHIP(_Holder):
                 pyrs[d].append(pyr)
         return pyrs
 
-    def _ensure_plan(self, pyrs, feats, N, geo, dev):
-        """What the on-demand level-0 passes of a window need (update_block.ensure_level0): the device cells that name, per
-        direction and centre, the query frame's rows, the target frame's level-0 hi plane, the level-0 buffer and its bitmap."""
+    def _ensure_plan(self, pyrs, feats, N, geo, dev, od_levels):
+        """What the on-demand passes of a window need (update_block.ensure_level0): the device cells that name, per direction
+        and centre, the query frame's rows and, per on-demand level, the target frame's hi plane of that level, the level's
+        buffer and its bitmap; and the dense call of every such level (of one of the pyramids: shapes and arithmetic)."""
         M = N - 2
-        cells = self._buf("ensure_cells", 64, dev, torch.int64)
+        cells = self._buf("ensure_cells", 128, dev, torch.int64)      # (8 problems x (1 + 3 x 3 levels) at most)
+        at, _ = self._bitmap_sections(geo, od_levels)
         ptrs = []
         for d, step in (("f", 1), ("b", -1)):
             for i, c in enumerate(range(1, N - 1)):
                 pyr = pyrs[d][i]
-                ptrs += [feats[c][0], feats[c + step][1][0].hi, pyr[0], self._pyramid_bitmap(pyr, geo.L)]
+                bits = self._pyramid_bitmap(pyr, geo.L)
+                ptrs.append(feats[c][0])
+                for l in od_levels:
+                    ptrs += [feats[c + step][1][l].hi, pyr[l], bits.data_ptr() + 4 * at[l]]
         hip.ptr_table_set(cells, ptrs)
-        count = self._buf("ensure_count", 1, dev, torch.int32, zero=True)     # (through _buf: captured launches hold its address)
-        return types.SimpleNamespace(cells=cells, M=M, rows=feats[1][0], weight=feats[2][1][0], level0=pyrs["f"][0][0],
+        count = self._buf("ensure_count", 4, dev, torch.int32, zero=True)     # (through _buf: captured launches hold its address)
+        levels = [(l, feats[2][1][l], pyrs["f"][0][l], geo.Nl[l], geo.ldl[l], geo.hl[l], geo.wl[l]) for l in od_levels]
+        return types.SimpleNamespace(cells=cells, M=M, rows=feats[1][0], levels=levels, per=1 + 3 * len(od_levels),
                                      D=self.cfg.feat_dim, scale=self._corr_scale(geo.AF), counter=count)
 
     def _frame_features(self, src, sel, keys, H, W, P, dev, L, hl, wl, Sl, vt=None):
@@ -1466,7 +1501,7 @@ class MOFNetHIP(_Holder):
                 join = torch.cuda.Event()
                 join.record()
         if win.ensure is not None:
-            ub.ensure_level0(s, ne, r0, win.ensure)     # the level-0 tiles this lookup reads and the pyramids lack
+            ub.ensure_level0(s, ne, r0, win.ensure)     # the tiles this lookup reads and the pyramids lack
         ub.lookup(s, ne, r0, win.tables, win.bidir)
         ub.convc1(s, ne, r0)
         ub.convc2(s, ne, r0)
@@ -1542,7 +1577,8 @@ class MOFNetHIP(_Holder):
             feats = self._frame_features(src, list(range(N)), keys, H, W, P, dev, L, geo.hl, geo.wl, geo.Sl, vt=geo.VT)
             # K3/K4 correlation pyramids, one per problem (query frame -> target frame)
             on_demand = self._level0_on_demand(keys, N, geo, dense_corr)
-            pyrs = self._window_pyramids(feats, keys, N, geo, dev, on_demand)
+            od_levels = self._on_demand_levels(on_demand, geo)
+            pyrs = self._window_pyramids(feats, keys, N, geo, dev, od_levels)
             s = self._window_state(P, dev, M, h, w, geo, R, AF, cor_p)
             # K2 context encoder on the centre frames -> h = tanh(first half), inp = relu(second half)
             ctx = self._frame_context(src, list(range(1, N - 1)), keys, H, W, P, dev, Pn, M)
@@ -1557,7 +1593,7 @@ class MOFNetHIP(_Holder):
             win.gates = self._gate_addends(ctx, dev, Pn, M)
             win.sk_ws = self._sk_workspace(MP, dev) if self.sk else None
             win.tables, win.bidir = self._pyramid_tables(pyrs, dev, M, L, cor_p)
-            win.ensure = self._ensure_plan(pyrs, feats, N, geo, dev) if on_demand else None
+            win.ensure = self._ensure_plan(pyrs, feats, N, geo, dev, od_levels) if on_demand else None
             no, nflows = (1, 1) if short else (M, 2 * M)
             up_fixed = self._buf("up_out", nflows * H * W * 2, dev)
             mask = self._buf("mask", MP * 1152, dev)
@@ -1602,7 +1638,7 @@ class MOFNetHIP(_Holder):
                             hip.convex_upsample(s.coords1, c * Pn * 4, 2 * d, mask, c * Pn * 1152 + d * 576, 1152, h, w,
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
-            gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), geo.vol16,
+            gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), geo.vol16, od_levels,
                     self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), win.warm, win.att_slots, on_demand)
             if self.sk:
                 gkey += ("sk",)

@@ -56,14 +56,15 @@ def lookup(s, n, r0, tables=(), bidir=None, pyrs=None):
 
 
 def ensure_level0(s, n, r0, en):
-    """In front of `lookup` on the same n query maps from row r0 on, both directions: compute the level-0 tiles of their
-    pyramids that the lookup's windows read and that are not there yet (hip.corr_level0_ensure).  en: the window's record -
-    cells (four per direction and centre, the second direction M centres behind the first), the dense level-0 call of one
-    of the pyramids (rows, weight, level0, D, scale) and the counter."""
+    """In front of `lookup` on the same n query maps from row r0 on, both directions: compute the tiles of their pyramids'
+    on-demand levels (level 0, and the pooled levels of en.levels) that the lookup's windows read and that are not there
+    yet, as ONE launch (hip.corr_levels_ensure).  en: the window's record - cells (en.per per direction and centre, the
+    second direction M centres behind the first), the dense calls of the levels of one of the pyramids (rows, D, scale,
+    levels) and the counters."""
     g = s.geo
     c0 = r0 // s.Pn
-    hip.corr_level0_ensure(en.rows, en.D, en.weight, en.level0, g.Pv, g.Nl[0], g.ldl[0], en.scale, en.cells[4 * c0:], n, 2,
-                           en.M, s.coords1, r0 * 4, 4, 2, g.hl[0], g.wl[0], s.R, g.TILE, counter=en.counter, in_fmt=s.AF)
+    hip.corr_levels_ensure(en.rows, en.D, g.Pv, en.levels, en.scale, en.cells[en.per * c0:], n, 2, en.M, s.coords1, r0 * 4, 4, 2,
+                           g.hl[0], g.wl[0], s.R, g.TILE, counters=en.counter, in_fmt=s.AF)
 
 
 # ---------------------------------------------------------------------- motion encoder
