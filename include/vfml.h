@@ -383,6 +383,25 @@ int vfml_corr_lookup_indirect_bidir(const float* const* table, const int32_t* hl
                                     int levels, int radius, int nmaps, int q_per_map, const float* coords, int ld_coords,
                                     int dir_coords, float* out, int ld_out, int dir_out, int dir_tab, int out_fmt, int vol_fmt,
                                     int vol_tile, void* stream);
+/* vfml_corr_lookup_indirect_bidir with a patch cache (radius 3 or 4, at most four levels).  What a query gathers - the
+ * (2r+2)^2 integer-grid texels of every level, zero outside the level, f16 levels converted - depends on the origins of its
+ * windows only, not on the fraction of its coordinate; while the pyramids stay what they are, a query whose origins did not
+ * change since its last launch reads that patch back (contiguous, 16-byte loads) instead of gathering it again, and mixes
+ * it with the new bilinear weights: the output is the uncached call's, bit for bit.
+ *   cache           : float [2][cache_rows][4][(2r+2)^2], 16-byte aligned: a patch per (direction, row)
+ *   key             : int32 [2][cache_rows][8], 16-byte aligned: x0, y0 of levels 0..3 as the patch was gathered.  A row
+ *                     whose key holds INT32_MIN (a value no origin takes: they are clamped to +-65536 - r) never hits; the
+ *                     caller resets the keys whenever a pyramid the table names changes.
+ *   cache_rows, row0: rows per direction, and the row of the launch's first query (the launch covers rows row0 ..
+ *                     row0 + nmaps * q_per_map - 1 of both directions, and touches no other row of cache and key)
+ *   store           : nonzero - a query whose origins differ (a miss) writes its patch and origins; 0 - a miss gathers
+ *                     as the uncached call does and leaves cache and key as they are
+ *   counter         : optional device cells: [0] += queries that hit, [1] += queries that missed (tests, profiles). */
+int vfml_corr_lookup_indirect_bidir_cached(const float* const* table, const int32_t* hl, const int32_t* wl, const int32_t* ld,
+                                           int levels, int radius, int nmaps, int q_per_map, const float* coords,
+                                           int ld_coords, int dir_coords, float* out, int ld_out, int dir_out, int dir_tab,
+                                           int out_fmt, int vol_fmt, int vol_tile, float* cache, int32_t* key, int cache_rows,
+                                           int row0, int store, uint32_t* counter, void* stream);
 int vfml_ptr_table_set(void* table, const void* const* ptrs, int n, void* stream);
 
 /* Level 0 of correlation pyramids on demand: in front of a lookup, compute the 128 x 64 tiles of the level-0 volumes that

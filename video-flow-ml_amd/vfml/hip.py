@@ -173,6 +173,8 @@ def lib():
     L.vfml_corr_lookup_indirect_bidir.argtypes = [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32),
                                                   c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                   c_int, c_int, c_int, c_int, c_void_p]
+    L.vfml_corr_lookup_indirect_bidir_cached.argtypes = L.vfml_corr_lookup_indirect_bidir.argtypes[:-1] + [
+        c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     L.vfml_ptr_table_set.argtypes = [c_void_p, POINTER(c_void_p), c_int, c_void_p]
     L.vfml_corr_level0_ensure.argtypes = L.vfml_conv2d_split.argtypes[:5] + [c_int, c_int, c_int] + [
         c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
@@ -265,6 +267,7 @@ EXPORTS = [
     "vfml_conv2d", "vfml_conv2d_split", "vfml_conv2d_variant", "vfml_conv2d_split_variant", "vfml_conv2d_split_variant_at", "vfml_split_f16", "vfml_to_s16", "vfml_softmax_rows_s16", "vfml_softmax_rows_f16", "vfml_attention_plane_workspace_bytes", "vfml_attention_plane_f16", "vfml_attention_bank_planes_f16", "vfml_axpy_f32", "vfml_dwconv2d", "vfml_gelu_rows", "vfml_layernorm_rows", "vfml_window_attention", "vfml_attention_shared_keys", "vfml_transpose_to_s16", "vfml_add_to_s16",
     "vfml_transpose_split_f16", "vfml_frames_to_nhwc4", "vfml_instnorm_workspace_bytes", "vfml_instnorm_stats",
     "vfml_instnorm_apply", "vfml_instnorm_finalize", "vfml_instnorm_finalize_workspace_bytes", "vfml_avgpool2x2", "vfml_corr_lookup", "vfml_corr_lookup_indirect", "vfml_corr_lookup_indirect_bidir",
+    "vfml_corr_lookup_indirect_bidir_cached",
     "vfml_ptr_table_set", "vfml_corr_level0_ensure", "vfml_corr_levels_ensure", "vfml_window_seed", "vfml_coords_update", "vfml_coords_init", "vfml_tapsum3x3", "vfml_tapsum3x3_update", "vfml_flow_rows7", "vfml_flow_half", "vfml_conv3x3_c64",
     "vfml_flow_forward_interpolate_workspace_bytes", "vfml_flow_forward_interpolate",
     "vfml_convex_upsample", "vfml_stem7x7s2", "vfml_stem7x7s2_chunks", "vfml_flow_lod", "vfml_flow_encode", "vfml_taa_blend", "vfml_flow_quality_map", "vfml_flow_correct_workspace_bytes", "vfml_flow_correct",
@@ -786,6 +789,7 @@ def corr_levels_ensure(rows, c, n_rows, levels, out_scale, cells, centres, dirs,
 
 
 SEED_NONE, SEED_LOAD, SEED_STORE = 0, 1, 2
+LOOKUP_KEY_NONE = -2 ** 31       # a patch-cache key no window origin takes (corr_lookup's `cache`)
 
 
 def window_seed(cells, ncentres, rows, cols, state, ld_state, h_off, mf_off, ld_ctx):
@@ -799,16 +803,38 @@ def window_seed(cells, ncentres, rows, cols, state, ld_state, h_off, mf_off, ld_
 
 
 def corr_lookup(pyrs, hl, wl, ld, radius, q_per_map, coords, coords_off, ld_coords, out, out_off, ld_out,
-                out_fmt=FMT_F32, table=None, nmaps=None, vol_fmt=FMT_F32, vol_tile=0, bidir=None):
+                out_fmt=FMT_F32, table=None, nmaps=None, vol_fmt=FMT_F32, vol_tile=0, bidir=None, cache=None):
     """pyrs: list (one entry per query map) of lists (one flat float32 device tensor per level, rows =
     that map's q_per_map queries).  Queries / coords / out rows are ordered map-major.
     table (with nmaps): instead of `pyrs`, an int64 device tensor holding the same pointers, map-major
     (ptr_table_set), read when the kernel runs (vfml_corr_lookup_indirect).
     vol_tile: 0 (row-major level images, rows in query order) or VolTile.code (include/vfml.h).
     bidir = (dir_coords, dir_out, dir_tab) with a table: both directions of the nmaps query maps in one launch
-    (vfml_corr_lookup_indirect_bidir)."""
+    (vfml_corr_lookup_indirect_bidir).
+    cache (with bidir; radius 3 or 4) = (patches, keys, rows, row0, store, counter): the launch keeps every query's gathered
+    patch and window origins in `patches` (f32) / `keys` (int32, LOOKUP_KEY_NONE = no entry) at row row0 + its query row of
+    `rows` per direction, and gathers only where the origins differ from the kept ones
+    (vfml_corr_lookup_indirect_bidir_cached; counter: None or an int32 device tensor [hits, misses])."""
     L = len(hl)
-    if bidir is not None:
+    if cache is not None:
+        if bidir is None or table is None:
+            raise ValueError("corr_lookup: the patch cache goes with the bidirectional table lookup")
+        dir_coords, dir_out, dir_tab = bidir
+        patches, keys, rows, row0, store, counter = cache
+        if keys.dtype != torch.int32 or (counter is not None and counter.dtype != torch.int32):
+            raise ValueError("corr_lookup: cache keys and counter are int32 device tensors")
+        side = 2 * radius + 2
+        if patches.numel() < 2 * rows * 4 * side * side or keys.numel() < 2 * rows * 8:
+            raise ValueError(f"corr_lookup: cache of {patches.numel()} floats / {keys.numel()} keys is too small for 2 x {rows} rows")
+
+        def launch():
+            _check(lib().vfml_corr_lookup_indirect_bidir_cached(
+                c_void_p(table.data_ptr()), (c_int32 * L)(*hl), (c_int32 * L)(*wl), (c_int32 * L)(*ld), L, radius, nmaps,
+                q_per_map, _ptr(_dev(coords), coords_off), ld_coords, dir_coords, _ptr(_dev(out), out_off), ld_out, dir_out,
+                dir_tab, out_fmt, vol_fmt, vol_tile, _ptr(_dev(patches)), c_void_p(_dev(keys, torch.int32).data_ptr()), rows,
+                row0, int(bool(store)), c_void_p(counter.data_ptr()) if counter is not None else None, _stream()),
+                "vfml_corr_lookup_indirect_bidir_cached")
+    elif bidir is not None:
         dir_coords, dir_out, dir_tab = bidir
 
         def launch():

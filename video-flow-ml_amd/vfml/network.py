@@ -1127,6 +1127,35 @@ class MOFNetHIP(_Holder):
     # works the same way ((1, 2)) but its gain at 1080p stayed inside the run-to-run noise: off.
     corr_on_demand_levels = (1,)
 
+    # The bidirectional lookup of the update iterations keeps every query's gathered texel patch, keyed by its window
+    # origins, and gathers again only where a window moved (vfml_corr_lookup_indirect_bidir_cached).
+    # False: the uncached launch (tests, A/B runs).  Same bits either way.
+    lookup_cache = True
+    lookup_cache_count = False      # True: count hits and misses per iteration (lookup_cache_counts; tests, the probe)
+
+    def _lookup_cache_plan(self, win, s, M, L, R, dev):
+        """The patch cache of a window's lookups -> (patches, keys, rows, counts or None), or None where the lookup stays
+        uncached: the cache goes with the split arithmetic's one-launch bidirectional lookup on a fixed-radius kernel."""
+        if not (self.lookup_cache and win.bidir is not None and self._split() and not self.sk and not self.tri_frame
+                and R in (3, 4) and L == 4):
+            return None
+        rows = M * s.Pn
+        counts = None
+        if self.lookup_cache_count:
+            counts = self._buf("lookup_count", 2 * max(1, self.cfg.decoder_depth), dev, torch.int32, zero=True)
+        return (self._buf("lookup_patches", 2 * rows * 4 * (2 * R + 2) ** 2, dev),
+                self._buf("lookup_keys", 2 * rows * 8, dev, torch.int32), rows, counts)
+
+    def lookup_cache_counts(self, reset=True):
+        """[(hits, misses)] per update iteration since the last reset, with lookup_cache_count on (this synchronises)."""
+        count = self._ws.get("lookup_count")
+        if count is None:
+            return []
+        n = [int(v) for v in count.tolist()]
+        if reset:
+            count.zero_()
+        return list(zip(n[0::2], n[1::2]))
+
     def _corr_scale(self, AF):
         scale = 1.0 / float(self.cfg.feat_dim) ** 0.5
         if AF == hip.FMT_S16:
@@ -1502,7 +1531,12 @@ class MOFNetHIP(_Holder):
                 join.record()
         if win.ensure is not None:
             ub.ensure_level0(s, ne, r0, win.ensure)     # the tiles this lookup reads and the pyramids lack
-        ub.lookup(s, ne, r0, win.tables, win.bidir)
+        cache = None
+        if win.cache is not None:
+            # (nobody reads the patches of the last iteration's launch: it stores none)
+            patches, keys, rows, counts = win.cache
+            cache = (patches, keys, rows, it + 1 < self.cfg.decoder_depth, counts[2 * it:] if counts is not None else None)
+        ub.lookup(s, ne, r0, win.tables, win.bidir, cache=cache)
         ub.convc1(s, ne, r0)
         ub.convc2(s, ne, r0)
         if join is None:
@@ -1594,6 +1628,7 @@ class MOFNetHIP(_Holder):
             win.sk_ws = self._sk_workspace(MP, dev) if self.sk else None
             win.tables, win.bidir = self._pyramid_tables(pyrs, dev, M, L, cor_p)
             win.ensure = self._ensure_plan(pyrs, feats, N, geo, dev, od_levels) if on_demand else None
+            win.cache = self._lookup_cache_plan(win, s, M, L, R, dev)
             no, nflows = (1, 1) if short else (M, 2 * M)
             up_fixed = self._buf("up_out", nflows * H * W * 2, dev)
             mask = self._buf("mask", MP * 1152, dev)
@@ -1605,6 +1640,9 @@ class MOFNetHIP(_Holder):
             # become one; same kernels, same order: bit-identical results).
             def body():
                 update_block.init_coords(s, M)
+                if win.cache is not None:
+                    # no patch of an earlier field, pyramid set or plan can hit: every key starts the field empty
+                    win.cache[1].fill_(hip.LOOKUP_KEY_NONE)
                 branch = None
                 if os.environ.get("VFML_FLOW_BRANCH", "0") == "1" and self._split():
                     branch = self._side2.get(dev)
@@ -1639,7 +1677,10 @@ class MOFNetHIP(_Holder):
                                                 up_fixed, out_off=(d * M + c) * H * W * 2)
 
             gkey = (H, W, N, M, bool(tri_batch), bool(pick_only), cfg.decoder_depth, L, R, self._plan_key(), geo.vol16, od_levels,
-                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"), win.warm, win.att_slots, on_demand)
+                    self._packed_serial, str(dev), os.environ.get("VFML_FLOW_BRANCH", "0"),
+                    # (the lookup's patch cache, and whether its launches count)
+                    win.cache is not None, win.cache is not None and win.cache[3] is not None,
+                    win.warm, win.att_slots, on_demand)
             if self.sk:
                 gkey += ("sk",)
             self._pre_body = torch.cuda.Event()

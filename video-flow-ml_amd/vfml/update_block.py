@@ -39,10 +39,12 @@ def init_coords(s, n, flow_init=None):
     hip.coords_update(s.coords1, flow_init, n, s.h, s.w, **_put_flow(s))
 
 
-def lookup(s, n, r0, tables=(), bidir=None, pyrs=None):
+def lookup(s, n, r0, tables=(), bidir=None, pyrs=None, cache=None):
     """K5 on n query maps from row r0 on."""
     # pyrs: the maps' pyramids as a list (one direction); else `tables` of their pointers, one per direction and launch - or
     # ONE table with both directions behind one another and `bidir` (the two lookups of an iteration as one launch)
+    # cache (with bidir) = (patches, keys, rows, store, counter): the launch keeps each query's gathered texel patch at its
+    # state row and gathers only where a window moved since the row's last launch (hip.corr_lookup)
     g = s.geo
     if pyrs is not None:
         hip.corr_lookup(pyrs, g.hl, g.wl, g.ldl, s.R, s.Pn, s.coords1, r0 * 4, 4, s.corr, r0 * s.ld_corr, s.ld_corr,
@@ -52,7 +54,8 @@ def lookup(s, n, r0, tables=(), bidir=None, pyrs=None):
     t0 = r0 // s.Pn * g.L
     for d, tab in enumerate(tables):
         hip.corr_lookup(None, g.hl, g.wl, g.ldl, s.R, s.Pn, s.coords1, r0 * 4 + 2 * d, 4, s.corr, r0 * s.ld_corr + d * s.cor_p,
-                        s.ld_corr, out_fmt=s.AF, table=tab[t0:], nmaps=n, vol_fmt=g.VF, vol_tile=g.TILE, bidir=bidir)
+                        s.ld_corr, out_fmt=s.AF, table=tab[t0:], nmaps=n, vol_fmt=g.VF, vol_tile=g.TILE, bidir=bidir,
+                        cache=cache[:3] + (r0,) + cache[3:] if cache is not None else None)
 
 
 def ensure_level0(s, n, r0, en):
