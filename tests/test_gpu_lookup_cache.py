@@ -1,15 +1,16 @@
-"""The bidirectional lookup with a patch cache (csrc/flow_ops.hip, vfml_corr_lookup_indirect_bidir_cached; DESIGN.md
-section 4b): a query whose eight window origins are the ones its cache row was gathered at reads the patch back instead
-of gathering it again.
+"""The bidirectional lookup with a patch cache (csrc/flow_ops.hip, vfml_corr_lookup_indirect_bidir_cached, which launches
+corr_lookup_fixed_kernel with CACHED set): a query whose eight window origins are the ones its cache
+row was gathered at reads the patch back instead of gathering it again.
 
-Oracle: the uncached vfml_corr_lookup_indirect_bidir on the same inputs.  Both kernels mix the same LDS patch with the same
-code, so the comparison is BYTE equality of the whole output buffer - pad channels and rows outside a launch's range (which
-hold a sentinel) included.  Which queries hit is pinned per query, not only counted: after a fill the volumes are
-overwritten with a NaN pattern, so a query that gathers again shows the pattern's output and one that hits the original's.
+Oracle: the uncached vfml_corr_lookup_indirect_bidir on the same inputs - the same kernel body without the cache steps,
+which mixes the same LDS patch - so the comparison is BYTE equality of the whole output buffer, pad channels and rows
+outside a launch's range (which hold a sentinel) included.  Which queries hit is pinned per query, not only counted: after
+a fill the volumes are overwritten with a NaN pattern, so a query that gathers again shows the pattern's output and one
+that hits the original's.
 
 Geometry: the on-demand tests' - a 30 x 38 map in 4 x 8 tiles (1280 volume rows), M = 2 centres, both directions: 4 560
-queries, 1 140 blocks of four waves.  Every case runs for radius 4 and 3 and for f32, f16-from-level-3 (the shipped plan)
-and all-f16 volumes."""
+queries, 1 140 blocks of four waves.  Every case runs for radius 4 and 3 and for every volume form the dispatcher has a
+kernel for: f32, f16 from level 3 (the shipped plan), from level 2, from level 1, and all f16."""
 import numpy as np
 import pytest
 import torch
@@ -20,7 +21,7 @@ H, W, L, M = 30, 38, 4, 2
 Pn = H * W
 NAN_BITS = 0x7FC0BEEF      # f32 volumes overwritten / buffers nobody may write
 NAN_HALF = 0x7E00
-VOL_FMTS = ("f32", "f16@3", "f16")
+VOL_FMTS = ("f32", "f16@3", "f16@2", "f16@1", "f16")
 
 
 def _bits(t):
@@ -55,7 +56,7 @@ class _Setup:
         self.hl, self.wl = [H >> l for l in range(L)], [W >> l for l in range(L)]
         self.Pv = vt.count(H, W)
         self.ld = [(vt.count(self.hl[l], self.wl[l]) + 31) // 32 * 32 + 32 for l in range(L)]
-        mask = {"f32": 0, "f16@3": 8, "f16": 15}[vol]
+        mask = {"f32": 0, "f16@3": 8, "f16@2": 12, "f16@1": 14, "f16": 15}[vol]
         self.half = [bool((mask >> l) & 1) for l in range(L)]
         self.vf = hip.FMT_F32 if mask == 0 else (hip.FMT_F16 if mask == 15 else hip.vol_f16_levels(mask))
 

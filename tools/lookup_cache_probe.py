@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The lookup's patch cache (csrc/flow_ops.hip corr_lookup_fixed_cached_kernel) in numbers.  GPU only.
+"""The lookup's patch cache (csrc/flow_ops.hip corr_lookup_fixed_kernel<.., CACHED = true>) in numbers.  GPU only.
 
     python tools/lookup_cache_probe.py [--drift 0,1] [--fields N] [--rounds R]
             a keyed sliding 1080p job, mixed plan, per clip (drift C: tests_support.drift_state_dict's c - 0 is the

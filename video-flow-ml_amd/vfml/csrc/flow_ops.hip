@@ -153,6 +153,15 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// The patch cache of the fixed-radius lookup (vfml_corr_lookup_indirect_bidir_cached); every other launch passes an empty one.
+struct LookupCache {
+  float* patch;          // [2][rows][FIXED_LEVELS][PSZ]: the patches as the gather leaves them in LDS
+  int* key;              // [2][rows][2 * FIXED_LEVELS]: x0, y0 of every level's window (window_origin's values)
+  int rows, row0;        // state rows per direction; the launch's first query row among them
+  int store;             // a miss writes its patch and origins back
+  unsigned* counter;     // optional: [0] += hits, [1] += misses
+};
+
 // The same lookup with the radius as a compile-time constant (4: default, 3: --fast), one wave per query, no workgroup
 // barrier.  The kernel is bound by the instructions it issues as much as by the lines it gathers (round 2: ~710 VALU
 // instructions per query = 1.5 us of a SIMD, 95 queries per SIMD per launch at 1080p), so every phase is laid out for few
@@ -164,153 +173,17 @@ __device__ __forceinline__ void wave_lds_sync() {
 //             upper pair of the next (one ds_read2 and four multiply-adds per sample, no index arithmetic)
 //   store     the samples go through LDS so that a lane owns one 8-channel unit: 32 bytes of split row (or two quads of f32)
 //   V16       bit l set: level l of the volumes holds f16 texels (a compile-time property of each unrolled level)
-template <int R, bool OUT16, int V16 = 0>
-__global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_kernel(const LookupArgs a) {
+//   CACHED    the patch the gather leaves in LDS depends on the eight window origins alone, not on the fractions of the
+//             coordinate, so it is kept per (direction, state row) beside those origins (LookupCache): a wave whose origins
+//             are the kept ones copies the patch back - contiguous 16-byte loads, no address arithmetic - instead of
+//             gathering it again; the decision is one per wave, in scalar registers.  The mix reads the same LDS contents
+//             either way, so `out` holds the same bits with and without the cache.  Not set: `c` is never read.
+template <int R, bool OUT16, int V16, bool CACHED>
+__global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_kernel(const LookupArgs a, const LookupCache c) {
   constexpr int SIDE = 2 * R + 2, PSZ = SIDE * SIDE, WIN = 2 * R + 1, WW = WIN * WIN;
   constexpr int NOUTPAD = (FIXED_LEVELS * WW + 7) & ~7;
   static_assert(PSZ <= 128 && FIXED_LEVELS * WIN <= 64 && NOUTPAD / 8 <= 64, "one wave: at most two gather passes per level");
-  __shared__ float patch[LOOKUP_WAVES][FIXED_LEVELS][PSZ];
-  __shared__ __attribute__((aligned(16))) float outs[LOOKUP_WAVES][NOUTPAD];
-  const int lane = threadIdx.x & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int q = blockIdx.x * LOOKUP_WAVES + wv;       // the wave's query: everything derived from it is scalar
-  if (q >= a.nq) return;
-  // (integer division runs on the vector unit: readfirstlane tells the compiler its result is still one value per wave)
-  int map = __builtin_amdgcn_readfirstlane(q / a.q_per_map);
-  const int qq = q - map * a.q_per_map;
-  const int qrow = __builtin_amdgcn_readfirstlane((a.tws | a.ths) ? tiled_at(qq / a.qw, qq % a.qw, a.qw, a.tws, a.ths) : qq);
-  int64_t crow, orow;
-  lookup_rows(a, q, map, crow, orow);
-  const float cx = a.coords[crow + 0];
-  const float cy = a.coords[crow + 1];
-  // the two passes of a level: window cells lane and lane + 64 (the second pass: cells 64 .. PSZ-1)
-  const int pyA = lane / SIDE, pxA = lane - pyA * SIDE;
-  const int pyB = (lane + 64) / SIDE, pxB = (lane + 64) - pyB * SIDE;
-  const bool inB = lane + 64 < PSZ;
-  // Row pointers of all levels first (a device table is read here), then STRAIGHT-LINE code for the gathers: behind a
-  // branch - even a uniform `l < levels` - hipcc waits for a level's texels before it asks for the next level's.  A level the
-  // call does not have reads level 0's first texel and drops it.
-  const float* pl[FIXED_LEVELS];
-  if (a.table) {
-#pragma unroll
-    for (int l = 0; l < FIXED_LEVELS; ++l) pl[l] = a.table[map * a.levels + (l < a.levels ? l : 0)];
-  } else {
-#pragma unroll
-    for (int l = 0; l < FIXED_LEVELS; ++l) pl[l] = a.pyr[map][l < a.levels ? l : 0];
-  }
-  float va[FIXED_LEVELS], vb[FIXED_LEVELS];
-  bool oka[FIXED_LEVELS], okb[FIXED_LEVELS];
-#pragma unroll
-  for (int l = 0; l < FIXED_LEVELS; ++l) {
-    const bool have = l < a.levels;
-    const int ll = have ? l : 0;
-    const bool v16 = (V16 >> l) & 1;         // (l is unrolled: a constant per copy of the body)
-    const int ES = v16 ? 2 : 4;              // bytes per texel of this level
-    const char* base = reinterpret_cast<const char*>(pl[l]) + (int64_t)qrow * a.ld[ll] * ES;
-    const int wl = a.wl[ll], hl = a.hl[ll];
-    const float x = level_coord(cx, l), y = level_coord(cy, l);        // exact: power-of-two scale (a constant here)
-    const int x0 = window_origin(x, R);
-    const int y0 = window_origin(y, R);
-    auto texel = [&](int px, int py, bool in, float& out, bool& ok) {
-      const int xx = x0 + px, yy = y0 + py;
-      ok = have && in && xx >= 0 && xx < wl && yy >= 0 && yy < hl;
-      const int at = tiled_at(min(max(yy, 0), hl - 1), min(max(xx, 0), wl - 1), wl, a.tws, a.ths);
-      // (explicitly GLOBAL: a pointer that went through selects or a table loses its address space and becomes flat_load)
-      if (v16) out = (float)((const __attribute__((address_space(1))) _Float16*)base)[at];
-      else out = ((const __attribute__((address_space(1))) float*)base)[at];          // (zeroed below, once every load is on its way)
-    };
-    texel(pxA, pyA, true, va[l], oka[l]);
-    if constexpr (PSZ > 64) texel(pxB, pyB, inB, vb[l], okb[l]);
-    else { vb[l] = 0.f; okb[l] = false; }
-  }
-#pragma unroll
-  for (int l = 0; l < FIXED_LEVELS; ++l) {
-    va[l] = oka[l] ? va[l] : 0.f;
-    vb[l] = okb[l] ? vb[l] : 0.f;
-  }
-#pragma unroll
-  for (int l = 0; l < FIXED_LEVELS; ++l) {
-    if (l < a.levels) {
-      if (PSZ > 64 || lane < PSZ) patch[wv][l][lane] = va[l];
-      if constexpr (PSZ > 64) if (inB) patch[wv][l][lane + 64] = vb[l];
-    }
-  }
-  const int nout = a.levels * WW;
-  const int nunits = (nout + 7) >> 3;
-  if (lane >= 56 && nout + (lane - 56) < nunits * 8) outs[wv][nout + (lane - 56)] = 0.f;   // the zero channels that fill the last unit
-  wave_lds_sync();
-  if (lane < a.levels * WIN) {
-    const int l = lane / WIN, i = lane - l * WIN;          // i: x offset index; the lane walks j, the y offset index
-    const float x = level_coord(cx, l), y = level_coord(cy, l);
-    const float fx = x - floorf(x), fy = y - floorf(y);
-    const float wx0 = 1.f - fx, wy0 = 1.f - fy;
-    const float w00 = wx0 * wy0, w10 = fx * wy0, w01 = wx0 * fy, w11 = fx * fy;
-    const float* p = &patch[wv][l][i];
-    float* o = &outs[wv][l * WW + i * WIN];
-    float nw = p[0], ne = p[1];
-#pragma unroll
-    for (int j = 0; j < WIN; ++j) {
-      const float sw = p[(j + 1) * SIDE], se = p[(j + 1) * SIDE + 1];
-      o[j] = bilinear4w(nw, ne, sw, se, w00, w10, w01, w11);
-      nw = sw; ne = se;
-    }
-  }
-  wave_lds_sync();
-  if (lane < nunits) {
-    float* o = a.out + orow + lane * 8;
-    const f32x4 v0 = *reinterpret_cast<const f32x4*>(&outs[wv][lane * 8]);
-    const f32x4 v1 = *reinterpret_cast<const f32x4*>(&outs[wv][lane * 8 + 4]);
-    if (OUT16) {
-      // one unit of the split row: eight hi halves, then the eight lo halves
-      vfml_h16x2 h0, h1, h2, h3, l0, l1, l2, l3;
-      vfml_split2(v0[0], v0[1], h0, l0);
-      vfml_split2(v0[2], v0[3], h1, l1);
-      vfml_split2(v1[0], v1[1], h2, l2);
-      vfml_split2(v1[2], v1[3], h3, l3);
-      uint4 hv, lv;
-      hv.x = __builtin_bit_cast(unsigned, h0); hv.y = __builtin_bit_cast(unsigned, h1);
-      hv.z = __builtin_bit_cast(unsigned, h2); hv.w = __builtin_bit_cast(unsigned, h3);
-      lv.x = __builtin_bit_cast(unsigned, l0); lv.y = __builtin_bit_cast(unsigned, l1);
-      lv.z = __builtin_bit_cast(unsigned, l2); lv.w = __builtin_bit_cast(unsigned, l3);
-      *reinterpret_cast<uint4*>(o) = hv;
-      *reinterpret_cast<uint4*>(o + 4) = lv;
-    } else {
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int c = lane * 8 + 4 * h;
-        const f32x4 w = h ? v1 : v0;
-        if (c + 3 < nout && (((uintptr_t)(o + 4 * h)) & 15u) == 0) {
-          *reinterpret_cast<f32x4*>(o + 4 * h) = w;
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if (c + k < nout) o[4 * h + k] = w[k];
-        }
-      }
-    }
-  }
-}
-
-// The fixed-radius lookup with a patch cache (vfml_corr_lookup_indirect_bidir_cached).  The patch the gather leaves in LDS
-// depends on the eight window origins alone, not on the fractions of the coordinate, so it is kept per (direction, state
-// row) beside those origins: a wave whose origins are the kept ones copies the patch back - contiguous 16-byte loads, no
-// address arithmetic - instead of gathering it again; the decision is one per wave, in scalar registers.  Gather, mix and
-// store are corr_lookup_fixed_kernel's, as a COPY: that kernel and everything that launches it stay what they are, and
-// both leave the same bits in `out` since the mix reads the same LDS contents either way.
-struct LookupCache {
-  float* patch;          // [2][rows][FIXED_LEVELS][PSZ]: the patches as the gather leaves them in LDS
-  int* key;              // [2][rows][2 * FIXED_LEVELS]: x0, y0 of every level's window (window_origin's values)
-  int rows, row0;        // state rows per direction; the launch's first query row among them
-  int store;             // a miss writes its patch and origins back
-  unsigned* counter;     // optional: [0] += hits, [1] += misses
-};
-
-template <int R, bool OUT16, int V16 = 0>
-__global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_cached_kernel(const LookupArgs a, const LookupCache c) {
-  constexpr int SIDE = 2 * R + 2, PSZ = SIDE * SIDE, WIN = 2 * R + 1, WW = WIN * WIN;
-  constexpr int NOUTPAD = (FIXED_LEVELS * WW + 7) & ~7;
-  static_assert(PSZ <= 128 && FIXED_LEVELS * WIN <= 64 && NOUTPAD / 8 <= 64, "one wave: at most two gather passes per level");
-  static_assert(PSZ % 4 == 0 && FIXED_LEVELS * PSZ <= 4 * 128, "a patch moves as at most two 16-byte quads per lane");
+  static_assert(!CACHED || (PSZ % 4 == 0 && FIXED_LEVELS * PSZ <= 4 * 128), "a patch moves as at most two 16-byte quads per lane");
   __shared__ __attribute__((aligned(16))) float patch[LOOKUP_WAVES][FIXED_LEVELS][PSZ];
   __shared__ __attribute__((aligned(16))) float outs[LOOKUP_WAVES][NOUTPAD];
   const int lane = threadIdx.x & 63;
@@ -323,24 +196,30 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_cached_ke
   const int qrow = __builtin_amdgcn_readfirstlane((a.tws | a.ths) ? tiled_at(qq / a.qw, qq % a.qw, a.qw, a.tws, a.ths) : qq);
   int64_t crow, orow;
   // the query's entry in the patch cache: (direction, absolute state row)
-  const int qdir = a.dir_maps && map >= a.dir_maps;
-  const int64_t krow = (int64_t)qdir * c.rows + c.row0 + (q - (qdir ? a.dir_maps * a.q_per_map : 0));
+  int64_t krow = 0;
+  if constexpr (CACHED) {
+    const int qdir = a.dir_maps && map >= a.dir_maps;
+    krow = (int64_t)qdir * c.rows + c.row0 + (q - (qdir ? a.dir_maps * a.q_per_map : 0));
+  }
   lookup_rows(a, q, map, crow, orow);
   const float cx = a.coords[crow + 0];
   const float cy = a.coords[crow + 1];
   // the origins exactly as the gather below forms them: equal origins = the same texel addresses and bounds tests
   int ox[FIXED_LEVELS], oy[FIXED_LEVELS];
+  bool hit = false;
+  if constexpr (CACHED) {
 #pragma unroll
-  for (int l = 0; l < FIXED_LEVELS; ++l) {
-    ox[l] = window_origin(level_coord(cx, l), R);
-    oy[l] = window_origin(level_coord(cy, l), R);
+    for (int l = 0; l < FIXED_LEVELS; ++l) {
+      ox[l] = window_origin(level_coord(cx, l), R);
+      oy[l] = window_origin(level_coord(cy, l), R);
+    }
+    const int4* kp = reinterpret_cast<const int4*>(c.key + krow * (2 * FIXED_LEVELS));
+    const int4 k0 = kp[0], k1 = kp[1];
+    const bool same = k0.x == ox[0] && k0.y == oy[0] && k0.z == ox[1] && k0.w == oy[1] &&
+                      k1.x == ox[2] && k1.y == oy[2] && k1.z == ox[3] && k1.w == oy[3];
+    hit = __builtin_amdgcn_readfirstlane(same ? 1 : 0) != 0;
   }
-  const int4* kp = reinterpret_cast<const int4*>(c.key + krow * (2 * FIXED_LEVELS));
-  const int4 k0 = kp[0], k1 = kp[1];
-  const bool same = k0.x == ox[0] && k0.y == oy[0] && k0.z == ox[1] && k0.w == oy[1] &&
-                    k1.x == ox[2] && k1.y == oy[2] && k1.z == ox[3] && k1.w == oy[3];
-  const bool hit = __builtin_amdgcn_readfirstlane(same ? 1 : 0) != 0;
-  if (hit) {
+  if (CACHED && hit) {
     const f32x4* src = reinterpret_cast<const f32x4*>(c.patch + krow * (FIXED_LEVELS * PSZ));
     f32x4* dst = reinterpret_cast<f32x4*>(&patch[wv][0][0]);
     if (4 * lane < a.levels * PSZ) dst[lane] = src[lane];
@@ -403,7 +282,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_cached_ke
   const int nunits = (nout + 7) >> 3;
   if (lane >= 56 && nout + (lane - 56) < nunits * 8) outs[wv][nout + (lane - 56)] = 0.f;   // the zero channels that fill the last unit
   wave_lds_sync();
-  if (!hit && c.store) {      // the patch as the mix is about to read it, then the origins it belongs to
+  if (CACHED && !hit && c.store) {      // the patch as the mix is about to read it, then the origins it belongs to
     f32x4* dst = reinterpret_cast<f32x4*>(c.patch + krow * (FIXED_LEVELS * PSZ));
     const f32x4* src = reinterpret_cast<const f32x4*>(&patch[wv][0][0]);
     if (4 * lane < a.levels * PSZ) dst[lane] = src[lane];
@@ -414,7 +293,7 @@ __global__ __launch_bounds__(64 * LOOKUP_WAVES) void corr_lookup_fixed_cached_ke
       kq[1] = make_int4(ox[2], oy[2], ox[3], oy[3]);
     }
   }
-  if (c.counter && lane == 0) atomicAdd(c.counter + (hit ? 0 : 1), 1u);
+  if (CACHED && c.counter && lane == 0) atomicAdd(c.counter + (hit ? 0 : 1), 1u);
   if (lane < a.levels * WIN) {
     const int l = lane / WIN, i = lane - l * WIN;          // i: x offset index; the lane walks j, the y offset index
     const float x = level_coord(cx, l), y = level_coord(cy, l);
@@ -702,71 +581,6 @@ extern "C" int vfml_window_seed(const void* cells, int ncentres, int rows, int c
 static int corr_lookup_impl(const float* const* pyr, const float* const* table, const int32_t* hl, const int32_t* wl,
                             const int32_t* ld, int levels, int radius, int nmaps, int q_per_map, const float* coords,
                             int ld_coords, float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream,
-                            int dir_maps = 0, int dir_coords = 0, int dir_out = 0, int dir_tab = 0,
-                            const LookupCache* cache = nullptr);
-
-extern "C" int vfml_corr_lookup(const float* const* pyr, const int32_t* hl, const int32_t* wl, const int32_t* ld,
-                                int levels, int radius, int nmaps, int q_per_map, const float* coords, int ld_coords,
-                                float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream) {
-  VFML_REQUIRE(pyr, "vfml_corr_lookup: null pointer");
-  return corr_lookup_impl(pyr, nullptr, hl, wl, ld, levels, radius, nmaps, q_per_map, coords, ld_coords, out, ld_out, out_fmt,
-                          vol_fmt, vol_tile, stream);
-}
-
-extern "C" int vfml_corr_lookup_indirect(const float* const* table, const int32_t* hl, const int32_t* wl, const int32_t* ld,
-                                         int levels, int radius, int nmaps, int q_per_map, const float* coords,
-                                         int ld_coords, float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream) {
-  VFML_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7u) == 0, "vfml_corr_lookup_indirect: null / misaligned table");
-  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, nmaps, q_per_map, coords, ld_coords, out, ld_out,
-                          out_fmt, vol_fmt, vol_tile, stream);
-}
-
-extern "C" int vfml_corr_lookup_indirect_bidir(const float* const* table, const int32_t* hl, const int32_t* wl, const int32_t* ld,
-                                               int levels, int radius, int nmaps, int q_per_map, const float* coords,
-                                               int ld_coords, int dir_coords, float* out, int ld_out, int dir_out, int dir_tab,
-                                               int out_fmt, int vol_fmt, int vol_tile, void* stream) {
-  VFML_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7u) == 0, "vfml_corr_lookup_indirect_bidir: null / misaligned table");
-  VFML_REQUIRE(nmaps >= 1 && 2 * nmaps <= MAX_MAPS, "vfml_corr_lookup_indirect_bidir: nmaps=%d out of [1,%d]", nmaps, MAX_MAPS / 2);
-  VFML_REQUIRE(dir_coords >= 0 && dir_coords + 2 <= ld_coords && dir_out >= 0 && (out_fmt != VFML_FMT_S16 || dir_out % 8 == 0),
-               "vfml_corr_lookup_indirect_bidir: dir_coords within a coords row, dir_out >= 0 (a multiple of 8 floats for split rows)");
-  VFML_REQUIRE(dir_tab >= nmaps && (dir_tab + nmaps) * levels <= MAX_TABLE,
-               "vfml_corr_lookup_indirect_bidir: dir_tab=%d (the second direction's first map in the table) out of range", dir_tab);
-  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, 2 * nmaps, q_per_map, coords, ld_coords, out, ld_out,
-                          out_fmt, vol_fmt, vol_tile, stream, nmaps, dir_coords, dir_out, dir_tab);
-}
-
-extern "C" int vfml_corr_lookup_indirect_bidir_cached(const float* const* table, const int32_t* hl, const int32_t* wl,
-                                                      const int32_t* ld, int levels, int radius, int nmaps, int q_per_map,
-                                                      const float* coords, int ld_coords, int dir_coords, float* out, int ld_out,
-                                                      int dir_out, int dir_tab, int out_fmt, int vol_fmt, int vol_tile,
-                                                      float* cache, int32_t* key, int cache_rows, int row0, int store,
-                                                      uint32_t* counter, void* stream) {
-  const char* me = "vfml_corr_lookup_indirect_bidir_cached";
-  VFML_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7u) == 0, "%s: null / misaligned table", me);
-  VFML_REQUIRE(nmaps >= 1 && 2 * nmaps <= MAX_MAPS, "%s: nmaps=%d out of [1,%d]", me, nmaps, MAX_MAPS / 2);
-  VFML_REQUIRE(dir_coords >= 0 && dir_coords + 2 <= ld_coords && dir_out >= 0 && (out_fmt != VFML_FMT_S16 || dir_out % 8 == 0),
-               "%s: dir_coords within a coords row, dir_out >= 0 (a multiple of 8 floats for split rows)", me);
-  VFML_REQUIRE(dir_tab >= nmaps && levels >= 1 && (dir_tab + nmaps) * levels <= MAX_TABLE,
-               "%s: dir_tab=%d (the second direction's first map in the table) out of range", me, dir_tab);
-  VFML_REQUIRE((radius == 3 || radius == 4) && levels <= FIXED_LEVELS,
-               "%s: radius=%d, levels=%d - the patch cache belongs to the fixed-radius kernels (radius 3 or 4, at most %d levels)",
-               me, radius, levels, FIXED_LEVELS);
-  VFML_REQUIRE(cache && key, "%s: null cache / key", me);
-  // (a cache row is FIXED_LEVELS * (2 radius + 2)^2 floats - a multiple of 16 bytes - and a key row 32 bytes: with aligned
-  // bases every row moves as 16-byte quads)
-  VFML_REQUIRE(vfml_aligned16(cache) && vfml_aligned16(key), "%s: cache and key rows must be 16-byte aligned", me);
-  VFML_REQUIRE(q_per_map > 0 && row0 >= 0 && cache_rows >= 1 && (int64_t)row0 + (int64_t)nmaps * q_per_map <= cache_rows,
-               "%s: rows %d .. +%d x %d outside the cache's %d rows per direction", me, row0, nmaps, q_per_map, cache_rows);
-  VFML_REQUIRE(counter == nullptr || (reinterpret_cast<uintptr_t>(counter) & 3u) == 0, "%s: misaligned counter", me);
-  LookupCache c;
-  c.patch = cache; c.key = key; c.rows = cache_rows; c.row0 = row0; c.store = store != 0; c.counter = counter;
-  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, 2 * nmaps, q_per_map, coords, ld_coords, out, ld_out,
-                          out_fmt, vol_fmt, vol_tile, stream, nmaps, dir_coords, dir_out, dir_tab, &c);
-}
-
-static int corr_lookup_impl(const float* const* pyr, const float* const* table, const int32_t* hl, const int32_t* wl,
-                            const int32_t* ld, int levels, int radius, int nmaps, int q_per_map, const float* coords,
-                            int ld_coords, float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream,
                             int dir_maps, int dir_coords, int dir_out, int dir_tab, const LookupCache* cache) {
   VFML_REQUIRE(nmaps >= 1 && nmaps <= MAX_MAPS && q_per_map > 0, "vfml_corr_lookup: nmaps=%d out of [1,%d] or empty maps", nmaps, MAX_MAPS);
   const int nq = nmaps * q_per_map;
@@ -819,55 +633,95 @@ static int corr_lookup_impl(const float* const* pyr, const float* const* table, 
   a.dir_maps = dir_maps; a.dir_coords = dir_coords; a.dir_out = dir_out; a.dir_tab = dir_tab;
   const dim3 grid((nq + LOOKUP_WAVES - 1) / LOOKUP_WAVES), block(64 * LOOKUP_WAVES);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (cache) {
-    // (the entry point admits radius 3 / 4 and at most FIXED_LEVELS levels only: every form has its fixed-radius kernel)
-    const LookupCache c = *cache;
-    const int m = a.vol16;
-#define VFML_LOOKUP_CACHED(RR, OO)                                                                                  \
-  do {                                                                                                               \
-    if (m == 15) hipLaunchKernelGGL((corr_lookup_fixed_cached_kernel<RR, OO, 15>), grid, block, 0, st, a, c);        \
-    else if (m == 14) hipLaunchKernelGGL((corr_lookup_fixed_cached_kernel<RR, OO, 14>), grid, block, 0, st, a, c);   \
-    else if (m == 12) hipLaunchKernelGGL((corr_lookup_fixed_cached_kernel<RR, OO, 12>), grid, block, 0, st, a, c);   \
-    else if (m == 8) hipLaunchKernelGGL((corr_lookup_fixed_cached_kernel<RR, OO, 8>), grid, block, 0, st, a, c);     \
-    else hipLaunchKernelGGL((corr_lookup_fixed_cached_kernel<RR, OO, 0>), grid, block, 0, st, a, c);                 \
-  } while (0)
-    if (radius == 4) {
-      if (a.out16) VFML_LOOKUP_CACHED(4, true);
-      else VFML_LOOKUP_CACHED(4, false);
-    } else {
-      if (a.out16) VFML_LOOKUP_CACHED(3, true);
-      else VFML_LOOKUP_CACHED(3, false);
-    }
-#undef VFML_LOOKUP_CACHED
-    return vfml_check_launch("vfml_corr_lookup_indirect_bidir_cached");
+  // Radius 3 / 4 with at most FIXED_LEVELS levels: the fixed-radius kernel of (radius, output format, f16 mask, cached) -
+  // the checks above admit f16 levels, and the cached entry point admits itself, for nothing else.  The rest: the general kernel.
+  const LookupCache c = cache ? *cache : LookupCache{};
+  const int m = a.vol16;
+#define VFML_LOOKUP_FIXED(RR, OO, CC)                                                                          \
+  if (radius == RR && (a.out16 != 0) == OO && (cache != nullptr) == CC) {                                       \
+    if (m == 15) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 15, CC>), grid, block, 0, st, a, c);      \
+    else if (m == 14) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 14, CC>), grid, block, 0, st, a, c); \
+    else if (m == 12) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 12, CC>), grid, block, 0, st, a, c); \
+    else if (m == 8) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 8, CC>), grid, block, 0, st, a, c);   \
+    else hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 0, CC>), grid, block, 0, st, a, c);               \
   }
-  if (a.vol16) {
-    const int m = a.vol16;
-#define VFML_LOOKUP16(RR, OO)                                                                                  \
-  do {                                                                                                          \
-    if (m == 15) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 15>), grid, block, 0, st, a);             \
-    else if (m == 14) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 14>), grid, block, 0, st, a);        \
-    else if (m == 12) hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 12>), grid, block, 0, st, a);        \
-    else hipLaunchKernelGGL((corr_lookup_fixed_kernel<RR, OO, 8>), grid, block, 0, st, a);                      \
-  } while (0)
-    if (radius == 4) {
-      if (a.out16) VFML_LOOKUP16(4, true);
-      else VFML_LOOKUP16(4, false);
-    } else {
-      if (a.out16) VFML_LOOKUP16(3, true);
-      else VFML_LOOKUP16(3, false);
-    }
-#undef VFML_LOOKUP16
-  } else if (radius == 4 && levels <= FIXED_LEVELS) {
-    if (a.out16) hipLaunchKernelGGL((corr_lookup_fixed_kernel<4, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((corr_lookup_fixed_kernel<4, false>), grid, block, 0, st, a);
-  } else if (radius == 3 && levels <= FIXED_LEVELS) {
-    if (a.out16) hipLaunchKernelGGL((corr_lookup_fixed_kernel<3, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((corr_lookup_fixed_kernel<3, false>), grid, block, 0, st, a);
+  if ((radius == 3 || radius == 4) && levels <= FIXED_LEVELS) {
+    VFML_LOOKUP_FIXED(4, true, true)
+    VFML_LOOKUP_FIXED(4, true, false)
+    VFML_LOOKUP_FIXED(4, false, true)
+    VFML_LOOKUP_FIXED(4, false, false)
+    VFML_LOOKUP_FIXED(3, true, true)
+    VFML_LOOKUP_FIXED(3, true, false)
+    VFML_LOOKUP_FIXED(3, false, true)
+    VFML_LOOKUP_FIXED(3, false, false)
   } else {
     hipLaunchKernelGGL(corr_lookup_kernel, grid, block, 0, st, a);
   }
-  return vfml_check_launch("vfml_corr_lookup");
+#undef VFML_LOOKUP_FIXED
+  return vfml_check_launch(cache ? "vfml_corr_lookup_indirect_bidir_cached" : "vfml_corr_lookup");
+}
+
+extern "C" int vfml_corr_lookup(const float* const* pyr, const int32_t* hl, const int32_t* wl, const int32_t* ld,
+                                int levels, int radius, int nmaps, int q_per_map, const float* coords, int ld_coords,
+                                float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream) {
+  VFML_REQUIRE(pyr, "vfml_corr_lookup: null pointer");
+  return corr_lookup_impl(pyr, nullptr, hl, wl, ld, levels, radius, nmaps, q_per_map, coords, ld_coords, out, ld_out, out_fmt,
+                          vol_fmt, vol_tile, stream, 0, 0, 0, 0, nullptr);
+}
+
+extern "C" int vfml_corr_lookup_indirect(const float* const* table, const int32_t* hl, const int32_t* wl, const int32_t* ld,
+                                         int levels, int radius, int nmaps, int q_per_map, const float* coords,
+                                         int ld_coords, float* out, int ld_out, int out_fmt, int vol_fmt, int vol_tile, void* stream) {
+  VFML_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7u) == 0, "vfml_corr_lookup_indirect: null / misaligned table");
+  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, nmaps, q_per_map, coords, ld_coords, out, ld_out,
+                          out_fmt, vol_fmt, vol_tile, stream, 0, 0, 0, 0, nullptr);
+}
+
+// What the two bidirectional entry points ask of their own arguments; `me` is the entry point's name.  (`cached`: that one
+// refuses levels < 1 here, the other leaves them to corr_lookup_impl - each keeps the message it has always given.)
+static int check_bidir(const char* me, bool cached, const float* const* table, int levels, int nmaps, int ld_coords,
+                       int dir_coords, int dir_out, int dir_tab, int out_fmt) {
+  VFML_REQUIRE(table && (reinterpret_cast<uintptr_t>(table) & 7u) == 0, "%s: null / misaligned table", me);
+  VFML_REQUIRE(nmaps >= 1 && 2 * nmaps <= MAX_MAPS, "%s: nmaps=%d out of [1,%d]", me, nmaps, MAX_MAPS / 2);
+  VFML_REQUIRE(dir_coords >= 0 && dir_coords + 2 <= ld_coords && dir_out >= 0 && (out_fmt != VFML_FMT_S16 || dir_out % 8 == 0),
+               "%s: dir_coords within a coords row, dir_out >= 0 (a multiple of 8 floats for split rows)", me);
+  VFML_REQUIRE(dir_tab >= nmaps && (!cached || levels >= 1) && (dir_tab + nmaps) * levels <= MAX_TABLE,
+               "%s: dir_tab=%d (the second direction's first map in the table) out of range", me, dir_tab);
+  return 0;
+}
+
+extern "C" int vfml_corr_lookup_indirect_bidir(const float* const* table, const int32_t* hl, const int32_t* wl, const int32_t* ld,
+                                               int levels, int radius, int nmaps, int q_per_map, const float* coords,
+                                               int ld_coords, int dir_coords, float* out, int ld_out, int dir_out, int dir_tab,
+                                               int out_fmt, int vol_fmt, int vol_tile, void* stream) {
+  if (check_bidir("vfml_corr_lookup_indirect_bidir", false, table, levels, nmaps, ld_coords, dir_coords, dir_out, dir_tab, out_fmt))
+    return 1;
+  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, 2 * nmaps, q_per_map, coords, ld_coords, out, ld_out,
+                          out_fmt, vol_fmt, vol_tile, stream, nmaps, dir_coords, dir_out, dir_tab, nullptr);
+}
+
+extern "C" int vfml_corr_lookup_indirect_bidir_cached(const float* const* table, const int32_t* hl, const int32_t* wl,
+                                                      const int32_t* ld, int levels, int radius, int nmaps, int q_per_map,
+                                                      const float* coords, int ld_coords, int dir_coords, float* out, int ld_out,
+                                                      int dir_out, int dir_tab, int out_fmt, int vol_fmt, int vol_tile,
+                                                      float* cache, int32_t* key, int cache_rows, int row0, int store,
+                                                      uint32_t* counter, void* stream) {
+  const char* me = "vfml_corr_lookup_indirect_bidir_cached";
+  if (check_bidir(me, true, table, levels, nmaps, ld_coords, dir_coords, dir_out, dir_tab, out_fmt)) return 1;
+  VFML_REQUIRE((radius == 3 || radius == 4) && levels <= FIXED_LEVELS,
+               "%s: radius=%d, levels=%d - the patch cache belongs to the fixed-radius kernels (radius 3 or 4, at most %d levels)",
+               me, radius, levels, FIXED_LEVELS);
+  VFML_REQUIRE(cache && key, "%s: null cache / key", me);
+  // (a cache row is FIXED_LEVELS * (2 radius + 2)^2 floats - a multiple of 16 bytes - and a key row 32 bytes: with aligned
+  // bases every row moves as 16-byte quads)
+  VFML_REQUIRE(vfml_aligned16(cache) && vfml_aligned16(key), "%s: cache and key rows must be 16-byte aligned", me);
+  VFML_REQUIRE(q_per_map > 0 && row0 >= 0 && cache_rows >= 1 && (int64_t)row0 + (int64_t)nmaps * q_per_map <= cache_rows,
+               "%s: rows %d .. +%d x %d outside the cache's %d rows per direction", me, row0, nmaps, q_per_map, cache_rows);
+  VFML_REQUIRE(counter == nullptr || (reinterpret_cast<uintptr_t>(counter) & 3u) == 0, "%s: misaligned counter", me);
+  LookupCache c;
+  c.patch = cache; c.key = key; c.rows = cache_rows; c.row0 = row0; c.store = store != 0; c.counter = counter;
+  return corr_lookup_impl(nullptr, table, hl, wl, ld, levels, radius, 2 * nmaps, q_per_map, coords, ld_coords, out, ld_out,
+                          out_fmt, vol_fmt, vol_tile, stream, nmaps, dir_coords, dir_out, dir_tab, &c);
 }
 
 // ---- flow -> 8-bit motion-vector images (reference encoding/flow_encoders.py) ---------------------------

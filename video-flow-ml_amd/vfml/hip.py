@@ -819,46 +819,38 @@ def corr_lookup(pyrs, hl, wl, ld, radius, q_per_map, coords, coords_off, ld_coor
     if cache is not None:
         if bidir is None or table is None:
             raise ValueError("corr_lookup: the patch cache goes with the bidirectional table lookup")
-        dir_coords, dir_out, dir_tab = bidir
         patches, keys, rows, row0, store, counter = cache
         if keys.dtype != torch.int32 or (counter is not None and counter.dtype != torch.int32):
             raise ValueError("corr_lookup: cache keys and counter are int32 device tensors")
         side = 2 * radius + 2
         if patches.numel() < 2 * rows * 4 * side * side or keys.numel() < 2 * rows * 8:
             raise ValueError(f"corr_lookup: cache of {patches.numel()} floats / {keys.numel()} keys is too small for 2 x {rows} rows")
-
-        def launch():
-            _check(lib().vfml_corr_lookup_indirect_bidir_cached(
-                c_void_p(table.data_ptr()), (c_int32 * L)(*hl), (c_int32 * L)(*wl), (c_int32 * L)(*ld), L, radius, nmaps,
-                q_per_map, _ptr(_dev(coords), coords_off), ld_coords, dir_coords, _ptr(_dev(out), out_off), ld_out, dir_out,
-                dir_tab, out_fmt, vol_fmt, vol_tile, _ptr(_dev(patches)), c_void_p(_dev(keys, torch.int32).data_ptr()), rows,
-                row0, int(bool(store)), c_void_p(counter.data_ptr()) if counter is not None else None, _stream()),
-                "vfml_corr_lookup_indirect_bidir_cached")
-    elif bidir is not None:
-        dir_coords, dir_out, dir_tab = bidir
-
-        def launch():
-            _check(lib().vfml_corr_lookup_indirect_bidir(c_void_p(table.data_ptr()), (c_int32 * L)(*hl), (c_int32 * L)(*wl),
-                                                         (c_int32 * L)(*ld), L, radius, nmaps, q_per_map,
-                                                         _ptr(_dev(coords), coords_off), ld_coords, dir_coords,
-                                                         _ptr(_dev(out), out_off), ld_out, dir_out, dir_tab, out_fmt, vol_fmt,
-                                                         vol_tile, _stream()), "vfml_corr_lookup_indirect_bidir")
-    elif table is not None:
-        def launch():
-            _check(lib().vfml_corr_lookup_indirect(c_void_p(table.data_ptr()), (c_int32 * L)(*hl), (c_int32 * L)(*wl),
-                                                   (c_int32 * L)(*ld), L, radius, nmaps, q_per_map,
-                                                   _ptr(_dev(coords), coords_off), ld_coords, _ptr(_dev(out), out_off),
-                                                   ld_out, out_fmt, vol_fmt, vol_tile, _stream()), "vfml_corr_lookup_indirect")
-    else:
+    # the four entry points take the same arguments, plus the second direction's and then the cache's where they have them
+    name = "vfml_corr_lookup"
+    if bidir is None and table is None:
         if pyrs and torch.is_tensor(pyrs[0]):
             pyrs = [pyrs]
         nmaps, L = len(pyrs), len(pyrs[0])
-        ptrs = (c_void_p * (nmaps * L))(*[p.data_ptr() for m in pyrs for p in m])
+        head = (c_void_p * (nmaps * L))(*[p.data_ptr() for m in pyrs for p in m])
+    else:
+        name += "_indirect"
+        head = c_void_p(table.data_ptr())
+    args = [head, (c_int32 * L)(*hl), (c_int32 * L)(*wl), (c_int32 * L)(*ld), L, radius, nmaps, q_per_map]
+    src, dst = [_ptr(_dev(coords), coords_off), ld_coords], [_ptr(_dev(out), out_off), ld_out]
+    if bidir is not None:
+        name += "_bidir"
+        dir_coords, dir_out, dir_tab = bidir
+        src += [dir_coords]
+        dst += [dir_out, dir_tab]
+    args += src + dst + [out_fmt, vol_fmt, vol_tile]
+    if cache is not None:
+        name += "_cached"
+        args += [_ptr(_dev(patches)), c_void_p(_dev(keys, torch.int32).data_ptr()), rows, row0, int(bool(store)),
+                 c_void_p(counter.data_ptr()) if counter is not None else None]
 
-        def launch():
-            _check(lib().vfml_corr_lookup(ptrs, (c_int32 * L)(*hl), (c_int32 * L)(*wl), (c_int32 * L)(*ld), L, radius,
-                                          nmaps, q_per_map, _ptr(_dev(coords), coords_off), ld_coords,
-                                          _ptr(_dev(out), out_off), ld_out, out_fmt, vol_fmt, vol_tile, _stream()), "vfml_corr_lookup")
+    def launch():
+        _check(getattr(lib(), name)(*args, _stream()), name)
+
     if _PROFILE_HBM is None:
         launch()
         return
