@@ -915,6 +915,18 @@ int vfml_inflate_chunks(const unsigned char* data, int64_t data_bytes, const uin
                         int64_t raw_bytes, uint32_t crc_init, void* workspace, unsigned char* raw, uint32_t* crc,
                         int32_t* status, void* stream);
 
+/* Scene-cut statistic of uint8 RGB frames (tests/scene_cut_oracle.py is the definition).
+ * frames: device, [n][H][W][3] contiguous, any alignment (a frame inside a clip).  Per frame t the signature
+ * sig_out[t][16][64] counts the pixels per cell c = (y * 4 / H) * 4 + (x * 4 / W) and per bin Y >> 2 of the luma
+ * Y = (77 R + 150 G + 29 B + 128) >> 8; dist_out[t] = sum |sig[t] - sig[t-1]| over the 1024 counts (at most 2 H W).
+ * Frame 0 is measured against prev_sig (device, uint32[1024], the signature of the frame before this call's first) or
+ * gets 0 when prev_sig is null.  sig_out, dist_out, prev_sig: device, 4-byte aligned; prev_sig may be a row of an earlier
+ * call's sig_out but not of this one's.  All integer, all on `stream` (a memset and two launches), no host
+ * synchronisation, no allocation, the same bytes on every run.  Null frames / sig_out / dist_out, n outside 1..65535, an
+ * empty frame and H * W >= 2^31 return non-zero (vfml_last_error) before anything is launched. */
+int vfml_scene_distances(const unsigned char* frames, int n, int H, int W, const uint32_t* prev_sig, uint32_t* sig_out,
+                         uint32_t* dist_out, void* stream);
+
 const char* vfml_last_error(void);
 int vfml_abi_version(void);
 

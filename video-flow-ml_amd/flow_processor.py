@@ -42,7 +42,7 @@ from processing.flow_inference import VideoFlowInference
 from processing.memflow_inference import MemFlowInference
 from storage import AsyncFlowCacheWriter, FlowCacheManager
 from vfml import dist as vdist
-from vfml.runner import ClipFeeder, check_memory_job, run_sharded
+from vfml.runner import ClipFeeder, check_memory_job, check_scene_job, run_sharded
 from video.frame_extractor import fast_mode_dimensions, resize_frame
 from video.video_info import (SYNTHETIC_FPS, own_avi_reader, probe_video, read_frames, time_to_frame,
                               validate_frame_range)
@@ -411,6 +411,23 @@ def memflow_warm_start():
     return check_warm_start(MEMFLOW_WARM_START, "flow_processor.MEMFLOW_WARM_START")
 
 
+# Scene cuts: None, the clip is one continuous shot, as the reference treats it; (TH, R) or "TH,R" -
+# or True / "1" for the defaults 200,3 - the job finds the clip's cuts from the frames on the device (vfml_scene_distances
+# behind every upload) and keeps what it carries across frames inside a scene: the MOF / BOF window, MemFlow's pair, bank
+# and warm start, and the output video's TAA histories (one GPU; the cache directory carries _cuts and a scenes.json).  The
+# environment variable VFML_SCENE_CUTS (0, 1 or TH,R) overrides it.  No command-line flag: the parser stays the reference's.
+SCENE_CUTS = None
+
+
+def scene_cuts():
+    """SCENE_CUTS, or VFML_SCENE_CUTS when it is set -> None or (TH, R); anything else is refused."""
+    from video.scene_cuts import check_scene_cuts
+    env = os.environ.get("VFML_SCENE_CUTS")
+    if env:
+        return check_scene_cuts(env, "VFML_SCENE_CUTS")
+    return check_scene_cuts(SCENE_CUTS, "flow_processor.SCENE_CUTS")
+
+
 # True: the output video carries the reference's text labels, drawn with the project's own text (DESIGN.md section 9,
 # "Text"): vfml_text_draw behind the composer on the device path, visualization/text.py under --device cpu.  The
 # environment variable VFML_LABELS=1|0 overrides it.  Off: the fixtures cut from the reference and the render tests pin
@@ -434,13 +451,20 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
     overlay (vfml_flow_diff_overlay), and its re-encoded picture takes the flow tile's place.
     width x height is the size the job ran at: the frames' own, or under --fast the reduced one - then `frames` are
     already reduced (--device cpu) or still at the source's size on the host, and the ClipFeeder built here or handed in
-    resizes them on the device (vfml_resize_u8).  A cache whose fields have another size is refused."""
+    resizes them on the device (vfml_resize_u8).  A cache whose fields have another size is refused.
+    A cache directory with a scenes.json (a job with scene cuts on) restarts every TAA history at each
+    scene start: the first frame of a scene is rendered as frame 0 is."""
     from effects.taa_processor import TAAProcessor
     from storage.avi_writer import AviWriter, dib_stride
     from visualization.video_composer import (compose_device, create_6_video_grid, create_difference_overlay,
                                               create_side_by_side)
 
     n = len(frames)
+    from video.scene_cuts import read_scenes
+    scenes = read_scenes(cache_dir)
+    cuts = frozenset(s for s in scenes["starts"] if 0 < s < n) if scenes else frozenset()
+    if scenes:
+        log(f"Scene cuts: {len(cuts) + 1} scenes, the TAA histories restart at frames {sorted(cuts)}")
     cached = tuple(np.shape(FlowCacheManager().load_cached_flow(cache_dir, 0, fmt))[:2])
     if cached != (height, width):
         raise ValueError(f"Flow cache {cache_dir} holds {cached[1]}x{cached[0]} fields, the frames are {width}x{height}: "
@@ -492,6 +516,10 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
                 field = reader.get(i)
                 viz = encoder.encode(field, width, height) if external is None else None
                 taa_frame = taa_simple_frame = None
+                if i in cuts:               # a scene starts: nothing of the old one is blended in
+                    prev = None
+                    for t in (taa_flow, taa_simple, taa_external):
+                        t.reset_history()
                 if taa:
                     taa_frame = taa_flow.apply_taa(frames[i], flow_pixels=prev, alpha=0.1, use_flow=True,
                                                    sequence_id='flow_taa')
@@ -519,7 +547,7 @@ def render_video(args, frames, fps, width, height, cache_dir, fmt, device, feede
                            args.uncompressed, taa_flow, taa_simple, dib_stride, compose_device, external=external,
                            taa_external=taa_external, variant=variant, clamp_range=args.motion_vectors_clamp_range,
                            label_ops=_label_ops(width, height, taa, flow_only, external is not None, model_name,
-                                                args.fast, args.flow_format) if labels else None)
+                                                args.fast, args.flow_format) if labels else None, cuts=cuts)
     finally:
         if external is not None:
             external.close()
@@ -544,7 +572,7 @@ def _label_ops(width, height, taa, flow_only, grid6, model_name, fast_mode, flow
 
 def _render_device(frames, width, height, device, feeder, reader, encoder, taa, flow_only, writer, size, uncompressed,
                    taa_flow, taa_simple, dib_stride, compose_device, external=None, taa_external=None, variant=None,
-                   clamp_range=32.0, label_ops=None):
+                   clamp_range=32.0, label_ops=None, cuts=frozenset()):
     from vfml import hip
     n = len(frames)
     text_plan = None            # the labels of the layout, compiled once: drawn on every composed frame
@@ -593,6 +621,11 @@ def _render_device(frames, width, height, device, feeder, reader, encoder, taa, 
             fevents[k].record(stream)
         viz = encoder.encode(field, width, height) if external is None else None
         taa_frame = taa_simple_frame = None
+        if i in cuts:                       # a scene starts: nothing of the old one is blended in
+            prev = None
+            for t in (taa_flow, taa_simple, taa_external):
+                if t is not None:
+                    t.reset_history()
         if taa:
             taa_frame = taa_flow.apply_taa(frame, flow_pixels=prev, alpha=0.1, use_flow=True, sequence_id='flow_taa')
             taa_simple_frame = taa_simple.apply_taa(frame, flow_pixels=None, alpha=0.1, use_flow=False,
@@ -668,10 +701,16 @@ def main(argv=None):
     draw_labels()               # (likewise VFML_LABELS)
     memory = memflow_memory()   # (likewise VFML_MEMFLOW_MEMORY)
     warm = memflow_warm_start()  # (likewise VFML_MEMFLOW_WARM_START)
+    try:
+        cuts = scene_cuts()     # (likewise VFML_SCENE_CUTS)
+    except ValueError as e:
+        log(f"Error: {e}")
+        return 1
     if args.model != 'memflow':
         memory, warm = 0, False
     try:
         check_memory_job(memory, bool(args.tile), world, warm)
+        check_scene_job(cuts, not args.tile, world)
     except ValueError as e:
         log(f"Error: {e}")
         return 1
@@ -706,7 +745,7 @@ def main(argv=None):
     cache_dir = args.use_flow_cache or mgr.generate_cache_path(
         cache_src, start, n, args.sequence_length, args.fast, args.tile, args.model,
         args.stage if memflow else args.vf_dataset, args.vf_architecture, args.vf_variant, memory_frames=memory,
-        warm_start=warm)
+        warm_start=warm, scene_cuts=cuts)
     complete, fmt, missing = mgr.check_cache_exists(cache_dir, n)
     if complete and not args.force_recompute:
         if args.interactive:
@@ -726,7 +765,8 @@ def main(argv=None):
     eng.load_model()
     proc = eng.get_processor()
     # frames go up through a pinned ring while earlier fields compute (--fast: and are resized on the device behind it)
-    feeder = ClipFeeder(frames, device, size=(height, width))
+    # (with scene cuts on: and measured against their predecessor there)
+    feeder = ClipFeeder(frames, device, size=(height, width), scene_cuts=cuts)
     save_format = args.save_flow or 'npz'
     tiled = bool(args.tile and not memflow)
     num_lods = 0 if args.skip_lods else 5
@@ -768,6 +808,13 @@ def main(argv=None):
     dt = time.time() - t0
     if writer is not None:
         writer.close()
+    if cuts and rank == 0:
+        from video.scene_cuts import write_scenes
+        feeder.ensure(n - 1)                        # (every frame has been measured: the job reached the last one)
+        index = feeder.scenes
+        write_scenes(cache_dir, index)
+        log(f"Scene cuts (threshold {index.th}, ratio {index.r}): {len(index.starts)} scenes, starting at frames "
+            f"{index.starts}")
     if torch.distributed.is_initialized():
         torch.distributed.barrier()                 # every rank's files are on disk
     if rank == 0:

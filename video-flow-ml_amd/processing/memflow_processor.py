@@ -49,9 +49,17 @@ class MemFlowProcessor:
                 raise ValueError(f"Frame {i} shape {f.shape} differs from first frame {first.shape}")
         return True
 
+    scenes = None       # set by a job with scene cuts on (vfml.runner), for the job's duration; None: the clip is one shot
+
+    def _scene_start(self, frame_idx):
+        """First frame of frame_idx's scene (video.scene_cuts.SceneIndex); 0 without an index: the clip is one scene."""
+        return 0 if self.scenes is None else self.scenes.scene_of(frame_idx, 0)[0]
+
     def window_indices(self, frame_idx):
+        """The `sequence_length` frames ending at frame_idx, clamped at the clip's - with a scene index, the scene's - first
+        frame and front-padded by repeating it."""
         end = frame_idx + 1
-        idx = list(range(max(0, end - self.sequence_length), end))
+        idx = list(range(max(self._scene_start(frame_idx), end - self.sequence_length), end))
         while len(idx) < self.sequence_length:
             idx.insert(0, idx[0])
         return idx
@@ -113,7 +121,8 @@ class MemFlowProcessor:
     def compute_optical_flow_resident_batch(self, clip, frame_idxs):
         """Fields of several frames of a resident clip -> list of device tensors [H,W,2].  Runs of consecutive
         frames (pairs (i-1, i), same branch of the range heuristic) go through the engine PAIR_BATCH at a time;
-        frame 0 (pair (0, 0)) and anything irregular one by one.  Same fields as compute_optical_flow_resident."""
+        frame 0 (pair (0, 0)), with a scene index the first frame a of every scene (pair (a, a)), and anything irregular one
+        by one.  Same fields as compute_optical_flow_resident."""
         from vfml.clip_id import clip_token
         from vfml.network import take_frames
         frame_idxs = list(frame_idxs)
@@ -130,8 +139,9 @@ class MemFlowProcessor:
         while k < len(frame_idxs):
             i = frame_idxs[k]
             e = k
-            if i >= 1:
+            if i > self._scene_start(i):
                 while (e + 1 < len(frame_idxs) and e + 1 - k < self.PAIR_BATCH and frame_idxs[e + 1] == frame_idxs[e] + 1
+                       and self._scene_start(frame_idxs[e + 1]) < frame_idxs[e + 1]
                        and mode_of(frame_idxs[e + 1]) == mode_of(i)):
                     e += 1
             if e == k:
@@ -156,7 +166,9 @@ class MemFlowProcessor:
         values of the fields before it, so fields are not batched (field t needs field t-1's value map).  With `warm_start`
         field i also starts from field i-1's flow projected forward (with memory_frames = 0 that is all the stream carries).
         The stream carries over from one call to the next while the frames stay consecutive in one clip; anything else -
-        begin_stream_job(), another clip, a gap, a step back - starts from an empty bank and a zero flow."""
+        begin_stream_job(), another clip, a gap, a step back - starts from an empty bank and a zero flow.  With a scene index
+        the stream is reset() before the first field of every scene - bank and kept flow both go - and that field is the pair
+        (a, a) of the scene's first frame."""
         from vfml.clip_id import clip_token
         from vfml.network import take_frames
         core = self.core_engine
@@ -164,9 +176,12 @@ class MemFlowProcessor:
         tok = clip_token(clip)
         out = []
         for i in frame_idxs:
+            a = self._scene_start(i)
             if self._stream_at != (tok, i - 1) or core._stream is None:
                 core.open_stream()
-            ids = [max(0, i - 1), i]
+            elif i == a:
+                core._stream.reset()
+            ids = [max(a, i - 1), i]
             m = max(mx[j] for j in self.window_indices(i))
             mode = 0 if m > 2.0 else (1 if m > 1.0 else 2)
             x = take_frames(clip, ids).permute(0, 3, 1, 2).float().unsqueeze(0)

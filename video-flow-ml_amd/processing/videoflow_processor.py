@@ -26,6 +26,19 @@ except ImportError:                     # pragma: no cover - xxhash is part of t
 HOST_FRAME_CACHE = 24                   # uint8 frames kept in HBM for the host-array API (LRU)
 
 
+def _clip_window(T, num_frames, frame_idx):
+    """The reference's T-frame window of `frame_idx` in a clip of `num_frames` (VideoFlowProcessor.window_indices)."""
+    half = T // 2
+    start = max(0, frame_idx - half)
+    idx = list(range(start, min(num_frames, frame_idx + half + 1)))
+    while len(idx) < T:
+        if start == 0:
+            idx.insert(0, idx[0])
+        else:
+            idx.append(idx[-1])
+    return idx[:T]
+
+
 class VideoFlowProcessor:
     def __init__(self, device, fast_mode=False, tile_mode=False, sequence_length=5,
                  dataset='sintel', architecture='mof', variant='standard'):
@@ -67,17 +80,17 @@ class VideoFlowProcessor:
     def window_indices(self, num_frames, frame_idx):
         """Frame indices of the T-frame window the reference builds for `frame_idx` (:133-147):
         centred, clipped to the clip, then padded to T by repeating the first frame at the front when
-        the window starts at frame 0, else the last frame at the back."""
+        the window starts at frame 0, else the last frame at the back.
+        With a scene index set (`scenes`, a video.scene_cuts.SceneIndex: a job with scene cuts on, vfml.runner) the window
+        is that of the frame's scene [a, b) taken as a clip of its own: the same rule on (b - a, frame_idx - a), shifted
+        by a - no window mixes two scenes."""
         T = self.sequence_length
-        half = T // 2
-        start = max(0, frame_idx - half)
-        idx = list(range(start, min(num_frames, frame_idx + half + 1)))
-        while len(idx) < T:
-            if start == 0:
-                idx.insert(0, idx[0])
-            else:
-                idx.append(idx[-1])
-        return idx[:T]
+        scenes = getattr(self, "scenes", None)
+        if scenes is not None:
+            return scenes.scene_window(lambda n, i: _clip_window(T, n, i), frame_idx, T // 2)
+        return _clip_window(T, num_frames, frame_idx)
+
+    scenes = None       # set by a job with scene cuts on, for the job's duration; None: the clip is one shot
 
     def prepare_frame_sequence(self, frames, frame_idx):
         """list of [H,W,3] arrays -> float32 tensor [1,T,3,H,W] on the device; u8 is scaled by 1/255,
@@ -133,7 +146,7 @@ class VideoFlowProcessor:
         return flows[0, flows.shape[1] // 2].permute(1, 2, 0).cpu().numpy()
 
     def compute_optical_flow(self, frames, frame_idx):
-        """-> numpy [H,W,2] float32, pixels."""
+        """-> numpy [H,W,2] float32, pixels.  (Random access on host frames: `scenes` belongs to a job's resident clip.)"""
         self._require_model()
         fast = self._flow_from_host_u8(frames, frame_idx)
         if fast is not None:

@@ -198,12 +198,12 @@ class FlowCacheManager:
     def generate_cache_path(self, input_path: str, start_frame: int, max_frames: int, sequence_length: int,
                             fast_mode: bool, tile_mode: bool, model: str = 'videoflow', dataset: str = 'things',
                             architecture: str = 'mof', variant: str = 'noise', memory_frames: int = 0,
-                            warm_start: bool = False) -> str:
+                            warm_start: bool = False, scene_cuts=None) -> str:
         from .filename_generator import generate_cache_directory
         return generate_cache_directory(input_path=input_path, start_frame=start_frame, max_frames=max_frames,
                                         sequence_length=sequence_length, fast_mode=fast_mode, tile_mode=tile_mode,
                                         model=model, dataset=dataset, architecture=architecture, variant=variant,
-                                        memory_frames=memory_frames, warm_start=warm_start)
+                                        memory_frames=memory_frames, warm_start=warm_start, scene_cuts=scene_cuts)
 
     def check_cache_exists(self, cache_dir: str, max_frames: int) -> Tuple[bool, Optional[str], List[int]]:
         """(complete?, 'npz'|'flo'|None, missing frame indices).  Any .npz in the directory (LOD files

@@ -47,12 +47,15 @@ def generate_output_filepath(input_path: str, output_dir: str, **kwargs) -> str:
 def generate_cache_directory(input_path: str, start_frame: int = 0, max_frames: int = 1000,
                              sequence_length: int = 5, fast_mode: bool = False, tile_mode: bool = False,
                              model: str = 'videoflow', dataset: str = 'things', architecture: str = 'mof',
-                             variant: str = 'noise', memory_frames: int = 0, warm_start: bool = False) -> str:
-    """`{stem}_flow_cache_{model}[_{arch}_{dataset}_{variant} | _{dataset}]_seq{T}_start{s}_frames{n}[_fast][_tile][_mem{N}][_warm]`
+                             variant: str = 'noise', memory_frames: int = 0, warm_start: bool = False,
+                             scene_cuts=None) -> str:
+    """`{stem}_flow_cache_{model}[_{arch}_{dataset}_{variant} | _{dataset}]_seq{T}_start{s}_frames{n}[_fast][_tile][_mem{N}][_warm][_cuts]`
     next to the input video.  `_mem{N}` (an extension): a MemFlow job whose fields read a memory bank of N > 0 earlier fields
     - other fields than the memory-free job's, so another cache; every name without a bank is unchanged.  `_warm` (an
     extension, after `_mem{N}`): a MemFlow job whose fields start from the previous field's projected flow - other fields
-    again; every name without the warm start is unchanged."""
+    again; every name without the warm start is unchanged.  `_cuts`, or `_cuts{TH}x{R}` off the default threshold and
+    ratio (an extension, last): a job whose windows stay inside the scenes it detected (scene_cuts = (TH, R),
+    video/scene_cuts.py) - other fields near a cut; every name with scene cuts off (None) is unchanged."""
     src = Path(input_path)
     ident = [model]
     if model == 'videoflow':
@@ -68,4 +71,7 @@ def generate_cache_directory(input_path: str, start_frame: int = 0, max_frames: 
         run.append(f"mem{int(memory_frames)}")
     if warm_start:
         run.append("warm")
+    if scene_cuts:
+        from video.scene_cuts import cache_suffix
+        run.append(cache_suffix(scene_cuts))
     return str(src.parent / f"{src.stem}_flow_cache_{'_'.join(ident)}_{'_'.join(run)}")

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VFML_LIB") or os.path.join(_HERE, "libvfml_hip.so")   # VFML_LIB: experiment builds
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "corr_ensure.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip", "warm_start.hip"]
+SOURCES = ["api.hip", "conv_gemm.hip", "conv_gemm_split.hip", "corr_ensure.hip", "conv_gemm_tapx.hip", "conv_split_plan.hip", "stem.hip", "flow_half.hip", "enc_conv.hip", "norm_pool.hip", "flow_ops.hip", "effects.hip", "correct.hip", "render.hip", "text.hip", "turbulence.hip", "resize.hip", "jpeg.hip", "jpeg_decode.hip", "jpeg_decode_sync.hip", "deflate.hip", "attention.hip", "dwconv.hip", "twins.hip", "warm_start.hip", "scene.hip"]
 
 STATS_ROWS_F32, STATS_ROWS_S16 = 128, 32    # pixels per stats_part block (include/vfml.h VFML_STATS_ROWS_*)
 EPI_NONE, EPI_RELU, EPI_TANH, EPI_SIGMOID, EPI_TANH_RELU, EPI_GRU_ZR, EPI_GRU_Q, EPI_ADD_AUX = range(8)
@@ -255,6 +255,7 @@ def lib():
     L.vfml_inflate_chunks.argtypes = [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, ctypes.c_uint32, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p]
     L.vfml_convex_upsample.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.vfml_scene_distances.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
     for name in EXPORTS:
         getattr(L, name)  # AttributeError here = header/library drift
     if L.vfml_abi_version() != 27:
@@ -280,7 +281,7 @@ EXPORTS = [
     "vfml_jpeg_decode_sampled_workspace_bytes", "vfml_jpeg_decode_rgb_sampled",
     "vfml_jpeg_decode_sync_sampled_workspace_bytes", "vfml_jpeg_decode_rgb_sync_sampled",
     "vfml_deflate_capacity", "vfml_deflate_workspace_bytes", "vfml_deflate_huffman",
-    "vfml_inflate_workspace_bytes", "vfml_inflate_chunks",
+    "vfml_inflate_workspace_bytes", "vfml_inflate_chunks", "vfml_scene_distances",
     "vfml_last_error", "vfml_abi_version",
 ]
 
@@ -1285,6 +1286,40 @@ def resize_u8(src, size, out=None):
     _check(lib().vfml_resize_u8(c_void_p(src.data_ptr()), n, H, W, sstride, c_void_p(out.data_ptr()), h, w, dstride, xt, yt,
                                 _stream()), "vfml_resize_u8")
     return out
+
+
+SCENE_CELLS, SCENE_BINS = 16, 64        # a frame's scene-cut signature: uint32 [16 cells][64 luma bins]
+
+
+def scene_distances(frames, prev_sig=None, out=None):
+    """uint8 RGB frames [n,H,W,3] (or one [H,W,3]; a contiguous device tensor, frames of a clip included) -> (sig, dist):
+    int32 device tensors [n,1024] and [n] holding the uint32 signatures and distances of vfml_scene_distances (DESIGN.md
+    section 20) - read them as uint32 (`.cpu().numpy().view(numpy.uint32)`).  Stream-ordered, no synchronisation.
+    prev_sig: the signature (int32 [1024], device) of the frame before frames[0]; None: dist[0] = 0.
+    out: (sig, dist) tensors of those shapes to fill - rows of larger buffers, say - instead of fresh ones."""
+    if not (torch.is_tensor(frames) and frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() in (3, 4)
+            and frames.shape[-1] == 3 and frames.is_contiguous()):
+        raise ValueError(f"scene_distances: frames must be a contiguous uint8 device tensor [n,H,W,3] or [H,W,3], got "
+                         f"{getattr(frames, 'dtype', type(frames))} {tuple(getattr(frames, 'shape', ()))}")
+    n = 1 if frames.dim() == 3 else int(frames.shape[0])
+    H, W = int(frames.shape[-3]), int(frames.shape[-2])
+    words = SCENE_CELLS * SCENE_BINS
+    if out is None:
+        sig = torch.empty((n, words), dtype=torch.int32, device=frames.device)
+        dist = torch.empty((n,), dtype=torch.int32, device=frames.device)
+    else:
+        sig, dist = out
+        for t, shape, name in ((sig, (n, words), "sig"), (dist, (n,), "dist")):
+            if not (torch.is_tensor(t) and t.dtype == torch.int32 and t.device == frames.device and tuple(t.shape) == shape
+                    and t.is_contiguous()):
+                raise ValueError(f"scene_distances: out {name} must be a contiguous int32 tensor {shape} on {frames.device}")
+    if prev_sig is not None and not (torch.is_tensor(prev_sig) and prev_sig.dtype == torch.int32 and prev_sig.numel() == words
+                                     and prev_sig.device == frames.device and prev_sig.is_contiguous()):
+        raise ValueError(f"scene_distances: prev_sig must be a contiguous int32 tensor of {words} counts on {frames.device}")
+    _check(lib().vfml_scene_distances(c_void_p(frames.data_ptr()), n, H, W,
+                                      None if prev_sig is None else c_void_p(prev_sig.data_ptr()), c_void_p(sig.data_ptr()),
+                                      c_void_p(dist.data_ptr()), _stream()), "vfml_scene_distances")
+    return sig, dist
 
 
 _JPEG_WS = {}

@@ -97,14 +97,21 @@ class ClipFeeder:
 
     With a target `size` (h, w) - the --fast resolution - the clip is [F,h,w,3]: a frame still crosses PCIe once, as
     uint8 at its source size, into a staging slot on the device, and vfml_resize_u8 writes clip[f] from there on the same
-    side stream before the frame counts as ready.  A CPU "device" resizes on the host (video.resize_frame; the same bytes)."""
+    side stream before the frame counts as ready.  A CPU "device" resizes on the host (video.resize_frame; the same bytes).
+
+    With `scene_cuts` = (TH, R) the feeder also finds the clip's scene cuts: behind a frame's upload
+    - and its resize - on the same side stream, vfml_scene_distances measures clip[f] against the signature of clip[f-1]
+    kept on the device, the 4-byte distance goes to a pinned cell, and an event marks it.  `scenes` (video.scene_cuts
+    .SceneIndex) takes the scores in as they are asked for: reading one waits for that frame's event only, never for the
+    stream that computes.  A CPU "device" takes the numpy definition."""
 
     RING = 4
 
-    def __init__(self, frames, device, size=None):
+    def __init__(self, frames, device, size=None, scene_cuts=None):
         """frames: list of uint8 [H,W,3] arrays; entries may be None where this process will never need the frame (another
         rank's stretch of a sharded clip): those are never uploaded, and asking for one raises.
-        size: None, or the (h, w) the clip holds the frames at (the frames' own size means None)."""
+        size: None, or the (h, w) the clip holds the frames at (the frames' own size means None).
+        scene_cuts: None, or (TH, R) of video.scene_cuts."""
         f0 = next(f for f in frames if f is not None)
         self.device = torch.device(device)
         self.src_shape = tuple(f0.shape)
@@ -130,6 +137,18 @@ class ClipFeeder:
                 if not (self.src_shape[0] == 2 * size[0] and self.src_shape[1] == 2 * size[1]):
                     hip.resize_tables(self.src_shape[1], size[1], self.device)
                     hip.resize_tables(self.src_shape[0], size[0], self.device)
+        self.scene_cuts = None if scene_cuts is None else (int(scene_cuts[0]), int(scene_cuts[1]))
+        self.scenes = None
+        if self.scene_cuts is not None:
+            if len(shape) != 3 or shape[2] != 3:
+                raise ValueError(f"ClipFeeder: scene cuts need [H,W,3] frames, got {self.src_shape}")
+            if self.on_gpu:
+                from . import hip
+                F = len(frames)
+                self.cut_sig = torch.empty((F, hip.SCENE_CELLS * hip.SCENE_BINS), dtype=torch.int32, device=self.device)
+                self.cut_dist = torch.empty((F,), dtype=torch.int32, device=self.device)
+                self.cut_host = torch.zeros((F,), dtype=torch.int32).pin_memory()
+                self.cut_host_np = self.cut_host.numpy().view(np.uint32)
         self.reset(frames)
 
     def reset(self, frames):
@@ -147,6 +166,11 @@ class ClipFeeder:
         self.clip._vfml_clip_token = (new_id(), "fed")
         self.clip._vfml_frame_maxima = _LazyMaxima(frames) if self.size is None else _LazyResizedMaxima(frames, self.size)
         self.clip._vfml_frames_ready = 0
+        if self.scene_cuts is not None:
+            from video.scene_cuts import SceneIndex
+            self.scenes = SceneIndex(len(frames), *self.scene_cuts, source=self._cut_score)
+            self.cut_events = [None] * len(frames)      # device path: recorded behind a frame's 4-byte distance copy
+            self._cut_prev, self._cut_scores = None, {}  # host path: the signature of frame next - 1, the scores so far
         if self.on_gpu:
             self.stream.wait_stream(torch.cuda.current_stream(self.device))   # earlier readers of the old frames
 
@@ -156,8 +180,25 @@ class ClipFeeder:
         contiguous run [lo, next): with an uploaded prefix the frames in between simply go up as `ensure` reaches them)."""
         frame = max(0, min(frame, len(self.frames)))
         if frame > self.next and self.next == self.lo:
-            self.lo = self.next = frame
+            self._move_lo(frame)
             self.clip._vfml_frames_ready = self.next
+
+    def _move_lo(self, frame):
+        self.lo = self.next = frame
+        if self.scenes is not None:         # (nothing has been uploaded: the scenes are counted from the first frame held)
+            from video.scene_cuts import SceneIndex
+            self.scenes = SceneIndex(len(self.frames), *self.scene_cuts, first=frame, source=self._cut_score)
+
+    def _cut_score(self, f):
+        """The per-mille score of frame f against frame f - 1 as the clip holds them, or None while f has not been uploaded.
+        Device path: waits for that frame's own event - recorded on the side stream - and reads its pinned cell."""
+        from video.scene_cuts import score
+        if not self.lo <= f < self.next:
+            return None
+        if not self.on_gpu:
+            return self._cut_scores[f]
+        self.cut_events[f].synchronize()
+        return score(int(self.cut_host_np[f]), self.clip.shape[1], self.clip.shape[2])
 
     def require(self, first):
         """A window is about to read frames from `first` on: they must be resident (a second job on the same feeder that
@@ -171,7 +212,7 @@ class ClipFeeder:
         about to read - not having that one is an error."""
         upto = min(upto, len(self.frames) - 1)
         while self.next == self.lo and self.next <= upto and self.frames[self.next] is None:
-            self.lo = self.next = self.next + 1         # (leading frames this process does not hold: skipped like skip_to's)
+            self._move_lo(self.next + 1)                # (leading frames this process does not hold: skipped like skip_to's)
         for f in range(self.next, upto + 1):
             if self.frames[f] is None:          # another rank's stretch: the read-ahead stops here
                 upto = f - 1
@@ -188,6 +229,12 @@ class ClipFeeder:
                     from video.frame_extractor import resize_frame
                     frame = resize_frame(frame, (self.size[1], self.size[0]))
                 self.clip[f] = torch.from_numpy(np.ascontiguousarray(frame))
+                if self.scenes is not None:
+                    from video.scene_cuts import frame_signature, score, signature_distance
+                    sig = frame_signature(frame)
+                    d = 0 if f == self.lo else signature_distance(sig, self._cut_prev)
+                    self._cut_prev = sig
+                    self._cut_scores[f] = score(d, frame.shape[0], frame.shape[1])
             self.next = upto + 1
             self.clip._vfml_frames_ready = self.next
             return
@@ -208,10 +255,39 @@ class ClipFeeder:
                     hip.resize_u8(self.staging[r], self.size, out=self.clip[f])
                 last = torch.cuda.Event()
                 last.record(self.stream)
+                if self.scenes is not None:
+                    # behind the frame's own event: nothing that waits for the frame waits for its statistic
+                    from . import hip
+                    hip.scene_distances(self.clip[f:f + 1], prev_sig=self.cut_sig[f - 1] if f > self.lo else None,
+                                        out=(self.cut_sig[f:f + 1], self.cut_dist[f:f + 1]))
+                    self.cut_host[f:f + 1].copy_(self.cut_dist[f:f + 1], non_blocking=True)
+                    self.cut_events[f] = torch.cuda.Event()
+                    self.cut_events[f].record(self.stream)
             self.events[r] = last
         self.next = upto + 1
         self.clip._vfml_frames_ready = self.next      # frames [lo, next) are (stream-ordered) in the clip: what a prefetch may read
         torch.cuda.current_stream(self.device).wait_event(last)    # (copies on one stream complete in order)
+
+
+def check_scene_job(cuts, whole, world):
+    """What a job with scene cuts cannot be: spread over several ranks - a rank holds only its stretch of the clip and cannot
+    see every cut, and the fields would depend on the number of ranks.  (A tiled job on one rank is fine.)"""
+    if cuts and world > 1:
+        raise ValueError(f"scene cuts (VFML_SCENE_CUTS) need the whole clip on one GPU: a job over {world} ranks gives "
+                         f"every rank only its stretch of the frames, which cannot see every cut; run it on one GPU")
+
+
+def resident_scene_index(clip, cuts):
+    """The complete SceneIndex of a clip already on its device: all distances in one call (vfml_scene_distances; a CPU
+    "device" takes the numpy definition)."""
+    from video.scene_cuts import host_scene_index, index_of, score
+    th, r = cuts
+    if not clip.is_cuda:
+        return host_scene_index([f for f in clip.numpy()], th, r)
+    from . import hip
+    _, dist = hip.scene_distances(clip.contiguous())
+    h, w = clip.shape[1:3]
+    return index_of([score(int(d), h, w) for d in dist.cpu().numpy().view(np.uint32)], th, r)
 
 
 def memory_frames(proc):
@@ -361,7 +437,7 @@ class _Unpacker(threading.Thread):
 
 def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, group=None, on_field=None,
                 collect=True, num_lods=0, chunk=None, feeder=None, prepare_only=False, local_sink=None, out=None,
-                device_npz=None, continue_stream=False):
+                device_npz=None, continue_stream=False, scene_cuts=None):
     """Compute the flow field of every frame in `frame_indices` of the device-resident uint8 clip [F,H,W,3]
     (`clip` may be None when a ClipFeeder is given: its clip is used and fed as the job advances).
     Returns on rank 0 a float32 numpy array [len(frame_indices), H, W, 2] (None with collect=False, when the
@@ -383,7 +459,10 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     grows by 5 GB/s; first-touch page faults of a fresh array would be part of what is measured).
     continue_stream (MemFlow with a memory bank or the warm start): the job goes on where the processor's last one ended - its
     bank and kept flow stay while the frames follow on in the same clip (MemFlowProcessor.compute_optical_flow_stream);
-    otherwise a job starts with an empty bank, and cold, at its first frame."""
+    otherwise a job starts with an empty bank, and cold, at its first frame.
+    scene_cuts: None, or (TH, R): the windows stay inside their scenes and a stream restarts at each
+    scene start.  With a feeder the feeder's own setting counts (ClipFeeder(..., scene_cuts=)); a resident clip gets all its
+    distances in one call before the job.  One rank only."""
     frame_indices = list(frame_indices)
     if feeder is not None:
         clip = feeder.clip
@@ -392,6 +471,9 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     whole = len(tiles) == 1
     on_gpu = clip.is_cuda
     check_memory_job(memory_frames(proc), not whole, world, warm_start(proc))
+    if feeder is not None:
+        scene_cuts = feeder.scene_cuts
+    check_scene_job(scene_cuts, whole, world)
     local = local_sink is not None or device_npz is not None
     if local and (not whole or collect or on_field is not None):
         raise ValueError("local_sink applies to whole-frame jobs and replaces collect / on_field")
@@ -452,6 +534,9 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
 
     if feeder is not None and mine:
         feeder.skip_to(min(f for f, _ in mine) - seq)       # (a window reaches at most seq - 1 frames back)
+    scenes = None
+    if scene_cuts is not None and not prepare_only:
+        scenes = feeder.scenes if feeder is not None else resident_scene_index(clip, scene_cuts)
 
     def window(f):
         """Frames the processor reads for field f (VideoFlow: centred, seq // 2 either side; MemFlow: the seq - 1 before it)."""
@@ -465,8 +550,15 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
 
     def feed(first, last):
         if feeder is not None:
-            feeder.require(min(window(first)))
-            feeder.ensure(last + seq, need=max(window(last)))   # the window's last frame, and a few more ahead of use
+            if scenes is None:
+                feeder.require(min(window(first)))
+                feeder.ensure(last + seq, need=max(window(last)))   # the window's last frame, and a few more ahead of use
+            else:
+                # a window is known once its frames' scores are: upload first (one frame further: a scene start is decided
+                # by the score of the frame after it), then ask
+                feeder.ensure(last + seq + 1)
+                feeder.require(min(window(first)))
+                feeder.ensure(last + seq + 1, need=max(window(last)))
 
     def compute_chunk(c, sbuf):
         part = mine[c * K:(c + 1) * K]
@@ -612,6 +704,7 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
     # blocked on a host-blocking collective - gloo - or on the unpack thread being a ring of chunks behind)
     trace = [] if os.environ.get("VFML_RUNNER_TIMING") else None
     prev = None
+    proc.scenes = scenes                # window_indices and the batching follow it; None: the clip is one shot
     try:
         for c in range(n_chunks):
             b = c % nb
@@ -639,6 +732,7 @@ def run_sharded(proc, clip, frame_indices, tile_mode=False, rank=0, world=1, gro
         if prev is not None:
             finish(*prev)
     finally:
+        proc.scenes = None
         if unpacker is not None:
             unpacker.close()
         if pool is not None:
