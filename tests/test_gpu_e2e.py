@@ -150,7 +150,7 @@ def test_context_store_ring_wraps_and_falls_back(gpu, monkeypatch):
     for i in range(nfr):                                   # the sliding job
         a = proc.compute_optical_flow_resident(clip, i)
         assert torch.equal(a, ref[i]), i
-        live = sorted(net._ctx_store["live"])
+        live = sorted(net._ctx_store.ring.live)
         wrapped += live != list(range(live[0], live[0] + len(live)))
     assert wrapped >= 2                                    # (windows whose centres straddle the end of the ring)
     order = np.random.default_rng(0).permutation(nfr)

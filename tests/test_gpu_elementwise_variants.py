@@ -134,7 +134,7 @@ def _check(variant, kind, T, H, W, plane, precision, drift=None):
     if plane is None:
         assert store is None
     else:
-        assert store["plain"] == plane, (H // 8 * (W // 8), store["plain"])
+        assert store.plain == plane, (H // 8 * (W // 8), store.plain)
     ref, ref_low = pair["f64"]
     M = 1 if over.get("network") == "BOFNet" else T - 2
     assert got.shape == ref.shape == (1, 2 * M, 2, H, W)

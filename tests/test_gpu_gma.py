@@ -68,7 +68,7 @@ def test_gma_forward_matches_oracle(gpu, T, H, W, form):
     ref = _oracle_field(T, H, W)
     got, _ = net(_frames(T, H, W).cuda(), {})
     got = got.cpu()
-    assert net._att_store["plain"] == (form == "plane")
+    assert net._att_store.plain == (form == "plane")
     assert got.shape == ref.shape == (1, 2 * (T - 2), 2, H, W)
     assert torch.isfinite(got).all()
     e = _epe(got, ref)
@@ -152,7 +152,7 @@ def test_gma_sliding_job_is_exact(gpu):
     assert any(isinstance(g, torch.cuda.CUDAGraph) for g in net2._graphs.values())
     for i in range(8):
         assert torch.equal(eager[i], graphed[i]), i
-    assert net2._att_store["R"] == 5 and len(net2._att_store["A"]) == 5
+    assert net2._att_store.ring.R == 5 and len(net2._att_store.A) == 5
 
 
 def test_plain_checkpoint_allocates_no_plane(gpu):

@@ -1,10 +1,9 @@
-"""The per-frame store of first-iteration motion features (vfml/network.py Iter0Ring, MOFNetHIP._iter0_store) and the
-window set-up pass that feeds it (vfml_window_seed): a window that takes its older centres' rows from the store gives the
-bits of the same window computed from scratch, whatever happened to the store before."""
-import collections
+"""The per-frame store of first-iteration motion features (MOFNetHIP._iter0_store; its bookkeeping, vfml/frame_store.py
+Iter0Ring, is tested without a GPU in tests/test_frame_store_cpu.py) and the window set-up pass that feeds it
+(vfml_window_seed): a window that takes its older centres' rows from the store gives the bits of the same window computed
+from scratch, whatever happened to the store before."""
 import contextlib
 import io
-import types
 
 import pytest
 import torch
@@ -40,86 +39,6 @@ def _scratch(net, proc, clip, i):
     """Field i with no keys: nothing cached, nothing stored."""
     b, _ = net.forward_u8(clip[proc.window_indices(clip.shape[0], i)])
     return b[0, b.shape[1] // 2].permute(1, 2, 0).clone()
-
-
-def _windows(T, nfr):
-    from processing.videoflow_processor import VideoFlowProcessor
-    me = types.SimpleNamespace(sequence_length=T)
-    return [VideoFlowProcessor.window_indices(me, nfr, i) for i in range(nfr)]
-
-
-# ---------------------------------------------------------------------------------------------- bookkeeping (no GPU)
-def test_ring_bookkeeping_of_a_sliding_job_and_its_clip_ends():
-    from vfml import hip
-    from vfml.network import Iter0Ring
-    cache = collections.OrderedDict()
-    cache[("f", "other kinds stay")] = 1
-    ring = Iter0Ring(8, cache)
-    nfr = 2 * ring.R + 3
-    wins = _windows(5, nfr)
-    assert wins[0] == [0, 0, 0, 1, 2] and wins[1] == [0, 0, 1, 2, 3] and wins[-1] == [nfr - 3, nfr - 2, nfr - 1, nfr - 1, nfr - 1]
-    # the key names the neighbours: frame 0 between (0, 0) and between (0, 1) are different entries
-    assert Iter0Ring.entry_key(wins[0], 1) != Iter0Ring.entry_key(wins[0], 2)
-    assert Iter0Ring.entry_key(wins[0], 2) == Iter0Ring.entry_key(wins[1], 1)
-    assert Iter0Ring.entry_key(wins[0], 2) != Iter0Ring.entry_key(wins[0], 2, tail=(3,))
-    straddle = 0
-    for i, w in enumerate(wins):
-        warm, seeds, new = ring.plan(w)
-        slots, modes = [s for s, _ in seeds], [m for _, m in seeds]
-        assert len(set(slots)) == 3
-        if i == 0:
-            assert not warm and modes == [hip.SEED_STORE] * 3 and len(new) == 3
-        else:            # clamped windows at either end included: the two older centres hit
-            assert warm and modes == [hip.SEED_LOAD, hip.SEED_LOAD, hip.SEED_STORE], (i, modes)
-            assert new == [Iter0Ring.entry_key(w, 3)]
-            assert slots[:2] == prev[1:], i                       # ... in the slots the last window left them in
-            straddle += slots != sorted(slots)
-        prev = slots
-        assert sum(1 for k in cache if k[0] == "m") <= ring.R
-    assert straddle >= 2
-    assert cache[("f", "other kinds stay")] == 1
-    # the same window again: everything is there, nothing is stored twice
-    warm, seeds, new = ring.plan(wins[-1])
-    assert warm and [m for _, m in seeds] == [hip.SEED_LOAD, hip.SEED_LOAD, hip.SEED_NONE] and new == []
-    # a window whose first centre was evicted long ago runs cold and keeps what it still finds
-    warm, seeds, new = ring.plan(wins[nfr - 2])
-    assert warm
-    warm, seeds, new = ring.plan(wins[3])
-    assert not warm and [m for _, m in seeds] == [hip.SEED_STORE] * 3
-    # a cleared cache forgets every entry; forget() gives up a window's promises
-    cache.clear()
-    warm, seeds, new = ring.plan(wins[-1])
-    assert not warm and len(new) == 3
-    ring.forget(new)
-    assert not any(k[0] == "m" for k in cache)
-    assert not ring.plan(wins[-1])[0]
-
-
-def test_ring_bookkeeping_repeated_keys_and_sizes():
-    from vfml import hip
-    from vfml.network import Iter0Ring
-    ring = Iter0Ring(8, {})
-    # a two-frame clip: centres 0 (0, 0) twice and 0 (0, 1) - one slot per key, stored once
-    warm, seeds, new = ring.plan([0, 0, 0, 0, 1])
-    assert not warm and seeds[0][0] == seeds[1][0] != seeds[2][0]
-    assert [m for _, m in seeds] == [hip.SEED_STORE, hip.SEED_NONE, hip.SEED_STORE] and len(new) == 2
-    # the newest centre's key already stored by an older centre of the same window: loaded there, not stored again
-    warm, seeds, new = ring.plan([0, 0, 0, 0, 0])
-    assert warm and [m for _, m in seeds] == [hip.SEED_LOAD, hip.SEED_LOAD, hip.SEED_NONE] and new == []
-    # three-frame windows have one centre: never warm; nine-frame windows have seven
-    assert not Iter0Ring(8, {}).plan([0, 1, 2])[0]
-    ring = Iter0Ring(8, {})
-    assert not ring.plan(list(range(9)))[0]
-    warm, seeds, new = ring.plan(list(range(1, 10)))
-    assert warm and [m for _, m in seeds] == [hip.SEED_LOAD] * 6 + [hip.SEED_STORE]
-    assert len({s for s, _ in seeds}) == 7
-    with pytest.raises(ValueError):
-        Iter0Ring(4, {}).plan(list(range(9)))
-    # another ring over the same cache does not take this one's entries for its own
-    cache = {}
-    a, b = Iter0Ring(8, cache), Iter0Ring(8, cache)
-    a.plan([0, 1, 2, 3, 4])
-    assert not b.plan([1, 2, 3, 4, 5])[0]
 
 
 def test_window_seed_validates_its_arguments_without_a_gpu():

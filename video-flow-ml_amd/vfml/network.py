@@ -28,6 +28,7 @@ import torch
 import torch.nn as nn
 
 from . import hip, update_block
+from .frame_store import FrameContext, Iter0Ring, SlotRing, window_base
 from .weights import (BASE_CORR_LEVELS, BASE_CORR_RADIUS, GMA_NO_BIAS, TWINS_STAGES, TWINS_WS, conv_spec, corr_channel_subset,
                       is_depthwise, pack_conv_weight, pcblock_hidden, sk_blocks, twins_spec)
 
@@ -61,78 +62,6 @@ class _Holder(nn.Module):
         if name not in self._modules:
             self.add_module(name, _Holder())
         return self._modules[name]
-
-
-class Iter0Ring:
-    """Bookkeeping of the iteration-zero store (MOFNetHIP._iter0_store): which slot of a ring holds which centre frame's
-    first-iteration motion features.  No tensors here - slot numbers, keys and the cache dictionary the entries live in
-    (the engine's `_feat_cache`, kind "m": whatever clears that cache forgets the entries, and a slot handed out again
-    takes its old owner's entry along).
-
-    At iteration 0 the flow is zero, so a centre frame's motion features depend on its two correlation pyramids alone -
-    on the frame AND its two neighbours in the window.  The key is therefore the cache keys of all three: a window clamped
-    at the start of a clip gives frame 0 the neighbours (0, 0), the next one (0, 1) - different entries."""
-    _serials = 0
-
-    def __init__(self, slots, cache):
-        Iter0Ring._serials += 1
-        self.R, self.cache, self.next, self.owner, self.serial = slots, cache, 0, [None] * slots, Iter0Ring._serials
-
-    @staticmethod
-    def entry_key(keys, j, tail=()):
-        """Key of frame j (1 <= j <= len(keys) - 2) of a window whose frames have the cache keys `keys`."""
-        return ("m", keys[j - 1], keys[j], keys[j + 1]) + tuple(tail)
-
-    def lookup(self, ek):
-        ent = self.cache.get(ek)
-        if ent is not None and ent[1] == self.serial and self.owner[ent[0]] == ek:
-            return ent[0]
-        return None
-
-    def _take(self, ek, busy):
-        for _ in range(self.R):
-            s = self.next
-            self.next = (s + 1) % self.R
-            if s not in busy:
-                break
-        else:
-            raise RuntimeError("iteration-zero store: every slot is in use by the current window")
-        if self.owner[s] is not None:
-            self.cache.pop(self.owner[s], None)
-        self.owner[s] = ek
-        self.cache[ek] = (s, self.serial)
-        return s
-
-    def forget(self, eks):
-        for ek in eks:
-            s = self.lookup(ek)
-            if s is not None:
-                self.owner[s] = None
-                del self.cache[ek]
-
-    def plan(self, keys, tail=()):
-        """A window's slots: (warm, [(slot, mode)] per centre frame, keys of the entries this window fills).
-        warm: every centre but the newest (the last) has an entry - those are loaded (hip.SEED_LOAD) and only the newest is
-        computed, and stored unless it has an entry already.  Else every centre is computed and those without an entry are
-        stored (hip.SEED_STORE); a key that occurs twice in a window is stored once."""
-        M = len(keys) - 2
-        if M + 1 > self.R:
-            raise ValueError(f"iteration-zero store: {self.R} slots cannot serve {M} centre frames")
-        eks = [self.entry_key(keys, j, tail) for j in range(1, M + 1)]
-        found = [self.lookup(ek) for ek in eks]
-        warm = M >= 2 and all(s is not None for s in found[:-1])
-        busy = {s for s in found if s is not None}
-        out, new = [], []
-        for i, ek in enumerate(eks):
-            s = self.lookup(ek)           # (again: an earlier centre of this window may just have taken a slot for this key)
-            if s is not None:
-                out.append((s, hip.SEED_LOAD if warm and i < M - 1 else hip.SEED_NONE))
-            else:
-                s = self._take(ek, busy)
-                busy.add(s)
-                new.append(ek)
-                out.append((s, hip.SEED_STORE))
-        return warm, out, new
 
 
 class MOFNetHIP(_Holder):
@@ -179,7 +108,6 @@ class MOFNetHIP(_Holder):
                 leaf.bias = nn.Parameter(torch.zeros(cout), requires_grad=False)
         if self.gma:
             self.child("update_block").child("aggregator").gamma = nn.Parameter(torch.zeros(1), requires_grad=False)
-        self._att_store = None
         self._packed = None
         self._packed_key = None
         self._packed_serial = 0
@@ -671,62 +599,52 @@ class MOFNetHIP(_Holder):
         self._it0_store = None
         self._att_store = None
 
+    # ------------------------------------------------------------------ the per-frame stores
+    # Three results are computed once per frame and kept in device memory across the windows the frame is a centre of: the
+    # gates' context parts, the GMA attention planes, the motion features of iteration 0.  Each store is a ring of frame
+    # slots with the bookkeeping of vfml/frame_store.py (SlotRing: round-robin handout past the slots in use, the old
+    # owner's `_feat_cache` entry evicted, a serial that marks the entries of a rebuilt store as stale).  The engine owns the
+    # tensors and the rule by which a store is rebuilt - always behind a prefetch in flight (_join_prefetch).  Below, per
+    # store, only what differs.
+    _ctx_store = _att_store = _it0_store = None       # (class defaults: engines that share this class's plumbing build none)
+
     # ------------------------------------------------------------------ per-frame context parts of the gate convolutions
     # The context part of the four GRU gate convolutions is computed once per frame and ADDED by the gate convolutions of
     # every iteration of every window the frame is a centre of (vfml_conv_desc.addend): [centre frames][cells][256 | 128]
-    # floats, 300 MB per 1080p window.  They live in ONE store per gate, a ring of frame slots handed out in the order frames
+    # floats, 300 MB per 1080p window.  They live in ONE store per gate, its slots handed out in the order frames
     # arrive: the centre frames of a sliding job's window are then consecutive slots, and the gate convolutions - fixed
     # launches of a replayed graph - reach them through a device cell that holds the window's first slot
     # (vfml_conv_desc.addend_ind).  Nothing is gathered per field (round 2: twelve device copies, 0.6 GB of traffic).  The
-    # first slots are mirrored behind the ring so that a window that wraps is consecutive too; a window whose centres are not
-    # in arrival order (random access) is gathered into slots kept for that.
+    # first slots are mirrored behind the ring so that a window that wraps is consecutive too (frame_store.window_base); a
+    # window whose centres are not in arrival order (random access) is gathered into slots kept for that, behind the mirror.
     CTX_RING = 12            # >= FEATURE_CACHE_FRAMES: a cached context entry owns its slot until the ring comes round
     CTX_GATES = (("zr1", 256), ("q1", 128), ("zr2", 256), ("q2", 128))
 
     def _context_store(self, dev, Pn, M):
-        st = getattr(self, "_ctx_store", None)
-        if st is None or st["key"] != (str(dev), Pn) or st["M"] < M:
+        st = self._ctx_store
+        if st is None or st.key != (str(dev), Pn) or st.M < M:
             self._join_prefetch()
             # (a coming window's centres are prefetched while the current one's are being read: two windows' worth and some)
             R = max(self.CTX_RING, 2 * M + 4)
             for k in [k for k in self._feat_cache if k[0] == "c"]:     # (entries of another store)
                 del self._feat_cache[k]
-            st = self._ctx_store = {
-                "key": (str(dev), Pn), "M": M, "R": R, "next": 0, "owner": [None] * R, "live": set(),
-                "serial": getattr(self, "_ctx_serial", 0) + 1,
-                "S": {g: torch.empty((R + 2 * M - 1) * Pn * co, device=dev) for g, co in (() if self.sk else self.CTX_GATES)}}
-            self._ctx_serial = st["serial"]
+            st = self._ctx_store = types.SimpleNamespace(
+                key=(str(dev), Pn), M=M, ring=SlotRing("context", R, self._feat_cache),
+                S={g: torch.empty((R + 2 * M - 1) * Pn * co, device=dev) for g, co in (() if self.sk else self.CTX_GATES)})
         return st
-
-    def _context_slot(self, st, cache_key, busy):
-        """The next slot of the ring (not one of `busy`); whoever owned it loses its cache entry."""
-        R = st["R"]
-        busy = set(busy) | st["live"]          # (the last window's centres may still be read by its launches)
-        for _ in range(R):
-            s = st["next"]
-            st["next"] = (s + 1) % R
-            if s not in busy:
-                break
-        else:
-            raise RuntimeError("context store: every slot is in use by the current window")
-        old = st["owner"][s]
-        if old is not None:
-            self._feat_cache.pop(old, None)
-        st["owner"][s] = cache_key
-        return s
 
     # ------------------------------------------------------------------ per-frame attention of the GMA aggregator
     # attn = softmax(q k^T / sqrt(128)) over the cells of ONE centre frame, q | k = att.to_qk(inp): it depends on the frame's
     # context map alone, so it is built beside the gates' context parts (_frame_context) and kept like them - in a slot of a
-    # ring, named by the frame's context cache entry, reused by every window the frame is a centre of.  Two forms, chosen by
-    # _attention_geometry for this engine and for MemFlow (update_block.attention_readout reads both): the probabilities times ATT_SCALE as ONE f16 each, the weight plane
+    # ring, named by the frame's context cache entry (FrameContext.att_slot: this ring evicts "c" entries too), reused by
+    # every window the frame is a centre of.  Two forms, chosen by _attention_geometry for this engine and for MemFlow
+    # (update_block.attention_readout reads both): the probabilities times ATT_SCALE as ONE f16 each, the weight plane
     # (hip.PlainWeight) of a long-K GEMM (2.1 GB per 1080p frame), or - small or odd frames - as split rows.
     # The read-out GEMMs are fixed launches of the replayed graph and take the plane's ADDRESS, so the window's slots are part
     # of the graph's key; the ring is therefore short (M + 2: a window's centres, the centre a prefetch adds, one spare) and a
     # sliding job comes back to the same slots, and graphs, every M + 2 fields.
     ATT_DIM = 128
-    gma = False                # (class defaults: engines that share this class's plumbing but have no such block)
-    _att_store = None
+    gma = False                # (class default: engines that share this class's plumbing but have no such block)
 
     @staticmethod
     def _attention_geometry(Pn):
@@ -738,48 +656,30 @@ class MOFNetHIP(_Holder):
 
     def _attention_store(self, dev, Pn, M):
         st = self._att_store
-        if st is None or st["key"] != (str(dev), Pn) or st["R"] < M + 2:
+        if st is None or st.key != (str(dev), Pn) or st.ring.R < M + 2:
             self._join_prefetch()
             self._graphs.clear()           # captured read-outs hold the old planes' addresses
             self._att_store = None         # (let the old planes go before the new ones are asked for)
             P8, ldA, plain = self._attention_geometry(Pn)
             R = M + 2
-            st = self._att_store = {
-                "key": (str(dev), Pn), "R": R, "next": 0, "owner": [None] * R, "live": set(), "plain": plain,
-                "P8": P8, "ldA": ldA, "serial": getattr(self, "_att_serial", 0) + 1,
-                "k": None if plain else hip.SplitWeight(Pn, self.ATT_DIM, dev),
-                "vt": None if plain else hip.SplitWeight(self.ATT_DIM, P8, dev),
-                "A": [hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE) if plain else torch.empty(Pn * ldA, device=dev)
-                      for _ in range(R)]}
-            self._att_serial = st["serial"]
+            st = self._att_store = types.SimpleNamespace(
+                key=(str(dev), Pn), ring=SlotRing("attention", R, self._feat_cache), plain=plain, P8=P8, ldA=ldA,
+                k=None if plain else hip.SplitWeight(Pn, self.ATT_DIM, dev),
+                vt=None if plain else hip.SplitWeight(self.ATT_DIM, P8, dev),
+                A=[hip.PlainWeight(Pn, ldA, dev, scale=ATT_SCALE) if plain else torch.empty(Pn * ldA, device=dev)
+                   for _ in range(R)])
         return st
-
-    def _attention_slot(self, st, cache_key, busy):
-        """The next slot of the plane ring (not one of `busy`); whoever owned it loses its context cache entry."""
-        busy = set(busy) | st["live"]
-        for _ in range(st["R"]):
-            s = st["next"]
-            st["next"] = (s + 1) % st["R"]
-            if s not in busy:
-                break
-        else:
-            raise RuntimeError("attention store: every slot is in use by the current window")
-        old = st["owner"][s]
-        if old is not None and old != cache_key:
-            self._feat_cache.pop(old, None)
-        st["owner"][s] = cache_key
-        return s
 
     def _build_attention(self, st, slot, cx, h8, w8, Pn, P, dev, AF):
         """The attention of one frame (context map cx, [Pn][256] rows) into slot `slot` of the store."""
-        AD, ldA = self.ATT_DIM, st["ldA"]
+        AD, ldA = self.ATT_DIM, st.ldA
         wgt, _ = P["att.to_qk"]
         nmq = self._nm("att.to_qk")
-        if st["plain"]:
+        if st.plain:
             # q | k as f32 rows of one map, then the plane in one call: scores and softmax on chip (csrc/attention.hip)
             qk = self._buf("att_qk", Pn * 2 * AD, dev)
             hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, 2 * AD, 1, 1, qk, 2 * AD, in0_off=128, in_fmt=AF, mfma=nmq)
-            hip.attention_plane(qk, qk, Pn, st["A"][slot], score_scale=1.0 / float(AD) ** 0.5, d=AD, ld_q=2 * AD, ld_k=2 * AD,
+            hip.attention_plane(qk, qk, Pn, st.A[slot], score_scale=1.0 / float(AD) ** 0.5, d=AD, ld_q=2 * AD, ld_k=2 * AD,
                                 k_off=AD, workspace=self._buf("att_stats", 2 * Pn, dev))
             return
         # small or odd frames: q (rows 0..127 of to_qk) as the score GEMM's split-row operand, k (rows 128..255) as f32 for its
@@ -788,18 +688,19 @@ class MOFNetHIP(_Holder):
         kmap = self._buf("att_k", Pn * AD, dev)
         hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, AD, 1, 1, qmap, AD, in0_off=128, in_fmt=AF, out_fmt=AF, mfma=nmq)
         hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, None, AD, 1, 1, kmap, AD, in0_off=128, weight_off=AD, in_fmt=AF, mfma=nmq)
-        kw_ = st["k"].fill(kmap, scale=16.0)
+        kw_ = st.k.fill(kmap, scale=16.0)
         scores = self._buf("att_scores", Pn * ldA, dev)
         hip.conv2d(qmap, AD, AD, 1, 1, Pn, kw_, None, Pn, 1, 1, scores, ldA, out_scale=1.0 / float(AD) ** 0.5, in_fmt=AF)
-        hip.softmax_rows_s16(scores, Pn, Pn, ldA, st["A"][slot], ldA, scale=ATT_SCALE)
+        hip.softmax_rows_s16(scores, Pn, Pn, ldA, st.A[slot], ldA, scale=ATT_SCALE)
 
     # ------------------------------------------------------------------ per-frame motion features of iteration 0
     # At iteration 0 the flow is zero and the lookups, convc1, convc2, the flow half and encoder.conv act on every centre
     # frame by itself: the `mf` columns of the state after them depend on the frame and its two neighbours only, and a frame
     # is a centre of M consecutive windows of a sliding job.  Each centre's rows ([cells][128] floats in the update block's
-    # activation format, 16.6 MB at 1080p) are kept in a ring of slots (Iter0Ring); a window whose older centres all have
-    # theirs runs those five launches of iteration 0 on its newest centre alone ("warm").  The captured launch that moves the
-    # rows (vfml_window_seed) reaches the slots through device cells, so one graph serves every window.
+    # activation format, 16.6 MB at 1080p) are kept in a ring of slots (frame_store.Iter0Ring: the entry's key names the
+    # frame AND its two neighbours); a window whose older centres all have theirs runs those five launches of iteration 0
+    # on its newest centre alone ("warm").  The captured launch that moves the rows (vfml_window_seed) reaches the slots
+    # through device cells, so one graph serves every window.
     # Eight slots: a sliding job takes one per field and reads the two taken before it.  Jobs that interleave more streams
     # of windows than that (the six tiles of a 4K frame walked frame by frame) find their entries evicted and run cold - as
     # before, plus the 25 us store.
@@ -807,14 +708,14 @@ class MOFNetHIP(_Holder):
     iter0_store = True       # False: every window computes iteration 0 for all its centres (tests, A/B runs)
 
     def _iter0_store(self, dev, Pn, M):
-        st = getattr(self, "_it0_store", None)
-        if st is None or st["key"] != (str(dev), Pn) or st["ring"].R < M + 1:
+        st = self._it0_store
+        if st is None or st.key != (str(dev), Pn) or st.ring.R < M + 1:
             self._join_prefetch()
             for k in [k for k in self._feat_cache if k[0] == "m"]:     # (entries of another store)
                 del self._feat_cache[k]
             R = max(self.ITER0_RING, M + 1)
-            st = self._it0_store = {"key": (str(dev), Pn), "ring": Iter0Ring(R, self._feat_cache),
-                                    "S": torch.empty(R * Pn * 128, device=dev)}
+            st = self._it0_store = types.SimpleNamespace(key=(str(dev), Pn), ring=Iter0Ring(R, self._feat_cache),
+                                                         S=torch.empty(R * Pn * 128, device=dev))
         return st
 
     # ------------------------------------------------------------------ graph replay of the iteration body
@@ -1360,14 +1261,13 @@ class MOFNetHIP(_Holder):
 
     def _frame_context(self, src, sel, keys, H, W, P, dev, Pn, M=1):
         """Context maps (tanh | relu halves, [Pn*256] f32) of frames `sel`, and the context part of their gate convolutions:
-        out[j] = (map, {gate: view of the frame's slot in the gate's store}, slot, store serial); with the GMA aggregator
-        the slot of the frame's attention in its store and that store's serial follow."""
+        {j: frame_store.FrameContext}, with the frame's attention slot under the GMA aggregator."""
         out, todo = {}, []
         st = self._context_store(dev, Pn, max(M, len(sel)))
         att = self._attention_store(dev, Pn, max(M, len(sel))) if self.gma else None
         for j in sel:
             ent = self._cache_get("c", keys[j]) if keys is not None else None
-            if ent is not None and ent[3] == st["serial"] and (att is None or ent[5] == att["serial"]):
+            if ent is not None and ent.serial == st.ring.serial and (att is None or ent.att_serial == att.ring.serial):
                 out[j] = ent
             else:
                 todo.append(j)
@@ -1381,29 +1281,28 @@ class MOFNetHIP(_Holder):
             (self._twins_encoder if self.twins else self._encoder)("cnet", frames, m, H, W, P, dev, ctx, 256, 0, hip.EPI_TANH_RELU,
                                                                    self.hidden_dim, out_fmt=AF)
             h8, w8 = H // 8, W // 8
-            R, Mst = st["R"], st["M"]
+            R, Mst = st.ring.R, st.M
             for i, j in enumerate(todo):
                 cx = ctx[i * Pn * 256:(i + 1) * Pn * 256]
-                busy = {e[2] for e in out.values()}
-                slot = self._context_slot(st, ("c", keys[j]) if keys is not None else None, busy)
+                owner = ("c", keys[j]) if keys is not None else None
+                slot = st.ring.take(owner, {e.slot for e in out.values()})
                 # context part of the GRU gate convolutions (+ bias), per pass: [z|r] (256) and q (128), into the frame's slot
                 add = {}
                 for k, (kh, kw) in () if self.sk else (("1", (1, 5)), ("2", (5, 1))):      # (the SK block has no gates)
                     for g, co in (("zr", 256), ("q", 128)):
                         wgt, b = P[f"update_block.gru.conv{g}{k}.ctx"]
-                        S = st["S"][g + k]
+                        S = st.S[g + k]
                         hip.conv2d(cx, 128, 256, 1, h8, w8, wgt, b, co, kh, kw, S, co, in0_off=128, out_off=slot * Pn * co,
                                    pad_h=kh // 2, pad_w=kw // 2, in_fmt=AF,
                                    mfma=self._nm(f"update_block.gru.conv{g}{k}.ctx") if self._split() else 3)
                         add[g + k] = S[slot * Pn * co:(slot + 1) * Pn * co]
                         if slot < Mst - 1:          # the ring's first slots again behind it: a window that wraps stays consecutive
                             S[(R + slot) * Pn * co:(R + slot + 1) * Pn * co].copy_(add[g + k])
-                ent = (cx, add, slot, st["serial"])
+                ent = FrameContext(cx, add, slot, st.ring.serial)
                 if att is not None:
-                    aslot = self._attention_slot(att, ("c", keys[j]) if keys is not None else None,
-                                                 {e[4] for e in out.values()})
+                    aslot = att.ring.take(owner, {e.att_slot for e in out.values()})
                     self._build_attention(att, aslot, cx, h8, w8, Pn, P, dev, AF)
-                    ent += (aslot, att["serial"])
+                    ent = ent._replace(att_slot=aslot, att_serial=att.ring.serial)
                 out[j] = ent
                 if keys is not None:
                     self._cache_put("c", keys[j], out[j])
@@ -1430,7 +1329,7 @@ class MOFNetHIP(_Holder):
         MP = M * h * w
         GLD, cols = self._state_columns()
         if self.gma and self._att_store is not None:
-            self._att_store["live"] = set()     # (the last window's read-outs are ahead of this one on the stream)
+            self._att_store.ring.live = set()     # (the last window's read-outs are ahead of this one on the stream)
 
         def rows(name, c):
             return self._buf(name, MP * c, dev)
@@ -1453,14 +1352,14 @@ class MOFNetHIP(_Holder):
         if (self.iter0_store and not self.sk and keys is not None and self._split() and not self.tri_frame and M >= 2
                 and cfg.decoder_depth >= 1 and not (pick_only and cfg.decoder_depth + 1 < M)):
             it0 = self._iter0_store(dev, s.Pn, M)
-            warm, seeds, it0_new = it0["ring"].plan(keys, tail=(R,))
+            warm, seeds, it0_new = it0.ring.plan(keys, tail=(R,))
             self.iter0_stats["warm" if warm else "cold"] += 1
             self.iter0_last = (warm, [slot for slot, _ in seeds])
         else:
             warm, seeds, it0_new = False, [(None, hip.SEED_NONE)] * M, []
         seed_cells = self._buf("seed_cells", 64, dev, torch.int64)
         hip.ptr_table_set(seed_cells, [v for i, (slot, mode) in enumerate(seeds) for v in
-                                       (ctx[i + 1][0], it0["S"][slot * s.Pn * 128:] if slot is not None else 0, mode)])
+                                       (ctx[i + 1].map, it0.S[slot * s.Pn * 128:] if slot is not None else 0, mode)])
         return it0, warm, it0_new, seed_cells
 
     def _gate_addends(self, ctx, dev, Pn, M):
@@ -1468,25 +1367,25 @@ class MOFNetHIP(_Holder):
         # the centre frames' slots, consecutive in a sliding job (through the mirror when the ring wraps) - else gathered
         # into the store's spare slots
         st = self._ctx_store
-        RING, Mst = st["R"], st["M"]
-        slots = [ctx[c][2] for c in range(1, M + 1)]
-        st["live"] = set(slots)
-        first = slots[0]
+        RING, Mst = st.ring.R, st.M
+        slots = [ctx[c].slot for c in range(1, M + 1)]
+        st.ring.live = set(slots)
+        first = window_base(slots, RING, Mst - 1)
         # (the exact-f32 kernel takes the pointer itself - a captured launch needs it fixed: always the gathered copy)
         # (A/B switch: VFML_CTX_GATHER=1 gathers every window, as round 2 did)
-        if not self.sk and (not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or
-                            not all(s == first + i or (first + i >= RING and s == first + i - RING and s < Mst - 1)
-                                    for i, s in enumerate(slots))):
+        if self.sk:
+            first = slots[0]
+        elif not self._split() or os.environ.get("VFML_CTX_GATHER", "0") == "1" or first is None:
             first = RING + Mst - 1
             for i, c in enumerate(range(1, M + 1)):
                 for name, co in self.CTX_GATES:
-                    st["S"][name][(first + i) * Pn * co:(first + i + 1) * Pn * co].copy_(ctx[c][1][name])
-        gate_add = {name: st["S"].get(name) for name, _ in self.CTX_GATES}
+                    st.S[name][(first + i) * Pn * co:(first + i + 1) * Pn * co].copy_(ctx[c].addends[name])
+        gate_add = {name: st.S.get(name) for name, _ in self.CTX_GATES}
         gate_off = {name: first * Pn * co for name, co in self.CTX_GATES}
         gate_ind = None
         if self._split() and not self.sk:      # (the exact-f32 kernel takes the pointer itself)
             cells = self._buf("gate_add_cells", 8, dev, torch.int64)
-            hip.ptr_table_set(cells, [st["S"][name][gate_off[name]:] for name, _ in self.CTX_GATES])
+            hip.ptr_table_set(cells, [st.S[name][gate_off[name]:] for name, _ in self.CTX_GATES])
             gate_ind = {name: (cells, i) for i, (name, _) in enumerate(self.CTX_GATES)}
         return gate_add, gate_off, gate_ind
 
@@ -1507,8 +1406,8 @@ class MOFNetHIP(_Holder):
     def _gma_readout(self, s, win, ng):
         """mg = mf + gamma * attn . to_v(mf), per centre frame with its own attention, on the ng centres whose GRU runs."""
         att = self._att_store
-        update_block.attention_readout(s, "update_block.aggregator.to_v", [att["A"][k] for k in win.att_slots[:ng]],
-                                       att["plain"], att["ldA"], att["P8"], self._gamma, ATT_SCALE, s.MF, s.MG, win.readout)
+        update_block.attention_readout(s, "update_block.aggregator.to_v", [att.A[k] for k in win.att_slots[:ng]],
+                                       att.plain, att.ldA, att.P8, self._gamma, ATT_SCALE, s.MF, s.MG, win.readout)
 
     def _iteration(self, s, win, it, ng, nm, branch):
         """One iteration of the plain update block: GRU + flow head on `ng` centres, lookups + motion encoder on `nm`."""
@@ -1619,10 +1518,9 @@ class MOFNetHIP(_Holder):
             win = types.SimpleNamespace(M=M, dev=dev, att_slots=(), readout=None)
             if self.gma:
                 att = self._att_store
-                win.att_slots = tuple(ctx[c][4] for c in range(1, N - 1))
-                att["live"] = set(win.att_slots)
-                win.readout = update_block.readout_scratch(self._buf, dev, MP, Pn, self.ATT_DIM, att["ldA"], att["plain"],
-                                                           att["vt"])
+                win.att_slots = tuple(ctx[c].att_slot for c in range(1, N - 1))
+                att.ring.live = set(win.att_slots)
+                win.readout = update_block.readout_scratch(self._buf, dev, MP, Pn, self.ATT_DIM, att.ldA, att.plain, att.vt)
             it0, win.warm, it0_new, win.seed_cells = self._seed_plan(s, ctx, keys, dev, M, R, pick_only)
             win.gates = self._gate_addends(ctx, dev, Pn, M)
             win.sk_ws = self._sk_workspace(MP, dev) if self.sk else None
@@ -1689,7 +1587,7 @@ class MOFNetHIP(_Holder):
                 self._run_body(body, gkey, dev)
             except BaseException:
                 if it0_new:      # (slots promised to this window's centres that may not have been filled)
-                    it0["ring"].forget(it0_new)
+                    it0.ring.forget(it0_new)
                 raise
             up = up_fixed.clone().view(nflows, H, W, 2)          # the caller owns its field; the fixed buffer is reused
             # [2M,H,W,2] stored HWC; expose the reference's [B, 2M, 2, H, W] as a view ([1, 1, 2, H, W] of a pick)
